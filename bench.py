@@ -2,7 +2,13 @@
 """bench.py -- simplex pivots/sec on a fp64 4096 x 8192 tableau (BASELINE.json's metric), batched
 small-LP throughput sharded over the GPUs of one node, and one leg per remaining BASELINE config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full [--legs a,b,...]
+
+A plain run is leg 1 alone: set-up, warm-up, K timed steps, one JSON line. --full adds everything else:
+the other legs, the CPU baselines, the self-checks against the reference fixtures (tests/golden), the
+roofline figures from HIP events on the timed sweeps, and RCCL's fixed cost at world size 1.
+--dump-outputs DIR writes what leg 1's last timed step computed to DIR/<name>.npy (see dump_outputs).
 
 With N > 1 and no RANK in the environment bench.py starts its own N ranks (torch.distributed.run on
 127.0.0.1, one rank per GPU, backend nccl = RCCL) BEFORE anything touches a GPU and relays rank 0's
@@ -199,11 +205,10 @@ def golden(name):
     return json.load(open(os.path.join(ROOT, "tests", "golden", name)))
 
 
-def selfcheck_bench_lp(lp):
-    """The device state the LAST timed step left (3840 pivots after xpg_lp_begin) against the real reference's
-    TwoStageMethod(max_iter = 3840) on the same LP: whole tableau, objective row, basis."""
+def selfcheck_bench_lp(got):
+    """The device state the LAST timed step left (3840 pivots after xpg_lp_begin, as lp.read() returns it) against the
+    real reference's TwoStageMethod(max_iter = 3840) on the same LP: whole tableau, objective row, basis."""
     rec = [r for r in golden("g11_bench_lp.json")["bench_lp"] if r["K"] == PIVOTS_PER_STEP][0]
-    got = lp.read()
     bad = []
     if checksum(got["tab"]) != rec["tab"]:
         bad.append("tableau")
@@ -219,6 +224,22 @@ def selfcheck_bench_lp(lp):
                 against="tests/golden/g11_bench_lp.json: xcom::SIX<FloatMat,Float>::TwoStageMethod(max_iter=%d) of the real "
                         "reference on this LP (tools/gen_golden_bench.py)" % PIVOTS_PER_STEP,
                 result="bit-identical")
+
+
+DUMP_ROWS, DUMP_SEED = 512, 20240611             # tableau rows written by --dump-outputs (512 x 8192 fp64 = 32 MiB)
+
+
+def dump_outputs(got, d):
+    """--dump-outputs: the state leg 1's last timed step left (lp.read()), as float64 .npy files for comparing two builds.
+    The whole tableau is 268 MB, so it goes out as a fixed sample of DUMP_ROWS rows (the same rows in every run) plus its
+    whole right-hand-side column; the objective row and both basis maps go out whole (indices as exact float64)."""
+    os.makedirs(d, exist_ok=True)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(got["tab"].shape[0], DUMP_ROWS, replace=False))
+    arrays = dict(tableau_rows=got["tab"][rows], tableau_rhs_column=got["tab"][:, got["rhs"]], objective_row=got["tgtf"],
+                  eq2bv=got["eq2bv"].astype(np.float64), bv2eq=got["bv2eq"].astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def selfcheck_batched(fam, d_st, d_v, d_sol, gathered):
@@ -262,7 +283,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated subset of " + ",".join(LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other legs, CPU baselines, self-checks against the reference fixtures, "
+                         "roofline figures (HIP events on the timed sweeps) and RCCL's fixed cost")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, about 32 MiB)")
+    ap.add_argument("--legs", default=None,
+                    help="comma-separated subset of %s (default: pivots; with --full: all); legs other than pivots need --full"
+                         % ",".join(LEGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref-baseline", action="store_true",
                     help="skip timing the real reference build (oracle/_ref, ~1 s on the GPU box's host)")
@@ -278,8 +306,16 @@ def main():
     ap.add_argument("--stub-solver", action="store_true",
                     help="ranks fabricate their shard's records instead of solving (CPU test of the N > 1 path)")
     a = ap.parse_args()
-    legs = set(x for x in a.legs.split(",") if x)
-    assert legs <= set(LEGS), "unknown leg in --legs"
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    legs = set(x for x in (a.legs or (",".join(LEGS) if a.full else "pivots")).split(",") if x)
+    if not legs <= set(LEGS):
+        ap.error("unknown leg in --legs: %s" % ",".join(sorted(legs - set(LEGS))))
+    if not a.full and legs != {"pivots"}:
+        ap.error("without --full a run is leg 1 (pivots) alone: --legs %s needs --full" % a.legs)
+    if a.dump_outputs and "pivots" not in legs:
+        ap.error("--dump-outputs writes leg 1 (pivots): add it to --legs")
+    no_events = a.no_events or not a.full
 
     if (a.gpus > 1 or a.force_dist) and "RANK" not in os.environ:
         sys.exit(spawn_ranks(a, sys.argv[1:]))          # nothing has touched a GPU yet
@@ -292,7 +328,7 @@ def main():
     stub = a.stub_solver
     cpu = None
     use_dist = world > 1 or a.force_dist
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not stub:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not stub:
         cpu = cpu_baselines(legs, a.no_ref_baseline)     # forks: before torch / HIP are initialised in this process
 
     # the rank's host thread (and the pinned staging it allocates from here on) onto the NUMA node of its GPU -- from sysfs,
@@ -382,13 +418,13 @@ def main():
         barrier()
         batches = a.steps * (PIVOTS_PER_STEP // BLOCK)
         stride = max(1, batches // 320)                 # ~320 sampled sweep launches spread over the region
-        ctx.profile_begin(0 if a.no_events else batches // stride + 1, stride)
+        ctx.profile_begin(0 if no_events else batches // stride + 1, stride)
         sweeps_full = sweeps_part = 0
         pivots = 0
         t0 = time.perf_counter()
         for _ in range(a.steps):
             run_step()
-            if not a.no_events:                         # device counters of this step (the iterate call has
+            if not no_events:                           # device counters of this step (the iterate call has
                 f, p = lp.counters()                    # synchronised already: no extra round trip inside)
                 sweeps_full += f
                 sweeps_part += p
@@ -454,8 +490,13 @@ def main():
                                 "stages the batch's pivots: latency-bound (two L2 hand-offs and two gathers per stage), no byte or "
                                 "flop roofline applies; us per stage from the whole-loop time",
                            us_per_stage=round((per_pivot_s * 1e6 * ppl - sweep_avg_s * 1e6) / ppl, 3) if ppl else None))
-        if rank == 0:
-            out["self_check"] = {"pivots": selfcheck_bench_lp(lp)}      # outside the timed region
+        if rank == 0 and (a.full or a.dump_outputs):    # outside the timed region
+            got = lp.read()
+            if a.dump_outputs:
+                out["outputs"] = dict(dir=a.dump_outputs, arrays=dump_outputs(got, a.dump_outputs))
+            if a.full:
+                out["self_check"] = {"pivots": selfcheck_bench_lp(got)}
+            del got
         lp.close()
 
     # ---- leg 2: batched 32 x 64 LPs, sharded across ranks, one all_gather at the end ----------------
@@ -680,10 +721,12 @@ def main():
             for leg in ("cfg2b", "rational"):
                 if leg in out and "self_check" in out[leg]:
                     out["self_check"][leg] = out[leg].pop("self_check")
-        out["cpu_baseline"] = cpu
-        if cpu is None and world > 1:
-            out["cpu_baseline_note"] = "timed on rank 0 of the N = 1 run only (the contract's rule); not repeated at N > 1"
-        print(json.dumps(out))
+        if a.full:
+            out["cpu_baseline"] = cpu
+            if cpu is None and world > 1:
+                out["cpu_baseline_note"] = "timed on rank 0 of the N = 1 run only (the contract's rule); not repeated at N > 1"
+        C.CDLL(None).fflush(None)                       # what RCCL printed through C stdio goes out before the line, not after it
+        print(json.dumps(out), flush=True)
     if ctx is not None:
         ctx.close()
     if dist is not None:

@@ -179,7 +179,7 @@ def test_bench_two_ranks_real_solver_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
-                        "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
+                        "--full", "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -203,7 +203,7 @@ def test_bench_rccl_at_world_size_one():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--backend", "nccl",
-                        "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
+                        "--full", "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -127,7 +127,7 @@ def test_bench_spawns_its_own_ranks_and_gathers():
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--stub-solver", "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
+                        "--stub-solver", "--full", "--legs", "batched,sharded", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -152,7 +152,7 @@ def test_bench_without_gpus_fails_loudly():
     from xpoly_amd import _capi
     if _capi.lib().xpg_device_count() > 0:
         pytest.skip("a GPU is present")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--legs", "batched",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--legs", "batched",
                         "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode != 0

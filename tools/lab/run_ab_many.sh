@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 LEGS=${1:-pivots,cfg2b}; shift
 SOS=${@:-$(ls tools/_build/libxpoly_*.so | grep -v stamps)}
 for rep in 1 2; do for so in $SOS; do
-  XPG_SO_PATH=$PWD/$so python bench.py --legs $LEGS --no-cpu-baseline 2>/dev/null | python -c "
+  XPG_SO_PATH=$PWD/$so python bench.py --full --legs $LEGS --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().split('\n') if l.startswith('{')][-1])
 o=['$so']

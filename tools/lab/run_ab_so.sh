@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 LEGS=${1:-batched}
 for rep in 1 2; do for so in xpoly_amd/libxpoly_amd.so tools/_build/libxpoly_prev.so; do
-  XPG_SO_PATH=$PWD/$so python bench.py --legs $LEGS --no-cpu-baseline 2>/dev/null | python -c "
+  XPG_SO_PATH=$PWD/$so python bench.py --full --legs $LEGS --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().split('\n') if l.startswith('{')][-1])
 o=['$so']

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 export XPG_SO_PATH=$GRAFT_REPO_ROOT/xpoly_amd/libxpoly_amd_hooks.so
 for rep in 1 2; do for w in 5 4; do
-  XPG_BATCH_WAVES=$w python bench.py --legs batched --no-cpu-baseline 2>/dev/null | python -c "
+  XPG_BATCH_WAVES=$w python bench.py --full --legs batched --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])['batched']['families']
 print('LPs per CU $w:', {k: v['lps_per_s'] for k, v in d.items()})"

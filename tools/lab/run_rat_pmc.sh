@@ -6,7 +6,7 @@ O=$R/gpurun_out/r4rat
 rm -rf $O; mkdir -p $O
 for g in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU" "SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU" "SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   n=$(echo $g | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --pmc $g --output-format csv -d $O/pmc_$n -- python3 $R/bench.py --legs rational --no-cpu-baseline > $O/$n.log 2>&1
+  rocprofv3 --pmc $g --output-format csv -d $O/pmc_$n -- python3 $R/bench.py --full --legs rational --no-cpu-baseline > $O/$n.log 2>&1
 done
 python3 - "$O" <<'PY'
 import csv, glob, json, os, sys, collections
@@ -19,7 +19,7 @@ for f in glob.glob(os.path.join(O, "**", "*counter_collection.csv"), recursive=T
         a = acc[(k, row["Counter_Name"])]; a[0] += 1; a[1] += float(row["Counter_Value"])
 per = collections.defaultdict(dict)
 for (k, c), (n, s) in acc.items(): per[k][c] = s / n; per[k]["launches"] = n
-out = dict(command="rocprofv3 --pmc <4 counters per pass> --output-format csv -- python3 bench.py --legs rational --no-cpu-baseline (tools/lab/run_rat_pmc.sh); averages per launch over the 16 pivot positions of 6 solves",
+out = dict(command="rocprofv3 --pmc <4 counters per pass> --output-format csv -- python3 bench.py --full --legs rational --no-cpu-baseline (tools/lab/run_rat_pmc.sh); averages per launch over the 16 pivot positions of 6 solves",
            units="SQ_*_CYCLES / SQ_ACTIVE_* / SQ_WAIT_* in quad-cycles summed over the chip's 1024 SIMDs; GRBM_GUI_ACTIVE in cycles summed over the 8 XCDs", kernels=per)
 for k, d in per.items():
     if "GRBM_GUI_ACTIVE" in d and d["GRBM_GUI_ACTIVE"] > 0:

@@ -8,7 +8,7 @@ python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_pivots -- python3 $R/bench.py --steps 20 --warmup 5 --legs pivots --no-cpu-baseline > $O/ks_pivots.log 2>&1
 cp $(find $O/ks_pivots -name "*kernel_stats.csv" | head -1) $O/kernel_stats_pivots.csv; head -6 $O/kernel_stats_pivots.csv | cut -c1-150
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_legs -- python3 $R/bench.py --legs batched,cfg2b,rational,mip,lineq --no-cpu-baseline > $O/ks_legs.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_legs -- python3 $R/bench.py --full --legs batched,cfg2b,rational,mip,lineq --no-cpu-baseline > $O/ks_legs.log 2>&1
 cp $(find $O/ks_legs -name "*kernel_stats.csv" | head -1) $O/kernel_stats_other_legs.csv; head -8 $O/kernel_stats_other_legs.csv | cut -c1-150
 find $O -name "*kernel_trace.csv" -delete
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -18,7 +18,7 @@ done
 cd $R && python3 tools/pmc_summarise.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_hbm_traffic.json k_blk_sweep_full
 cd /tmp
 for c in VALUBusy SALUBusy; do
-  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --legs rational --no-cpu-baseline > $O/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --legs rational --no-cpu-baseline > $O/pmc_$c.log 2>&1
   tail -2 $O/pmc_$c.log | cut -c1-200
 done
 cd $R && python3 - <<'PY'
