@@ -139,7 +139,7 @@ int  xpg_lp_chain_aborts(xpg_lp * lp, unsigned * aborts, int * chain_off, unsign
 /* ... and how many of the launches that passed did their batch's first stage themselves (no pick / prep launches for it). */
 int  xpg_lp_chain_folds(xpg_lp * lp, unsigned * folds);
 /* Which loop and which kernel instances the handle runs the LP in its current shape with (evidence for bench.py's `shapes`
- * leg; no reference counterpart).  out[0..n-1], n <= 10: loop (0 pipelined, 1 serial, 3 blocked), pivots per blocked pass,
+ * leg; no reference counterpart).  out[0..n-1], n <= 10: loop (0 pipelined, 3 blocked), pivots per blocked pass,
  * chain form (0 launch-per-stage kernels, 1 one persistent launch on one XCD, 2 the same spread over the chip), columns of
  * the entering column's line kept in LDS (0 / 8 / 16), rows per workgroup of the pass (16 / 32), leading dimension, chain
  * workers, pick workers, prep workers, LDS bytes per chain worker. */

@@ -125,19 +125,18 @@ def test_full_size_tableau_properties(ctx, port):
     assert np.array_equal(eq2bv, want["eq2bv"])
 
 
-@needs_hooks
 def test_full_size_loops_against_each_other_and_oracle(port, monkeypatch):
-    """4096 x 8192 fp64 under full load: the three device loops -- blocked (16 pivots staged per
-    sweep, the default at this size), pipelined (pick workgroups inside the sweep launch) and the
-    serial three-launch loop -- and the CPU oracle must agree bit for bit: same (entering, leaving)
-    trace, same basis, same tableau -- ALL 4096 x 8192 entries, between the GPU loops after 300 and
+    """4096 x 8192 fp64 under full load: the two device loops -- blocked (pivots staged per sweep,
+    the default at this size) and pipelined (pick workgroups inside the sweep launch) -- and the CPU
+    oracle must agree bit for bit: same (entering, leaving) trace, same basis, same tableau -- ALL
+    4096 x 8192 entries, between the GPU loops after 300 and
     after 2000 pivots and against the oracle after 300 (the chunks 7 + 93 + 200 also end batches early,
     so the short-batch sweep kernels are on the path)."""
     import xpoly_amd
     m, n, K = 4096, 4095, 300
     leq, tg = gen.hard_lp_f64(m, n)
     got = {}
-    for mode in ("block", "pipe", "serial"):
+    for mode in ("block", "pipe"):
         monkeypatch.setenv("XPG_LOOP", mode)             # read when the context is created
         c = xpoly_amd.Context(0)
         lp = xpoly_amd.DeviceLP(c, F64, leq, tg)
@@ -149,14 +148,13 @@ def test_full_size_loops_against_each_other_and_oracle(port, monkeypatch):
         got[mode + "+"] = (lp.read(), lp.trace().copy(), lp.pivots_done())
         lp.close(); c.close()
     for tag, total in (("", K), ("+", 2000)):
-        b, tb, nb = got["serial" + tag]
-        for mode in ("block", "pipe"):
-            a, ta, na = got[mode + tag]
-            assert na == nb == total and np.array_equal(ta, tb), (mode, tag)
-            for k in ("tab", "tgtf"):
-                assert np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)), (mode, tag, k)
-            for k in ("nvset", "bvset", "bv2eq", "eq2bv"):
-                assert np.array_equal(a[k], b[k]), (mode, tag, k)
+        a, ta, na = got["block" + tag]
+        b, tb, nb = got["pipe" + tag]
+        assert na == nb == total and np.array_equal(ta, tb), tag
+        for k in ("tab", "tgtf"):
+            assert np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)), (tag, k)
+        for k in ("nvset", "bvset", "bv2eq", "eq2bv"):
+            assert np.array_equal(a[k], b[k]), (tag, k)
     a, ta, _ = got["block"]
     want = port.two_stage(F64, leq, tg, K)               # ~5 s of CPU: the whole tableau, not a sample
     assert a["tab"].shape == want["tab"].shape == (m, m + n + 1)
@@ -278,16 +276,15 @@ def test_batch_sizes_ragged_and_single(ctx, port):
                 assert status[b] == want[0] and np.array_equal(v[b], want[1])
 
 
-@needs_hooks
 def test_wide_tableau_keeps_the_chain(port, monkeypatch):
     """W >= 16 384 (here 1024 x 17 025: 267 prep workers, 268 partial slots -- two polling rounds per pick) used to drop
-    silently to the launch-per-stage kernels; the chain now runs there too, and its results are the serial loop's and
+    silently to the launch-per-stage kernels; the chain now runs there too, and its results are the pipelined loop's and
     the oracle's bit for bit."""
     import xpoly_amd
     m, n, K = 1024, 16000, 160
     leq, tg = gen.hard_lp_f64(m, n)
     got = {}
-    for mode in ("block", "serial"):
+    for mode in ("block", "pipe"):
         monkeypatch.setenv("XPG_LOOP", mode)
         c = xpoly_amd.Context(0)
         lp = xpoly_amd.DeviceLP(c, F64, leq, tg)
@@ -298,7 +295,7 @@ def test_wide_tableau_keeps_the_chain(port, monkeypatch):
         got[mode] = (lp.read(), lp.trace().copy(), lp.pivots_done(), lp.chain_runs, aborts)
         lp.close(); c.close()
     a, ta, na, runs, aborts = got["block"]
-    b, tb, nb, _, _ = got["serial"]
+    b, tb, nb, _, _ = got["pipe"]
     assert runs >= 5 and aborts == 0, (runs, aborts)     # the persistent launch really ran (2 x 24 + 2, then 4 x 24 + 14 pivots)
     assert na == nb == K and np.array_equal(ta, tb)
     for k in ("tab", "tgtf"):

@@ -330,7 +330,7 @@ def test_rational_pipelined_loop_with_several_pick_workgroups(ctx, port, m, n, s
                 assert np.array_equal(got["maxv"], want["maxv"]) and np.array_equal(got["sol"], want["sol"])
 
 
-SERIAL_R32_SCRIPT = r"""
+PIPE_R32_SCRIPT = r"""
 import json, sys, zlib
 import numpy as np
 sys.path.insert(0, sys.argv[1])
@@ -349,16 +349,16 @@ print(json.dumps(dict(tab=checksum(got["tab"]), tgtf=checksum(got["tgtf"]), eq2b
 """
 
 
-def test_cfg4_rational_serial_loop_against_the_reference():
-    """XPG_R32_LOOP=serial (the three-launch pick -> prep -> sweep loop kept for A/B runs) reaches the same state as the
-    real reference on the 1024 x 2048 LP after 16 pivots. The switch is read once per process, hence a process of its own."""
+def test_cfg4_rational_two_launch_loop_against_the_reference():
+    """XPG_R32_LOOP=pipe (the two-launch prep -> sweep loop; the fused one-launch loop is the default at this size) reaches
+    the same state as the real reference on the 1024 x 2048 LP after 16 pivots. The switch is read once per process, hence
+    a process of its own."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rec = [r for r in GOLD["g4_large"] if r["K"] == 16][0]
-    from conftest import hooks_env
-    env = hooks_env(XPG_R32_LOOP="serial")               # (the serial loop exists in the -DXPG_TEST_HOOKS build only)
-    r = subprocess.run([sys.executable, "-c", SERIAL_R32_SCRIPT, root], capture_output=True, text=True, timeout=600, env=env)
+    env = dict(os.environ, XPG_R32_LOOP="pipe")
+    r = subprocess.run([sys.executable, "-c", PIPE_R32_SCRIPT, root], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["tab"] == rec["tab"] and out["tgtf"] == rec["tgtf"] and out["eq2bv"] == rec["eq2bv"]

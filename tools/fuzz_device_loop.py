@@ -1,5 +1,5 @@
-"""GPU fuzz (one-off, not part of the suite): the device-resident loop (pipelined for fp64, serial
-for rational) against the CPU oracle on many small LPs of the two families that exercise its rare
+"""GPU fuzz (one-off, not part of the suite): the device-resident loop (the loop the handle chooses
+for each LP, fp64 and rational) against the CPU oracle on many small LPs of the two families that exercise its rare
 branches -- dependence-test-like integer data (ties, zero pivots, pair-table exhaustion) and random
 problems with phase 1 -- comparing status, tableau, objective row and basis bit for bit.
 

@@ -21,4 +21,4 @@ for fam in (0, 1):
     for _ in range(3): run()
     dt = (time.perf_counter() - t0) / 3
     piv = int(d_piv.sum().item())
-    print("fam", fam, "threads", os.environ.get("XPG_BATCH_THREADS", "default"), "LPs/s %.0f" % (nb / dt), "pivots/s %.1fM" % (piv / dt / 1e6), "ms %.2f" % (dt * 1e3), "checksum", int(d_st.sum().item()), float(d_v.sum().item()))
+    print("fam", fam, "LPs/s %.0f" % (nb / dt), "pivots/s %.1fM" % (piv / dt / 1e6), "ms %.2f" % (dt * 1e3), "checksum", int(d_st.sum().item()), float(d_v.sum().item()))

@@ -15,7 +15,7 @@ acc = collections.defaultdict(lambda: [0, 0.0])
 for f in glob.glob(os.path.join(O, "**", "*counter_collection.csv"), recursive=True):
     for row in csv.DictReader(open(f)):
         k = row["Kernel_Name"].split("(")[0].replace("void xpg::", "").replace("xpg::", "")
-        if not any(s in k for s in ("k_pipe_fused_r32", "k_fused_generic", "k_pipe_sweep_r32", "k_pipe_prep", "k_update_r32", "k_pick", "k_prep")): continue
+        if not any(s in k for s in ("k_pipe_fused_r32", "k_fused_generic", "k_pipe_sweep_r32", "k_pipe_prep", "k_update_r32", "k_prep")): continue
         a = acc[(k, row["Counter_Name"])]; a[0] += 1; a[1] += float(row["Counter_Value"])
 per = collections.defaultdict(dict)
 for (k, c), (n, s) in acc.items(): per[k][c] = s / n; per[k]["launches"] = n

@@ -18,8 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "xpoly_amd.hip")
 OUT = os.path.join(HERE, "libxpoly_amd.so")
 OBJ = os.path.join(HERE, "csrc", "_obj")
-# the same sources with -DXPG_TEST_HOOKS: fault injection, forced routes, debug prints and the lab's A/B knobs are compiled
-# in (scalar.hip.h xpg_hook). Loaded only by the tests that need a hook (tests/conftest.py needs_hooks) and by tools/lab.
+# the same sources with -DXPG_TEST_HOOKS: fault injection, forced routes and debug prints are compiled in (scalar.hip.h
+# xpg_hook). Loaded only by the tests that need a hook (tests/conftest.py needs_hooks) and by tools/lab.
 HOOKS_OUT = os.path.join(HERE, "libxpoly_amd_hooks.so")
 HOOKS_OBJ = os.path.join(HERE, "csrc", "_obj", "hooks")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17"]

@@ -29,10 +29,8 @@ struct xpg_ctx {
     std::vector<std::pair<void *, size_t> > dev_cache;   // device blocks between host-array row-elimination calls (DevBuf)
     size_t dev_cache_bytes = 0;
     void * slice_buf = 0; size_t slice_cap = 0;   // k_batch's time slices: checkpoints, queue and counters (grow-only)
-    int update_variant;     // tuning knob for the fp64 sweep (see launch_update_f64)
-    int loop_mode;          // 0: pipelined fp64 loop (2 launches per pivot), 1: serial pick/prep/update
-    int zigzag;             // pipelined sweep alternates its tile order (Infinity Cache reuse)
-    int block_len;          // blocked loop (loop_mode 3): pivots staged per sweep, 1..16
+    int loop_mode;          // XPG_LOOP: 0 the pipelined loop (2 launches per pivot), 3 the blocked loop (xpg_lp_loop_info's codes)
+    int block_len;          // blocked loop: pivots staged per sweep, 1..BLK_MAX
     int loop_auto;          // XPG_LOOP unset: blocked loop where the sweep is what costs (large fp64 tableaux)
     int num_cus;            // compute units of the device
     int chain;              // blocked loop: stages 1.. of a batch in ONE persistent launch (lp_chain.hip.h); XPG_CHAIN=0 turns it off
@@ -96,12 +94,9 @@ inline hipError_t lds_limit(const void * fn, int device, size_t bytes)
 // ldscan, profiles/round3_sweep_lab.txt: k * (32 KiB + 128 B) -- 8224, 12336, 16448 elements -- and 32 KiB - 128 B).
 inline int pick_ld(int W)
 {
-    static const int align = [] { const char * s = xpg_hook("XPG_LD_ALIGN"); const int a = s ? atoi(s) : 64; return a >= 16 && a % 16 == 0 ? a : 64; }();
-    int ld = W % 16 == 0 ? W : round_up(W, align);
+    int ld = W % 16 == 0 ? W : round_up(W, 64);
     if (ld % 4112 == 0 || (ld + 16) % 4096 == 0) ld += 16;
-    // A/B aid: XPG_LD_PAD=n (a multiple of 16 elements) widens every row by n
-    static const int pad = [] { const char * s = xpg_hook("XPG_LD_PAD"); const int a = s ? atoi(s) : 0; return a > 0 && a % 16 == 0 ? a : 0; }();
-    return ld + pad;
+    return ld;
 }
 
 // Device scratch of one host-array call. The blocks come from, and go back to, a small cache the handle owns
@@ -162,7 +157,6 @@ inline LineqGeom lineq_geom(int nb, int width, size_t sys_lds)
 {
     LineqGeom q;
     q.L = width <= 16 ? 16 : (width <= 32 ? 32 : 64);
-    if (const char * e = xpg_hook("XPG_LINEQ_LANES")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) q.L = v > q.L ? v : q.L; }
     sys_lds = (sys_lds + 15) & ~(size_t)15;
     while (q.L < 64 && sys_lds * (size_t)(64 / q.L) > 64 * 1024) q.L *= 2;
     q.G = 64 / q.L;

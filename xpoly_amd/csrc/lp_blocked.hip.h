@@ -730,7 +730,7 @@ void k_blk_sweep_full(double * __restrict__ tab, int m, int W, int ld, const dou
     }
 }
 
-// The batch length as a template switch (block lengths below 16, and the A/B switch XPG_BLK_ROWS=1).
+// The batch length as a template switch (the batch lengths without a full-batch pass of their own).
 template <int ROWS, int UNROLL, int BCAP> __global__ __launch_bounds__(256)
 void k_blk_sweep(double * __restrict__ tab, int m, int W, int ld, const double * __restrict__ E,
                  const double * __restrict__ K, LoopState * __restrict__ st, int batch, int skip_full, int full_n)

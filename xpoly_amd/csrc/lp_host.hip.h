@@ -21,31 +21,6 @@
 
 namespace xpg {
 
-// fp64 sweep launch. Variants are (rows per workgroup, rows in flight); the
-// default is what measured best on MI355X (profiles/), the others stay
-// reachable through XPG_UPDATE_VARIANT for A/B runs.
-inline void launch_update_f64(hipStream_t s, int variant, double * tab, int m, int W, int ld,
-                              const double * rowbuf, const double * colbuf,
-                              LoopState * st, int guarded, double * nextcol, double * bcol,
-                              int rhs)
-{
-    const int strips = (W + 511) / 512;
-#define XPG_LAUNCH(R, U)                                                                    \
-    hipLaunchKernelGGL((k_update_f64<R, U>), dim3(strips, (m + R - 1) / R), dim3(256), 0, s, \
-                       tab, m, W, ld, rowbuf, colbuf, st, guarded, nextcol, bcol, rhs)
-    switch (variant) {
-    case 1: XPG_LAUNCH(16, 4); break;
-    case 2: XPG_LAUNCH(32, 4); break;
-    case 3: XPG_LAUNCH(64, 8); break;
-    case 4: XPG_LAUNCH(16, 8); break;
-    case 5: XPG_LAUNCH(128, 8); break;
-    case 6: XPG_LAUNCH(8, 8); break;
-    case 7: XPG_LAUNCH(64, 16); break;
-    default: XPG_LAUNCH(32, 8); break;
-    }
-#undef XPG_LAUNCH
-}
-
 template <class S> inline void launch_update(xpg_ctx * ctx, const LpView<S> & v, int guarded);
 inline bool prof_open(xpg_ctx * ctx)
 {
@@ -61,10 +36,11 @@ inline void prof_close(xpg_ctx * ctx)
 }
 template <> inline void launch_update<F64>(xpg_ctx * ctx, const LpView<F64> & v, int guarded)
 {
+    // 32 rows per workgroup, 8 in flight: what measured best on MI355X (profiles/)
     const bool timed = prof_open(ctx);
-    launch_update_f64(ctx->stream, ctx->update_variant, (double *)v.tab, v.m, v.W, v.ld,
-                      (const double *)v.rowbuf, (const double *)v.colbuf, v.st, guarded,
-                      (double *)v.nextcol, (double *)v.bcol, v.rhs);
+    hipLaunchKernelGGL((k_update_f64<32, 8>), dim3((v.W + 511) / 512, (v.m + 31) / 32), dim3(256), 0, ctx->stream,
+                       (double *)v.tab, v.m, v.W, v.ld, (const double *)v.rowbuf, (const double *)v.colbuf, v.st, guarded,
+                       (double *)v.nextcol, (double *)v.bcol, v.rhs);
     if (timed) prof_close(ctx);
 }
 template <class S> inline void launch_pipe_sweep(xpg_ctx *, const LpView<S> &, int, int, bool) {}
@@ -72,18 +48,14 @@ template <> inline void launch_pipe_sweep<F64>(xpg_ctx * ctx, const LpView<F64> 
                                                bool sample)
 {
     const int strips = (v.W + 511) / 512;
-    const int fused = ctx->loop_mode == 2 ? 0 : 1;
     // a sampled launch carries its own start/stop events (timestamps of the dispatch itself, as
     // rocprofv3 reports them) instead of being bracketed by two marker packets
     const bool timed = sample && ctx->prof_n < ctx->prof_cap && (ctx->prof_seen++ % ctx->prof_stride) == 0;
     hipEvent_t e0 = timed ? ctx->ev0[ctx->prof_n] : nullptr, e1 = timed ? ctx->ev1[ctx->prof_n] : nullptr;
     hipExtLaunchKernelGGL((k_pipe_sweep<32, 8>), dim3(strips, (v.m + 31) / 32 + 1), dim3(256), 0, ctx->stream, e0, e1, 0,
-                          v, slot, colstride, fused, (double *)v.tab, (const double *)v.rowbuf,
-                          (const double *)v.colbuf + (size_t)slot * colstride, ctx->zigzag ? (slot & 1) : 0);
+                          v, slot, colstride, (double *)v.tab, (const double *)v.rowbuf,
+                          (const double *)v.colbuf + (size_t)slot * colstride);
     if (timed) ctx->prof_n++;
-    if (!fused)
-        hipLaunchKernelGGL((k_pipe_pick<0>), dim3(strips < PICK_MAX_WGS ? strips : PICK_MAX_WGS), dim3(256), 0, ctx->stream,
-                           v, slot, colstride);
 }
 template <> inline void launch_pipe_sweep<R32>(xpg_ctx * ctx, const LpView<R32> & v, int slot, int colstride, bool sample)
 {
@@ -110,10 +82,6 @@ template <> inline void launch_side_home<R32>(xpg_ctx * ctx, const LpView<R32> &
 // What a batch of the blocked loop launches for an fp64 tableau of a given shape -- decided in ONE place: launch_blk_batch
 // launches it, Lp::blocked_from_bytes asks whether the chain can run at all (the automatic loop choice), xpg_lp_loop_info
 // reports it (bench.py's `shapes` leg).
-// workgroup sizes of pick and prep: 64 = one wave per workgroup, no LDS round in the reductions
-// (measured at 4096 x 8192: 58.7 k pivots/s with a 64-thread pick against 55.7 k with 256; prep +0.8 %)
-inline int blk_tpb_pick() { static const int t = [] { const char * s = xpg_hook("XPG_BLK_TPB_PICK"); return s && atoi(s) == 256 ? 256 : 64; }(); return t; }
-inline int blk_tpb_prep() { static const int t = [] { const char * s = xpg_hook("XPG_BLK_TPB_PREP"); return s && atoi(s) == 256 ? 256 : 64; }(); return t; }
 // Stages 1 .. B-1 in one persistent launch: one one-wave worker per 64 rows / 64 columns, all resident at once -- they
 // poll each other's records. The launch checks that itself (roll call, lp_chain.hip.h) and falls back when the device
 // cannot seat them all, so the shape limits here are only those of the hand-off areas: 256 records (m <= 16 384), 511
@@ -125,8 +93,7 @@ inline bool chain_shape_ok(const xpg_ctx * ctx, int m, int W)
 {
     const int cpick = (m + 63) / 64, cprep = (W + 63) / 64;
     const int cus = ctx->num_cus > 0 ? ctx->num_cus : 1;
-    return cpick <= BLK_REC_MAX && cprep <= 510 && cpick + cprep + 1 <= 8 * cus &&
-           blk_tpb_prep() == 64;                   // stage 0's prep leaves one look-ahead partial per 64 columns, as the chain's workers do
+    return cpick <= BLK_REC_MAX && cprep <= 510 && cpick + cprep + 1 <= 8 * cus;
 }
 struct BlkPlan {
     bool chain;            // a batch's stages in one persistent launch (else pick / prep kernels per stage)
@@ -171,10 +138,12 @@ template <> inline void launch_blk_batch<F64>(xpg_ctx * ctx, const LpView<F64> &
                                               bool chain_spread, bool fold, bool next_folds)
 {
     const int strips = (v.W + 511) / 512;
-    // prep workgroups leave one look-ahead partial each and there are 510 partial slots (BLK_PART_MAX): one wave per 64 columns
-    // up to W = 32 640, four beyond (W <= 130 560; wider tableaux do not take the blocked loop, blk_shape_ok). Round 6: a
+    // pick and prep workgroups of one wave: no LDS round in the reductions (measured at 4096 x 8192: 58.7 k pivots/s with
+    // a 64-thread pick against 55.7 k with 256; prep +0.8 %). Prep workgroups leave one look-ahead partial each -- one per
+    // 64 columns, as the chain's workers do -- and there are 510 partial slots (BLK_PART_MAX): one wave per 64 columns up
+    // to W = 32 640, four beyond (W <= 130 560; wider tableaux do not take the blocked loop, blk_shape_ok). Round 6: a
     // 1024 x 33793 tableau ran 529 one-wave prep workgroups over the 520 slots -- a memory fault.
-    const int tq = (v.W + blk_tpb_prep() - 1) / blk_tpb_prep() <= 510 ? blk_tpb_prep() : 256, tp = blk_tpb_pick();
+    const int tq = (v.W + 63) / 64 <= 510 ? 64 : 256, tp = 64;
     const int want_pick = (v.m + tp - 1) / tp;
     const int npick = want_pick < BLK_PICK_WGS ? want_pick : BLK_PICK_WGS;
     const dim3 gprep((v.W + tq - 1) / tq);
@@ -207,9 +176,6 @@ template <> inline void launch_blk_batch<F64>(xpg_ctx * ctx, const LpView<F64> &
     // of an xpg_lp_iterate budget -- moves the same bytes for fewer pivots and runs a different kernel)
     const bool timed = B == ctx->block_len && ctx->prof_n < ctx->prof_cap && (ctx->prof_seen++ % ctx->prof_stride) == 0;
     hipEvent_t e0 = timed ? ctx->ev0[ctx->prof_n] : nullptr, e1 = timed ? ctx->ev1[ctx->prof_n] : nullptr;
-    static const int rows_env = [] { const char * s = xpg_hook("XPG_BLK_ROWS"); return s ? atoi(s) : 32; }();
-    // alternate passes walk the row blocks in opposite directions (Infinity Cache reuse across passes); XPG_SERPENTINE=0 for A/B runs
-    static const int serpentine = [] { const char * s = xpg_hook("XPG_SERPENTINE"); return s ? atoi(s) : 1; }();
 #define XPG_BLK_LAUNCH(ROWS_, UNR_, CAP_)                                                                                 \
     hipExtLaunchKernelGGL((k_blk_sweep<ROWS_, UNR_, CAP_>), dim3(strips, (v.m + ROWS_ - 1) / ROWS_), dim3(256), 0,        \
                           ctx->stream, e0, e1, 0, (double *)v.tab, v.m, v.W, v.ld, (const double *)v.blkE,                \
@@ -218,29 +184,26 @@ template <> inline void launch_blk_batch<F64>(xpg_ctx * ctx, const LpView<F64> &
     hipExtLaunchKernelGGL((k_blk_sweep_full<ROWS_, UNR_, NB_>), dim3(blk_sweep_grid(strips, (v.m + ROWS_ - 1) / ROWS_)), \
                           dim3(256), 0, ctx->stream, e0, e1, 0, (double *)v.tab, v.m, v.W, v.ld,                          \
                           (const double *)v.blkE, (const double *)v.blkK, v.st, batch, closes_often ? 1 : 0,              \
-                          serpentine ? (batch & 1) : 0, ctx->block_len)
+                          batch & 1, ctx->block_len)
     // the full-batch kernels: 32 pivots per pass (the default; two register sets of e_s, 2-3 waves per SIMD: 110 / 166 us
     // per pass at 4096 x 8192 / 4096 x 12289 = 3.4 / 5.2 us per pivot against 4.9 / 7.9 with 16, tools/lab/sweep_lab2.hip) and
-    // 16 (XPG_BLOCK=16); every other length -- the tail of an iteration budget -- goes through the switch kernel
-    const bool full32 = B == 32 && rows_env != 1, full16 = B == 16 && rows_env != 1, full24 = B == 24 && rows_env != 1;
+    // 16 (XPG_BLOCK=16) and 24; every other length -- the tail of an iteration budget -- goes through the switch kernel.
+    // Alternate passes walk the row blocks in opposite directions (serpentine: Infinity Cache reuse across passes).
+    const bool full = B == 32 || B == 24 || B == 16;
     // 32 stages: 16 rows per workgroup where the tableau is of the Infinity Cache's size (4096 x 8192: 93.9 us against 95.5
     // with 32 rows), 32 rows -- the e_s read from the L2 half as often -- where it is beyond it (4096 x 12289, 403 MB: 150.0
-    // against 156.1 us, 105.7 k against 103.9 k pivots/s); XPG_BLK_ROWS = 162 / 322 / 164 force a form for A/B runs
-    const bool beyond_mall = pl.sweep_rows == 32;
-    if (full32) {
-        if (rows_env == 322 || (rows_env == 32 && beyond_mall)) XPG_BLK_FULL(32, 2, 32);
-        else if (rows_env == 164) XPG_BLK_FULL(16, 4, 32);
-        else XPG_BLK_FULL(16, 2, 32);
-    }
-    else if (full24) { if (rows_env == 164) XPG_BLK_FULL(16, 4, 24); else XPG_BLK_FULL(16, 2, 24); }
-    else if (full16) { if (rows_env == 324) XPG_BLK_FULL(32, 4, 16); else if (rows_env == 162) XPG_BLK_FULL(16, 2, 16); else XPG_BLK_FULL(16, 4, 16); }
+    // against 156.1 us, 105.7 k against 103.9 k pivots/s)
+    if (B == 32 && pl.sweep_rows == 32) XPG_BLK_FULL(32, 2, 32);
+    else if (B == 32) XPG_BLK_FULL(16, 2, 32);
+    else if (B == 24) XPG_BLK_FULL(16, 2, 24);
+    else if (B == 16) XPG_BLK_FULL(16, 4, 16);
     else if (B <= 8) XPG_BLK_LAUNCH(32, 8, 8);
     else XPG_BLK_LAUNCH(32, 4, 16);
     // An LP whose batches often close early (a rare branch of solveSlackForm met with pivots staged: 34-44 % of
     // the sweeps on whole solves of 300 x 300 and 1024 x 1500 LPs, 1 of 261 on the bench LP,
     // tools/lab/probe_partial_batches.py) gets a second launch with the stage count as a template switch for those
     // batches; the full-batch kernel above then leaves them alone.
-    if (closes_often && (full32 || full24 || full16))
+    if (closes_often && full)
         hipLaunchKernelGGL((k_blk_sweep<32, 4, 16>), dim3(strips, (v.m + 31) / 32), dim3(256), 0, ctx->stream, (double *)v.tab,
                            v.m, v.W, v.ld, (const double *)v.blkE, (const double *)v.blkK, v.st, batch, B, ctx->block_len);
 #undef XPG_BLK_LAUNCH
@@ -250,11 +213,8 @@ template <> inline void launch_blk_batch<F64>(xpg_ctx * ctx, const LpView<F64> &
 template <> inline void launch_update<R32>(xpg_ctx * ctx, const LpView<R32> & v, int guarded)
 {
     const bool timed = prof_open(ctx);
-    static const int rows = [] { const char * s = xpg_hook("XPG_R32_ROWS"); return s ? atoi(s) : 1; }();   // A/B knob: 8 / 4 / 2 / 1 rows per thread measured 15.6 / 16.5 / 16.8 / 17.2 k pivots/s at 1024 x 2048
-    if (rows <= 1) hipLaunchKernelGGL((k_update_r32<1>), dim3(v.m, (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, guarded);
-    else if (rows == 2) hipLaunchKernelGGL((k_update_r32<2>), dim3((v.m + 1) / 2, (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, guarded);
-    else if (rows == 4) hipLaunchKernelGGL((k_update_r32<4>), dim3((v.m + 3) / 4, (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, guarded);
-    else hipLaunchKernelGGL((k_update_r32<8>), dim3((v.m + 7) / 8, (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, guarded);
+    // one row per thread (8 / 4 / 2 / 1 rows measured 15.6 / 16.5 / 16.8 / 17.2 k pivots/s at 1024 x 2048)
+    hipLaunchKernelGGL((k_update_r32<1>), dim3(v.m, (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, guarded);
     if (timed) prof_close(ctx);
 }
 
@@ -299,7 +259,7 @@ template <class S> struct Lp : LpBase {
     int set_options(int pricing, double feas_tol)
     {
         if (pricing < 0 || pricing > 1 || !(feas_tol >= 0.0)) return XPG_ERR_SHAPE;
-        if ((pricing != 0 || feas_tol != 0.0) && (!std::is_same<S, F64>::value || ctx->loop_mode == 1))
+        if ((pricing != 0 || feas_tol != 0.0) && !std::is_same<S, F64>::value)
             return XPG_ERR_UNSUPPORTED;
         opt_pricing = pricing; opt_feas_tol = feas_tol;
         return 0;
@@ -477,11 +437,11 @@ template <class S> struct Lp : LpBase {
     {
         const int span = v.W > v.m ? v.W : v.m;
         hipLaunchKernelGGL((k_prep<S>), dim3((span + 255) / 256), dim3(256), 0, ctx->stream, v,
-                           guarded, counted, 1, 0);
+                           guarded, counted, 1);
         launch_update<S>(ctx, v, guarded);
     }
-    // Queues k loop iterations. The host runs far ahead of the GPU (3 launches cost
-    // ~10 us, one iteration ~90 us), and an over-full HIP queue was measured to stall
+    // Queues k loop iterations. The host runs far ahead of the GPU (a launch costs a
+    // few us, one iteration ~90 us), and an over-full HIP queue was measured to stall
     // the stream for tens of ms, so at most 2 x 64 iterations are kept in flight:
     // every 64 iterations an event is recorded and the one from two blocks back awaited.
     // Where the automatic choice takes the blocked loop: by the bytes one sweep moves. With the chain launch (one persistent
@@ -502,7 +462,7 @@ template <class S> struct Lp : LpBase {
     {
         const bool blocked = std::is_same<S, F64>::value && !irregular && blk_shape_ok(v.W) &&
                              (ctx->loop_mode == 3 || (ctx->loop_auto && (size_t)v.m * v.W * 16 >= blocked_from_bytes()));
-        o[0] = blocked ? 3 : ctx->loop_mode == 1 ? 1 : 0;
+        o[0] = blocked ? 3 : 0;
         o[5] = v.ld;
         if (!blocked) return;
         const BlkPlan pl = blk_plan(ctx, v.m, v.W, v.ld, ctx->block_len, opt_pricing == 0, chain_off, chain_spread, true);
@@ -523,12 +483,9 @@ template <class S> struct Lp : LpBase {
         if (blocked && irregular) blocked = false;          // NaN ratios need the generic pick's scan order: the pipelined loop has it
         blocked_now = blocked;
         if (blocked) { queue_blocked(k); return; }
-        // (the rational scalar: XPG_R32_LOOP=pipe forces the two-launch loop, =fused the one-launch loop; =serial, the three-launch
-        // loop -- neither a default nor a fallback -- exists in the -DXPG_TEST_HOOKS build only)
-        static const bool r32_serial = [] { const char * s = xpg_hook("XPG_R32_LOOP"); return s && !strcmp(s, "serial"); }();
+        // (the rational scalar: XPG_R32_LOOP=pipe forces the two-launch loop, =fused the one-launch loop)
         static const bool r32_pipe = [] { const char * s = xpg_env("XPG_R32_LOOP"); return s && !strcmp(s, "pipe"); }();
         static const unsigned generic_every = [] { const char * s = xpg_hook("XPG_R32_GENERIC_EVERY"); const int n = s ? atoi(s) : 0; return (unsigned)(n > 0 ? n : 16); }();
-        const bool pipelined = ctx->loop_mode != 1 && (std::is_same<S, F64>::value || !r32_serial);
         // The fused loop where it pays: its sweep copies the columns the in-place sweep skips (ping-pong tableau) and its
         // launch lasts as long as the pick -> staging chain inside it. Measured against the two-launch loop
         // (tools/lab/probe_rat_sizes.py, us per pivot fused / two-launch): 256 x 512 21.4 / 19.9, 384 x 785 21.0 / 21.0,
@@ -537,7 +494,7 @@ template <class S> struct Lp : LpBase {
         static const bool r32_fused = [] { const char * s = xpg_env("XPG_R32_LOOP"); return s && !strcmp(s, "fused"); }();
         const size_t cells = (size_t)v.m * (size_t)v.W;
         const bool fused_pays = r32_fused || (cells >= 350000u && cells <= 5000000u);
-        if (pipelined && !std::is_same<S, F64>::value && !r32_pipe && fused_pays && k > 0 && fused_buffers()) {
+        if (!std::is_same<S, F64>::value && !r32_pipe && fused_pays && k > 0 && fused_buffers()) {
             // one launch per pivot (lp_fused_r32.hip.h); the first launch of a call and every generic_every-th one are
             // preceded by a generic point
             for (unsigned t = 0; t < k; t++) {
@@ -552,7 +509,7 @@ template <class S> struct Lp : LpBase {
             }
             return;                                     // (read_state, which follows every call, brings the tableau home)
         }
-        if (pipelined && k > 0 && !pipe_primed) {
+        if (k > 0 && !pipe_primed) {
             // the first pivot is chosen by a launch that has nothing to sweep (pd[1].row < 0): fp64 the sweep launch's
             // pick workgroup, Rational the prep launch's first workgroup
             if (std::is_same<S, F64>::value) launch_pipe_sweep(ctx, v, 1, colstride, false);
@@ -560,16 +517,10 @@ template <class S> struct Lp : LpBase {
             pipe_primed = true;
         }
         for (unsigned t = 0; t < k; t++) {
-            if (pipelined) {
-                // two launches per pivot; the next pivot is chosen inside the sweep launch
-                const int slot = (int)(pipe_t++ & 1u);
-                hipLaunchKernelGGL((k_pipe_prep<S>), dim3((v.W + 255) / 256), dim3(256), 0, ctx->stream, v, slot, colstride);
-                launch_pipe_sweep(ctx, v, slot, colstride, true);
-            } else {
-                hipLaunchKernelGGL((k_pick<S>), dim3(1), dim3(1024), 0, ctx->stream, v);
-                hipLaunchKernelGGL((k_prep<S>), dim3((v.W + 255) / 256), dim3(256), 0, ctx->stream, v, 1, 1, 0, 1);
-                launch_update<S>(ctx, v, 1);
-            }
+            // two launches per pivot; the next pivot is chosen inside the sweep launch
+            const int slot = (int)(pipe_t++ & 1u);
+            hipLaunchKernelGGL((k_pipe_prep<S>), dim3((v.W + 255) / 256), dim3(256), 0, ctx->stream, v, slot, colstride);
+            launch_pipe_sweep(ctx, v, slot, colstride, true);
             if ((t & 63) == 63) {
                 hipEvent_t e = throttle[blk & 1];
                 if (blk >= 2) (void)hipEventSynchronize(e);

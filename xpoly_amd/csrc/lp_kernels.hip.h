@@ -3,19 +3,13 @@
 // kernel template over the scalar S (xpg::F64 or xpg::R32); the host only
 // queues launches and polls a status word every few dozen pivots.
 //
-// Serial loop (rational scalar, XPG_LOOP=serial): three launches per iteration,
-// communicating through LoopState:
-//   k_pick   : ratio test (lpsol.h:553-663) on the look-ahead column, pivot-pair table
-//              upkeep (lpsol.h:68-154), basis swap, -column -> colbuf   -- 1 workgroup
-//   k_prep   : row * 1/pivot -> rowbuf, objective row update (lpsol.h:1471-1474,
-//              :1496-1501) and look-ahead pricing of the next iteration (lpsol.h:1054-1069)
-//   k_update : a_ij += (-a_i,nv) * e_j for every i != r, all j   (lpsol.h:1481-1490)
-//              -- the HBM-bound sweep, >= 2048 workgroups; it also exports the
-//              look-ahead column and the constant column contiguously so the
-//              next k_pick's ratio test reads 2 x 32 KB coalesced instead of
-//              2 x 4096 64-byte sectors
-// Pipelined fp64 loop (default): k_pipe_prep + k_pipe_sweep, the next pivot being chosen
-// by extra workgroups inside the sweep launch -- see "Pipelined fp64 loop" below.
+// Two loops run on them (the host picks one per call, lp_host.hip.h queue_iterations):
+//   * the pipelined loop -- k_pipe_prep + k_pipe_sweep, the next pivot being chosen by extra
+//     workgroups inside the sweep launch (see "Pipelined fp64 loop" below; the Rational form and
+//     its one-launch variant are in lp_pipe_r32.hip.h / lp_fused_r32.hip.h);
+//   * the blocked loop -- up to 32 pivots staged per sweep (lp_blocked.hip.h, lp_chain.hip.h).
+// k_prep + k_update_* are the single pivot (K1) both loops' callers use outside the loop: the
+// one-shot entry points and the forced pivots of phase 1.
 //
 // HBM layout: tableau row-major, leading dimension ld (multiple of 16 elements
 // = 128 B so every row starts on a cache line and 16-byte vector accesses are
@@ -485,7 +479,7 @@ template <class S> __device__ void price_scan(const LpView<S> & v, int * sh_i, i
 // the basis (lpsol.h:1504-1510) and writes -column to colbuf (lpsol.h:1485).
 // Every rare branch of solveSlackForm (optimum, findPivotNVandBVPair, relaxed
 // ratio pass, disableNV) is handled here by the generic single-workgroup code.
-// Where a pick leaves its decision: the serial loop's LoopState fields or a PipeDesc.
+// Where a pick leaves its decision: LoopState's fields (the blocked loop's generic pick) or a PipeDesc.
 struct PickOut {
     int * status; int * row; int * col; int * leave; int * next_first; int * anypos;
     unsigned long long * cnv_bits; unsigned long long * piv_bits;
@@ -598,20 +592,6 @@ template <class S> __device__ bool pick_body(const LpView<S> & v, int first, int
     return true;
 }
 
-template <class S> __global__ __launch_bounds__(1024) void k_pick(LpView<S> v)
-{
-    __shared__ __attribute__((aligned(8))) unsigned char sh_c_raw[16 * sizeof(Cand<S>)];
-    __shared__ int sh_i[16];
-    __shared__ int sh_flag;
-    LoopState * st = v.st;
-    if (st->status != ST_RUNNING) return;
-    const PickOut o = { &st->status, &st->row, &st->col, &st->leave, &st->next_first, &st->anypos,
-                        &st->cnv_bits, &st->piv_bits };
-    const int first = st->next_first, anypos = st->anypos, cached_col = st->cached_col;
-    const bool b_cached = st->bcol_valid != 0;
-    pick_body<S>(v, first, anypos, cached_col, b_cached, false, o, v.colbuf, (Cand<S> *)sh_c_raw, sh_i, &sh_flag);
-}
-
 // Row / column staging, objective update and basis swap for the pivot chosen in
 // LoopState (lpsol.h:1468-1474, :1485, :1496-1510). Reads the tableau only.
 // guarded: only while the loop is running; counted: the pivot counts towards 'cnt'
@@ -647,7 +627,7 @@ template <> __device__ __forceinline__ R32 obj_update_c<R32>(R32 e, bool beyond_
 }
 
 template <class S> __global__ __launch_bounds__(256)
-void k_prep(LpView<S> v, int guarded, int counted, int bookkeeping, int lookahead)
+void k_prep(LpView<S> v, int guarded, int counted, int bookkeeping)
 {
     LoopState * st = v.st;
     if ((guarded && st->status != ST_RUNNING) || st->row < 0) return;
@@ -658,8 +638,6 @@ void k_prep(LpView<S> v, int guarded, int counted, int bookkeeping, int lookahea
     const S cnv = from_bits<S>(st->cnv_bits);
     const int cmode = scale_mode(cnv);
     const int gid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
-    const int lim = v.rhs - 1;
-    int nf = INT_MAX, any = 0;
     for (int j = gid; j < v.W; j += gsz) {
         S e = scaled_c(v.tab[(size_t)r * v.ld + j], s, smode, canon);
         v.rowbuf[j] = e;
@@ -668,19 +646,6 @@ void k_prep(LpView<S> v, int guarded, int counted, int bookkeeping, int lookahea
         t = scaled_c(t, cnv, cmode, canon);                    // nvexp.mul(tgtf(nv)), :1500
         const S o = add_c(t, v.obj[j], canon);                 // addRowToRow, :1501
         v.obj[j] = o;
-        // look-ahead pricing of the next iteration (basis already swapped by k_pick)
-        if (lookahead && j < v.rhs && v.nv[j] && gt(o, zero<S>())) {
-            any = 1;
-            if (v.rowcnt[j] < lim) nf = min(nf, j);
-        }
-    }
-    if (lookahead) {
-        for (int o = 32; o > 0; o >>= 1) { nf = min(nf, __shfl_xor(nf, o)); any |= __shfl_xor(any, o); }
-        if ((threadIdx.x & 63) == 0) {
-            if (nf != INT_MAX) atomicMin(&st->next_first, nf);
-            if (any) atomicOr(&st->anypos, 1);
-        }
-        return;                                                // colbuf / basis were done by k_pick
     }
     for (int i = gid; i < v.m; i += gsz)
         v.colbuf[i] = neg(v.tab[(size_t)i * v.ld + c]);        // coeff_of_nv, :1485
@@ -1136,21 +1101,11 @@ __device__ inline void pipe_pick_f64(const LpView<F64> & v, int slot, int colstr
                to_bits(F64(g_a)));
 }
 
-// A/B aid (XPG_LOOP=split): the pick as a launch of its own after a sweep launched without it.
-template <int UNUSED = 0> __global__ __launch_bounds__(256) void k_pipe_pick(LpView<F64> v, int slot, int colstride)
-{
-    if (v.st->status != ST_RUNNING) return;
-    pipe_pick_f64(v, slot, colstride, blockIdx.x, gridDim.x);
-}
-
 template <int ROWS, int UNROLL> __global__ __launch_bounds__(256)
-void k_pipe_sweep(LpView<F64> v, int slot, int colstride, int with_pick,
+void k_pipe_sweep(LpView<F64> v, int slot, int colstride,
                   double * __restrict__ tab, const double * __restrict__ rowbuf,
-                  const double * __restrict__ colbuf, int descending)
+                  const double * __restrict__ colbuf)
 {
-    // descending (XPG_ZIGZAG=1, off by default): tiles visited in the reverse order of the previous
-    // sweep, hoping to start on lines still in the 256 MiB Infinity Cache. Measured on MI355X:
-    // 79.7 us per sweep against 77.8 us in fixed order, so the cache does not retain them that way.
     // tab / rowbuf / colbuf (this slot's half) repeat v's pointers as restrict PARAMETERS: only then
     // does -a_i,nv arrive through the scalar cache (restrict on a local is not enough; measured
     // 84.5 us against 73 us per sweep).
@@ -1160,18 +1115,16 @@ void k_pipe_sweep(LpView<F64> v, int slot, int colstride, int with_pick,
     if (status != ST_RUNNING) return;
     if (blockIdx.y == 0) {
         const int N = pick_wgs(gridDim.x);
-        if ((int)blockIdx.x < N && with_pick) pipe_pick_f64(v, slot, colstride, blockIdx.x, N);
+        if ((int)blockIdx.x < N) pipe_pick_f64(v, slot, colstride, blockIdx.x, N);
         return;
     }
     if (r < 0) return;
     const int W = v.W, ld = v.ld, m = v.m;
-    const int bx = descending ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
-    const int by = descending ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y - 1;
-    const int j = bx * 512 + threadIdx.x * 2;
+    const int j = blockIdx.x * 512 + threadIdx.x * 2;
     if (j >= W) return;
     const int xc = (first >= 0 && first < W) ? first : -1;
     if (xc >= 0 && j == (xc & ~1)) return;                    // the pick workgroup's pair
-    const int i0 = by * ROWS;
+    const int i0 = ((int)blockIdx.y - 1) * ROWS;
     const int iend = min(i0 + ROWS, m);
     if (j + 1 < W) {
         const double2 e = *reinterpret_cast<const double2 *>(rowbuf + j);

@@ -2,7 +2,7 @@
 // the NEXT pivot chosen by a few pick workgroups inside the sweep launch -- the shape of the fp64 pipelined loop
 // (lp_kernels.hip.h, "Pipelined fp64 loop"), with the same descriptors, deferrals and record hand-off.
 //
-// Why it pays here: the serial loop spent 10.7 + 6.6 us per pivot in its single-workgroup pick and its prep, both
+// Why it pays here: the three-launch loop it replaced spent 10.7 + 6.6 us per pivot in its single-workgroup pick and its prep, both
 // latency (dependent round trips and ~1500 dependent integer instructions per thread), next to a ~19 us sweep that
 // is bound by integer issue. Under the sweep the pick costs nothing but one compute unit's share.
 //   * What the pick needs of the post-sweep tableau it computes itself with the sweep's own operation

@@ -408,7 +408,6 @@ template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax
     // more trees than the chip holds at that width: one wave per tree, more trees in flight (8192 knapsacks of 24
     // variables: 64 / 128 / 256 threads 623 k / 425 k / 318 k MIPs/s; at 1024, where the deepest tree decides, 163 / 171 / 170 k)
     if (nb >= 8 * cus) g.threads = 64;
-    if (const char * t = xpg_hook("XPG_BATCH_THREADS")) { const int v = atoi(t); if (v >= 64 && v <= 256 && v % 64 == 0) g.threads = v; }
     const int per_cu = (int)((160 * 1024) / g.lds) > 0 ? (int)((160 * 1024) / g.lds) : 1;
     g.grid = cus * (per_cu > 8 ? 8 : per_cu) * 4;
     if (g.grid > nb) g.grid = nb;
@@ -442,11 +441,10 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
     }
     // Speculative ceiling children (mip_kernels.hip.h, SP_*): for batches that leave the chip under-filled -- one tree per
     // walking workgroup, the batch lasts as long as its deepest tree -- helper workgroups behind the walkers solve the node
-    // LPs the walks will need next. Not with root equalities (the helper builds plain nodes only). XPG_MIP_SPEC=0: off.
-    static const int spec_env = [] { const char * e = xpg_hook("XPG_MIP_SPEC"); return e ? atoi(e) : 1; }();
+    // LPs the walks will need next, one helper per CU. Not with root equalities (the helper builds plain nodes only).
     const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const bool spec = spec_env != 0 && eq_rows == 0 && grid == nb && nb <= 8 * cus;
-    const int nhelp = spec ? (spec_env > 1 ? spec_env : cus) : 0;        // (256 / 512 / 2048 helpers measured alike: 3.72 / 3.77 / 3.86 ms for 1024 knapsacks, 4.41 without)
+    const bool spec = eq_rows == 0 && grid == nb && nb <= 8 * cus;
+    const int nhelp = spec ? cus : 0;        // (256 / 512 / 2048 helpers measured alike: 3.72 / 3.77 / 3.86 ms for 1024 knapsacks, 4.41 without)
     DevBuf dq;
     if (spec) { XPG_TRY(dq.alloc(ctx, spq_bytes())); XPG_TRY(hipMemsetAsync(dq.p, 0, spq_bytes(), ctx->stream)); }
     XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dws.alloc(ctx, (size_t)(grid + nhelp) * ws_words * 8));

@@ -19,7 +19,7 @@
 #define XPG_HD __host__ __device__ __forceinline__
 
 // Environment switches (host side). xpg_env: the switches the product documents -- always read.
-// xpg_hook: test hooks (fault injection, forced routes, debug prints) and the lab's A/B knobs -- they exist only in the
+// xpg_hook: test hooks (fault injection, forced routes, debug prints) -- they exist only in the
 // -DXPG_TEST_HOOKS build (xpoly_amd/libxpoly_amd_hooks.so: the tests that need one load it, tools/lab runs on it); the
 // product library does not look at them.
 #include <stdlib.h>

@@ -91,18 +91,11 @@ int xpg_create(xpg_ctx ** out, int device)
     c->rowbuf = c->colbuf = 0; c->st = 0; c->row_cap = c->col_cap = 0;
     c->stage = 0; c->stage_cap = 0;
     c->hstage = 0; c->hstage_cap = 0;
-    const char * var = xpg_hook("XPG_UPDATE_VARIANT");
-    c->update_variant = var ? atoi(var) : 0;
-    // XPG_LOOP: "block" / "pipe" force the blocked / the pipelined loop whatever the size (unset: chosen by size). The
-    // three-launch "serial" loop and the "split" form of the pipelined one (neither a default nor a fallback: kept for the
-    // lab's A/B runs and the tests that compare the loops with each other) are selectable in the -DXPG_TEST_HOOKS build only.
+    // XPG_LOOP: "block" / "pipe" force the blocked / the pipelined loop whatever the size (unset: chosen by size; a value
+    // beginning with 's', once the names of loops the product never ran, reads as unset)
     const char * lm = xpg_env("XPG_LOOP");
-    if (lm && lm[0] == 's' && !xpg_hook("XPG_LOOP")) lm = nullptr;
-    const char * zz = xpg_hook("XPG_ZIGZAG");
-    c->zigzag = zz ? atoi(zz) : 0;                      // measured slower (79.7 vs 77.8 us per sweep): off
-    c->loop_mode = (lm && lm[0] == 's' && lm[1] == 'e') ? 1 : ((lm && lm[0] == 's' && lm[1] == 'p') ? 2 : 0);
-    if (lm && lm[0] == 'b') c->loop_mode = 3;          // "block": B pivots per sweep (lp_blocked.hip.h)
-    if (lm && lm[0] == 'p') c->loop_mode = 0;          // "pipe": always the pipelined loop
+    if (lm && lm[0] == 's') lm = nullptr;
+    c->loop_mode = lm && lm[0] == 'b' ? 3 : 0;          // "block": B pivots per sweep (lp_blocked.hip.h), else pipelined
     const char * ch = xpg_env("XPG_CHAIN");               // "0": launch-per-stage chain, for A/B runs
     c->chain = ch ? atoi(ch) : 1;
     const char * cx = xpg_hook("XPG_CHAIN_XCD");
@@ -268,7 +261,7 @@ int pivot_dev(xpg_ctx * ctx, S * tab, int m, int W, int ld, S * obj, int rhs, in
     v.rowbuf = (S *)ctx->rowbuf; v.colbuf = (S *)ctx->colbuf; v.st = ctx->st;
     hipLaunchKernelGGL((k_stage_pivot<S>), dim3(1), dim3(64), 0, ctx->stream, v, row, col);
     const int span = W > m ? W : m;
-    hipLaunchKernelGGL((k_prep<S>), dim3((span + 255) / 256), dim3(256), 0, ctx->stream, v, 0, 0, 0, 0);
+    hipLaunchKernelGGL((k_prep<S>), dim3((span + 255) / 256), dim3(256), 0, ctx->stream, v, 0, 0, 0);
     launch_update<S>(ctx, v, 0);
     XPG_HIP(ctx, hipGetLastError());
     return 0;

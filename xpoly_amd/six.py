@@ -264,7 +264,7 @@ class DeviceLP:
         """xpg_lp_loop_info: which loop and kernel instances run the LP in its current shape."""
         o = (C.c_int32 * 10)()
         self.ctx.check(lib().xpg_lp_loop_info(self._h, o, C.c_int(10)), "xpg_lp_loop_info")
-        return dict(loop={0: "pipelined", 1: "serial", 3: "blocked"}.get(o[0], o[0]), pivots_per_pass=o[1],
+        return dict(loop={0: "pipelined", 3: "blocked"}.get(o[0], o[0]), pivots_per_pass=o[1],
                     chain={0: "launch per stage", 1: "one launch, one XCD", 2: "one launch, spread"}[o[2]] if o[0] == 3 else None,
                     chain_line=o[3], sweep_rows=o[4], ld=o[5], chain_workers=o[6], pick_workers=o[7], prep_workers=o[8],
                     chain_lds_bytes=o[9])
