@@ -30,7 +30,7 @@ CASES = [
     ("crosscheck_pivot_weird.py", ["9"], ["9"]),            # K1 on non-canonical / non-finite cells
     ("crosscheck_batch_rat.py", ["5", "24"], ["5", "512"]),     # rational LDS batches, several shapes
     ("crosscheck_dep.py", ["1", "192"], ["1", "1024"]),     # DepPoly::is_empty front end
-    ("crosscheck_lineq.py", ["2026", "128"], ["2026", "768"]),  # reduce / fme / calcBound / gauss / hnf
+    ("crosscheck_lineq.py", ["2026", "128"], ["2026", "768"]),  # reduce / removeIdenRow / fme / rank / det / inv
     ("crosscheck_mip.py", ["3", "48"], ["3", "256"]),       # MIP batches (integer and 0-1)
 ]
 

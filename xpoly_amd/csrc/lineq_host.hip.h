@@ -26,17 +26,26 @@ inline int lineq_reduce_batch_dev(xpg_ctx * ctx, int nb, R32 * d_mats, int rows,
     XPG_TRY(hipGetLastError());
     return 0;
 }
-// Pinned host memory of the packed-result entry points: grows, never shrinks, freed with the handle.
-inline int hpack_reserve(xpg_ctx * ctx, size_t bytes)
+// Pinned host memory of one of the handle's staging buffers: grows, never shrinks, freed with the handle.
+inline int pinned_reserve(xpg_ctx * ctx, void *& buf, size_t & buf_cap, size_t bytes, const char * what)
 {
-    if (bytes <= ctx->hpack_cap) return 0;
+    if (bytes <= buf_cap) return 0;
     const size_t cap = bytes + bytes / 4 + 4096;
     void * fresh = 0;
-    if (hipHostMalloc(&fresh, cap, hipHostMallocDefault) != hipSuccess) { ctx->err = "hipHostMalloc(packed results)"; return XPG_ERR_ALLOC; }
-    if (ctx->hpack) (void)hipHostFree(ctx->hpack);
-    ctx->hpack = fresh; ctx->hpack_cap = cap;
+    if (hipHostMalloc(&fresh, cap, hipHostMallocDefault) != hipSuccess) { ctx->err = std::string("hipHostMalloc(") + what + ")"; return XPG_ERR_ALLOC; }
+    if (buf) (void)hipHostFree(buf);
+    buf = fresh; buf_cap = cap;
     return 0;
 }
+// The pinned buffer of a packed-result call: hpack, what the *view of a packed entry point points into; or, `internal`,
+// hred -- for the calls that copy their results out before they return (the in-place reduce forms, the ragged fme) and
+// must leave that view alone (include/xpoly_amd.h: valid until the next packed call).
+inline int hpack_reserve(xpg_ctx * ctx, size_t bytes, bool internal = false)
+{
+    return internal ? pinned_reserve(ctx, ctx->hred, ctx->hred_cap, bytes, "in-place staging")
+                    : pinned_reserve(ctx, ctx->hpack, ctx->hpack_cap, bytes, "packed results");
+}
+inline char * hpack_buf(xpg_ctx * ctx, bool internal) { return (char *)(internal ? ctx->hred : ctx->hpack); }
 
 // Lineq::reduce / removeIdenRow for nb host systems with a PACKED result (round 6): row_offsets[nb + 1] (in rows) and the
 // surviving rows of every system back to back. The systems go up once (small batches through the handle's pinned buffer,
@@ -45,10 +54,10 @@ inline int hpack_reserve(xpg_ctx * ctx, size_t bytes)
 // over the link), so the row counts, the verdicts, the offsets and the rows are all there after ONE synchronisation -- no
 // device slots come back, nothing is allocated per call beyond the handle's cached blocks. `out` (may be NULL) receives a
 // copy of the rows, *view (may be NULL) the pinned buffer itself (valid until the handle's next packed call), out_rows
-// (may be NULL) the per-system counts.
+// (may be NULL) the per-system counts. `internal`: staged through hred instead (hpack_reserve), for the in-place form below.
 inline int lineq_reduce_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, int mode, int is_intersect,
                                      R32 * out, long long out_cap_rows, const R32 ** view, long long * row_offsets,
-                                     int32_t * out_rows, int32_t * out_ok)
+                                     int32_t * out_rows, int32_t * out_ok, bool internal = false)
 {
     if (view) *view = 0;
     if (!ctx || nb < 0 || !mats || rows <= 0 || cols <= 0 || !row_offsets || (mode == 1 && (rhs < 0 || rhs >= cols || !out_ok)) ||
@@ -62,9 +71,9 @@ inline int lineq_reduce_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, in
     DevBuf di, dr, dk, doff;
     XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
     XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + bi);
+    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + bi, internal);
     if (rc) return rc;
-    char * hp = (char *)ctx->hpack;
+    char * hp = hpack_buf(ctx, internal);
     char * hrows_out = hp + meta_al + (small_in ? bi : 0);           // where the survivors land
     if (small_in) {
         memcpy(hp + meta_al, mats, bi);
@@ -104,7 +113,8 @@ inline int lineq_reduce_batch(xpg_ctx * ctx, int nb, R32 * mats, int rows, int c
     std::vector<int32_t> ok_tmp;
     if (mode == 1 && !out_ok) { ok_tmp.resize((size_t)nb); out_ok = ok_tmp.data(); }
     const R32 * view = 0;
-    const int rc = lineq_reduce_batch_packed(ctx, nb, mats, rows, cols, rhs, mode, is_intersect, (R32 *)0, 0, &view, off.data(), out_rows, out_ok);
+    const int rc = lineq_reduce_batch_packed(ctx, nb, mats, rows, cols, rhs, mode, is_intersect, (R32 *)0, 0, &view, off.data(), out_rows, out_ok,
+                                             true);
     if (rc) return rc;
     const size_t rowb = (size_t)cols * 8, slot = (size_t)rows * rowb;
     for (int b = 0; b < nb; b++)
@@ -176,10 +186,11 @@ inline int lineq_fme_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows, in
 // third of the worst case: 751 MB of slots against 267 MB of rows for 16 384 systems of 40 x 13). The systems go up and
 // the rows come down through pinned memory; `out` (optional) receives a copy, *view (optional) the pinned buffer itself,
 // valid until the next packed call on this handle. Returns 0; XPG_ERR_SHAPE when `out` holds fewer than the
-// row_offsets[nb] rows needed (row_offsets is filled: the caller can size its buffer and call again).
+// row_offsets[nb] rows needed (row_offsets is filled: the caller can size its buffer and call again). `internal`: staged
+// through hred (hpack_reserve), for a caller that copies the rows out of *view before it returns.
 inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, int u, int darkshadow,
                                   int cap, R32 * out, long long out_cap_rows, const R32 ** view, long long * row_offsets,
-                                  int32_t * out_ok)
+                                  int32_t * out_ok, bool internal = false)
 {
     if (!ctx || nb < 0 || !mats || rows <= 0 || cols <= 1 || !row_offsets || !out_ok || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
     if (view) *view = 0;
@@ -196,9 +207,9 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
     auto lap = [&](const char * what) { if (dbg) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "  fme_packed %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count()); } };
     const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
     const size_t meta_al = (meta + 255) & ~(size_t)255;
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
+    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0), internal);
     if (rc) return rc;
-    char * hp = (char *)ctx->hpack;
+    char * hp = hpack_buf(ctx, internal);
     // small inputs through the pinned buffer (one memcpy, then a true asynchronous copy); large ones straight from
     // the caller's pages (the runtime's own staging is faster than a single-threaded memcpy of tens of MB)
     if (small_in) {
@@ -255,12 +266,13 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
     XPG_TRY(hipGetLastError());
     lap("pack");
     if (view) {                                                    // into pinned memory; the caller's copy, if any, from there
-        rc = hpack_reserve(ctx, bp);
+        rc = hpack_reserve(ctx, bp, internal);
         if (rc) return rc;
-        XPG_TRY(hipMemcpyAsync(ctx->hpack, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        char * hv = hpack_buf(ctx, internal);
+        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
-        if (out) memcpy(out, ctx->hpack, bp);
-        *view = (const R32 *)ctx->hpack;
+        if (out) memcpy(out, hv, bp);
+        *view = (const R32 *)hv;
     } else {
         XPG_TRY(hipMemcpyAsync(out, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));

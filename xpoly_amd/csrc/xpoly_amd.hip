@@ -131,6 +131,7 @@ void xpg_destroy(xpg_ctx * ctx)
     if (ctx->stage) (void)hipFree(ctx->stage);
     if (ctx->hstage) (void)hipHostFree(ctx->hstage);
     if (ctx->hpack) (void)hipHostFree(ctx->hpack);
+    if (ctx->hred) (void)hipHostFree(ctx->hred);
     if (ctx->slice_buf) (void)hipFree(ctx->slice_buf);
     for (xpg_ctx * l : ctx->lanes) xpg_destroy(l);
     ctx->lanes.clear();
@@ -603,6 +604,7 @@ int xpg_trim(xpg_ctx * ctx)
     for (auto & b : ctx->dev_cache) (void)hipFree(b.first);
     ctx->dev_cache.clear(); ctx->dev_cache_bytes = 0;
     if (ctx->hpack) { (void)hipHostFree(ctx->hpack); ctx->hpack = 0; ctx->hpack_cap = 0; }
+    if (ctx->hred) { (void)hipHostFree(ctx->hred); ctx->hred = 0; ctx->hred_cap = 0; }
     return 0;
 }
 
@@ -1088,7 +1090,8 @@ int xpg_lineq_fme_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * ma
         std::vector<R32> buf; std::vector<int32_t> ko(ng); std::vector<long long> off(ng + 1);
         ragged_gather(buf, (const R32 *)mats, offsets, g, per);
         const R32 * view = 0;
-        const int r = lineq_fme_batch_packed(c, (int)ng, buf.data(), g.rows, gc, rhs, uu, darkshadow, 0, (R32 *)0, 0, &view, off.data(), ko.data());
+        const int r = lineq_fme_batch_packed(c, (int)ng, buf.data(), g.rows, gc, rhs, uu, darkshadow, 0, (R32 *)0, 0, &view, off.data(), ko.data(),
+                                           true);                 // (copied out below: the caller's packed view stays)
         if (r) return r;
         for (size_t k = 0; k < ng; k++) {
             const int b = g.idx[k];
