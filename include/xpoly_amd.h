@@ -255,9 +255,11 @@ int xpg_six_batch_rat32_multi(int ndev, const int * devices, int is_max, int nb,
  * node is a from-scratch SIX solve (max_iter 10000, lpsol.h:2441) on the GPU; is_bin
  * selects 0-1 programming; rational_indicator (cols bytes, may be NULL) marks entries
  * allowed to stay fractional (lpsol.h:2369-2393).  Returns XPG_IP_* or XPG_ERR_*.
- * With vc = -I (x >= 0; what the reference's caller PolyTran::FeaSchedule passes, src/eng/poly.cpp:5118-5130), with
- * or without equalities, and node LPs within 64 KB of LDS the whole tree walk runs on the device in one launch;
- * any other vc is walked by the host controller (node LPs on the device, lock-step rounds): same results.
+ * With a vc that is a SIGN PATTERN -- zero everywhere but a diagonal of -1 (x_j >= 0) and 0 (x_j free): -I is what the
+ * reference's caller PolyTran::FeaSchedule passes (src/eng/poly.cpp:5118-5130), the mixed form is what
+ * Lineq::initVarConstraint builds (src/com/linsys.cpp:803-819) --, with or without equalities, and node LPs (one more
+ * variable per free one: SIX::normalize's v = v' - v'') within 64 KB of LDS the whole tree walk runs on the device in one
+ * launch; any other vc is walked by the host controller (node LPs on the device, lock-step rounds): same results.
  * (The reference cannot instantiate MIP<FloatMat,Float>, lpsol.h:2242-2254; the f64
  * flavour follows the same template text.) */
 int xpg_mip_maxm_rat32(xpg_ctx * ctx, const xpg_rat32 * tgtf, const xpg_rat32 * vc, int vc_rows,
@@ -320,6 +322,30 @@ int xpg_mip_batch_eq_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const 
 int xpg_mip_batch_eq_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf,
                          const double * leq, int leq_rows, const double * eq, int eq_rows, int cols,
                          int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes);
+/* The same under the caller's variable constraints vc [cols-1][cols], shared by the batch -- the vc the single-problem
+ * entry points take: eq [nb][eq_rows][cols] and leq [nb][leq_rows][cols], either of which may be NULL / 0 (not both);
+ * rational_indicator (cols bytes, may be NULL) as for MIP::maxm.  A vc that is a sign pattern (see above) and node LPs
+ * within 64 KB of LDS: one launch of the device tree walk, free variables split in front of every node LP.  Any other
+ * vc, or larger node LPs: the host controller, so the call is defined wherever MIP::maxm / minm is.  Same results. */
+int xpg_mip_batch_vc_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg_rat32 * tgtf,
+                           const xpg_rat32 * vc, const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows,
+                           int cols, const uint8_t * rational_indicator, int32_t * out_status, xpg_rat32 * out_v,
+                           xpg_rat32 * out_sol, long long * out_nodes);
+int xpg_mip_batch_vc_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf,
+                         const double * vc, const double * eq, int eq_rows, const double * leq, int leq_rows,
+                         int cols, const uint8_t * rational_indicator, int32_t * out_status, double * out_v,
+                         double * out_sol, long long * out_nodes);
+/* Evidence, no reference counterpart: which route the trees of the calling thread's last MIP, has_solution or
+ * dep_is_empty call took (single-context entry points; answers are identical on both routes).  Reset when such a call
+ * starts and summed over its walks: out[0] trees walked on the device, out[1] trees walked by the host controller,
+ * out[2] free variables split per tree on the device route (0 on the host route).  Fills min(n, 3) entries. */
+int xpg_mip_last_route(long long * out, int n);
+/* Host-only views for tests (no device needed).  vc_pattern: 1 when vc [vc_rows][cols] of kind (0 fp64, 1 rational) is a
+ * sign pattern, with out_free[j] = 1 for every free variable j < cols - 1; 0 when it is general; XPG_ERR_SHAPE unless
+ * vc_rows == cols - 1.  mip_fits: 1 / 0, whether the device tree walk takes a problem of that shape with `extra` free
+ * variables (the LDS budget of its largest node LP). */
+int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free);
+int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin, int extra);
 /* DepPoly::is_empty(keepit, vc = NULL), src/eng/poly.cpp:530-573, for nb dependence polyhedra
  * mats[nb][rows][cols] without constant symbols (constant in the last column):
  * Lineq::reduce pre-filter, then Lineq::has_solution(is_int_sol, is_unique_sol) = MIP::maxm

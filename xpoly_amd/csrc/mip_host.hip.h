@@ -258,9 +258,15 @@ public:
 inline MipPool & mip_pool() { static MipPool p; return p; }
 template <class F> inline void mip_parallel_for(size_t n, F f) { mip_pool().run(n, std::function<void(size_t)>(f)); }
 
+// Which route the trees of the calling thread's last MIP / has_solution / dep_is_empty call took (xpg_mip_last_route):
+// answers are the same on both routes, so this is the only way to tell them apart. Reset by the C entry points.
+struct MipRoute { long long device_trees, host_trees, free_vars; };
+inline MipRoute & mip_route() { static thread_local MipRoute r = {0, 0, 0}; return r; }
+
 // Advances every task to completion; node LPs of equal shape share one kernel launch.
 template <class S> int run_mip_tasks(xpg_ctx * ctx, int kind, std::vector<MipTask<S> > & tasks)
 {
+    mip_route().host_trees += (long long)tasks.size();
     struct Key { int is_max, rows, cols; bool operator<(const Key & o) const
         { return is_max != o.is_max ? is_max < o.is_max : (rows != o.rows ? rows < o.rows : cols < o.cols); } };
     const std::vector<S> none;
@@ -332,11 +338,11 @@ template <class S> int run_mip_tasks(xpg_ctx * ctx, int kind, std::vector<MipTas
     }
 }
 
-template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_bin, int eq_rows = 0);
+template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_bin, int eq_rows = 0, int extra = 0);
 template <class S>
 int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
                      int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes,
-                     const uint8_t * allow_rational, const S * eqs, int eq_rows);
+                     const uint8_t * allow_rational, const S * eqs, int eq_rows, const int * free_var = (const int *)0, int extra = 0);
 
 // MIP::maxm / minm (lpsol.h:2636-2657, :2681-2702).
 template <class S>
@@ -347,19 +353,18 @@ int mip_solve(xpg_ctx * ctx, int kind, bool is_max, bool is_bin, const S * tgtf,
     if (!ctx || !tgtf || !vc || !out_v || cols < 2 || vc_rows != cols - 1 || eq_rows < 0 || leq_rows < 0 ||
         (eq_rows == 0 && leq_rows == 0) || (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq))
         return XPG_ERR_SHAPE;
-    // x >= 0 (vc = -I) with inequalities and / or equalities at the root, with or without a rational_indicator, is what
-    // the device tree walk takes; free or otherwise bounded variables stay with the host controller
+    // a vc that is a sign pattern (every variable x >= 0 or free: vc_sign_pattern, six_host.hip.h) with inequalities and / or
+    // equalities at the root, with or without a rational_indicator, is what the device tree walk takes where its node LPs --
+    // widened by one twin per free variable -- fit; variables bounded otherwise stay with the host controller
     static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_device && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows)) {
-        bool plain = true;
-        for (int i = 0; i < vc_rows && plain; i++)
-            for (int j = 0; j < cols && plain; j++)
-                plain = eq(vc[(size_t)i * cols + j], i == j ? minus_one<S>() : zero<S>());
-        if (plain) {
+    if (on_device) {
+        std::vector<int> fv;
+        if (vc_sign_pattern(vc, vc_rows, cols, fv) && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows, (int)fv.size())) {
             int32_t st = 0; long long nodes = 0;
             std::vector<S> sol((size_t)cols, zero<S>());
             if (out_sol) for (int j = 0; j < cols; j++) sol[(size_t)j] = out_sol[j];
-            const int rc = mip_batch_device<S>(ctx, 1, is_max, is_bin, tgtf, leq, leq_rows, cols, &st, out_v, sol.data(), &nodes, allow_rational, eqs, eq_rows);
+            const int rc = mip_batch_device<S>(ctx, 1, is_max, is_bin, tgtf, leq, leq_rows, cols, &st, out_v, sol.data(), &nodes, allow_rational, eqs, eq_rows,
+                                               fv.data(), (int)fv.size());
             if (rc != XPG_ERR_UNSUPPORTED) {
                 if (rc) return rc;
                 if (st == XPG_IP_SUCC && out_sol) for (int j = 0; j < cols; j++) out_sol[j] = sol[(size_t)j];
@@ -383,18 +388,18 @@ int mip_solve(xpg_ctx * ctx, int kind, bool is_max, bool is_bin, const S * tgtf,
 // Whether the node LPs of the deepest path fit the device tree walk's LDS budget, maximising and minimising.
 // Rows of the largest node LP: the root's inequalities, one bound row per ancestor under integer branching, and -- with
 // equalities at the root -- two rows for every equality convertEq2Ineq may leave unsubstituted (the root's, and under
-// 0-1 branching one per ancestor).
+// 0-1 branching one per ancestor). Its variables: the problem's plus one twin per free variable (extra).
 inline int mip_rmax(int leq_rows, int eq_rows, int n, bool is_bin)
 {
     int r = leq_rows + (is_bin ? 0 : n);
     if (eq_rows > 0) r += 2 * (eq_rows + (is_bin ? n : 0));
     return r;
 }
-template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_bin, int eq_rows)
+template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_bin, int eq_rows, int extra)
 {
     const int n = cols - 1, rmax = mip_rmax(leq_rows, eq_rows, n, is_bin);
-    if (rmax <= 0 || eq_rows + n + 2 > MIP_EQ_MAX) return false;
-    return small_lds_bytes<S>(rmax, n) <= 64 * 1024 && small_lds_bytes<S>(n, rmax) <= 64 * 1024;
+    if (rmax <= 0 || eq_rows + n + 2 > MIP_EQ_MAX || extra < 0 || extra > n) return false;
+    return small_lds_bytes<S>(rmax, n + extra) <= 64 * 1024 && small_lds_bytes<S>(n + extra, rmax) <= 64 * 1024;
 }
 // Launch shape of k_mip_tree for nb trees whose node LPs have at most rmax rows and n variables.
 struct MipGeom { size_t lds; int threads, grid; };
@@ -415,20 +420,25 @@ template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax
 }
 // The same batch with the tree walks on the device (mip_kernels.hip.h): one workgroup per problem. Returns
 // XPG_ERR_UNSUPPORTED where a node LP of the deepest path would not fit the LDS budget -- the caller then takes the
-// host controller below.
+// host controller below. free_var [extra] (host; may be NULL / 0): the batch's free variables, ascending.
 template <class S>
 int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
                      int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes,
-                     const uint8_t * allow_rational, const S * eqs, int eq_rows)
+                     const uint8_t * allow_rational, const S * eqs, int eq_rows, const int * free_var, int extra)
 {
     const int n = cols - 1;
     const int rmax = mip_rmax(leq_rows, eq_rows, n, is_bin);
     const int depth = n + 2;
-    const MipGeom g = mip_geom<S>(ctx, nb, rmax, n, is_max);
+    const MipGeom g = mip_geom<S>(ctx, nb, rmax, n + extra, is_max);
     if (g.lds > 64 * 1024) return XPG_ERR_UNSUPPORTED;
     const size_t lds = g.lds;
     const int threads = g.threads, grid = g.grid;
-    const size_t ws_words = mip_ws_words(rmax, cols, depth);
+    const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
+    DevBuf dfv;
+    if (extra > 0) {
+        XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
+        XPG_TRY(hipMemcpyAsync(dfv.p, free_var, (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     const size_t bl = (size_t)nb * leq_rows * cols * 8, bt = (size_t)nb * cols * 8, be = (size_t)nb * eq_rows * cols * 8;
     DevBuf dl, dt, dws, dst, dv, dsol, dn, dal, de;
     if (eq_rows > 0) {
@@ -458,7 +468,7 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
                        leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)dws.p, ws_words,
                        (int32_t *)dst.p, (S *)dv.p, out_sol ? (S *)dsol.p : (S *)0, (int *)dn.p, (const int *)0, (const int *)0,
                        allow_rational ? (const uint8_t *)dal.p : (const uint8_t *)0, eq_rows > 0 ? (const S *)de.p : (const S *)0, eq_rows,
-                       grid, spec ? (int *)dq.p : (int *)0);
+                       grid, spec ? (int *)dq.p : (int *)0, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
     XPG_TRY(hipGetLastError());
     if (spec && xpg_hook("XPG_MIP_DEBUG")) {
         int hq[4] = {0, 0, 0, 0};
@@ -473,6 +483,9 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
     XPG_TRY(hipMemcpyAsync(nodes.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     if (out_nodes) { long long t = 0; for (int b = 0; b < nb; b++) t += nodes[(size_t)b]; *out_nodes = t; }
+    MipRoute & rt = mip_route();
+    rt.device_trees += nb;
+    if (extra > rt.free_vars) rt.free_vars = extra;
     return 0;
 }
 
@@ -551,6 +564,49 @@ int mip_batch_eq(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, cons
     return 0;
 }
 
+// nb independent MIPs of one shape under the caller's variable constraints vc [cols - 1][cols], shared by the batch (what
+// the single-problem entry points take): equalities and / or inequalities at the root, an optional rational_indicator.
+// A vc that is a sign pattern (vc_sign_pattern: every variable x >= 0 or free) goes to the device tree walk in one launch
+// where the node LPs, widened by the free variables' twins, fit; every other vc -- and what does not fit -- to the host
+// controller with the caller's vc, so the call is defined wherever MIP::maxm / minm is.
+template <class S>
+int mip_batch_vc(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
+                 const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
+                 long long * out_nodes)
+{
+    if (!ctx || nb < 0 || !tgtf || !vc || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) || (eq_rows > 0 && !eqs) ||
+        (leq_rows > 0 && !leq) || cols < 2 || !out_status || !out_v)
+        return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
+    if (on_device) {
+        std::vector<int> fv;
+        if (vc_sign_pattern(vc, cols - 1, cols, fv) && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows, (int)fv.size())) {
+            const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes,
+                                               allow_rational, eqs, eq_rows, fv.data(), (int)fv.size());
+            if (rc != XPG_ERR_UNSUPPORTED) return rc;
+        }
+    }
+    std::vector<MipTask<S> > tasks(nb);
+    for (int b = 0; b < nb; b++)
+        tasks[b].start(make_problem<S>(tgtf + (size_t)b * cols, vc, cols - 1, eq_rows > 0 ? eqs + (size_t)b * eq_rows * cols : (const S *)0, eq_rows,
+                                       leq_rows > 0 ? leq + (size_t)b * leq_rows * cols : (const S *)0, leq_rows, cols),
+                       is_max, is_bin, allow_rational);
+    int rc = run_mip_tasks<S>(ctx, kind, tasks);
+    if (rc) return rc;
+    long long nodes = 0;
+    for (int b = 0; b < nb; b++) {
+        const MipTask<S> & T = tasks[b];
+        out_status[b] = T.final_status;
+        out_v[b] = T.v;
+        nodes += T.nodes;
+        if (T.final_status == XPG_IP_SUCC && out_sol && (int)T.sol.size() == cols)
+            for (int j = 0; j < cols; j++) out_sol[(size_t)b * cols + j] = T.sol[j];
+    }
+    if (out_nodes) *out_nodes = nodes;
+    return 0;
+}
+
 // SIX::reviseTargetFunc on the all-ones objective (lpsol.h:2053-2074, linsys.cpp:851-862).
 inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, int cols, int rhs)
 {
@@ -605,14 +661,32 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
     if (!ctx || nb < 0 || !mats || rows <= 0 || cols < 2 || !out_empty || rhs_idx < 1 || rhs_idx > cols - 1) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     const int last = cols - 1, nsym = last - rhs_idx;
-    // No constant symbols and the default x >= 0: the whole test stays on the device -- reduce, the feasibility
-    // objectives, the integer maxm walk, the minm walk of what that left open -- and only the verdicts come back.
+    // Variables that are x >= 0 or free (no vc, or a vc that is a sign pattern) and either no constant symbols or -- opt-in --
+    // the symbols as free variables: the whole test stays on the device -- reduce, the feasibility objectives, the integer
+    // maxm walk, the minm walk of what that left open -- and only the verdicts come back. With symbols, move2var runs on the
+    // host in front of the upload; the walks' free list is the caller's free variables, then every symbol.
     static const bool on_dev = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_dev && nsym == 0 && !vc_in && mip_device_fits<R32>(rows, cols, false) &&
+    const bool widen_dev = nsym > 0 && symbols_as_vars != 0;
+    std::vector<int> fv;
+    const bool pattern = !vc_in || vc_sign_pattern(vc_in, rhs_idx, rhs_idx + 1, fv);
+    if (widen_dev) for (int j = rhs_idx; j < last; j++) fv.push_back(j);
+    const int extra = (int)fv.size();
+    if (on_dev && (nsym == 0 || widen_dev) && pattern && mip_device_fits<R32>(rows, cols, false, 0, extra) &&
         lineq_lds_bytes(rows, cols) <= 160 * 1024 && rows <= 32767) {
         const int n = cols - 1, rmax = rows + n, depth = n + 2;
         const size_t bm = (size_t)nb * rows * cols * 8, bt = (size_t)nb * cols * 8;
-        DevBuf dm, dt, dk, dok, dact, demp, dst, dv, dn, dws;
+        DevBuf dm, dt, dk, dok, dact, demp, dst, dv, dn, dws, dfv;
+        std::vector<R32> moved;
+        if (nsym > 0) {
+            moved.resize((size_t)nb * rows * cols);
+            for (int b = 0; b < nb; b++)
+                move2var_one(mats + (size_t)b * rows * cols, moved.data() + (size_t)b * rows * cols, rows, cols, rhs_idx, rhs_idx + 1, last);
+            mats = moved.data();
+        }
+        if (extra > 0) {
+            XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
+            XPG_TRY(hipMemcpyAsync(dfv.p, fv.data(), (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
         XPG_TRY(dm.alloc(ctx, bm)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
         XPG_TRY(dok.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dact.alloc(ctx, (size_t)nb * 4)); XPG_TRY(demp.alloc(ctx, (size_t)nb * 4));
         XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(dn.alloc(ctx, (size_t)nb * 4));
@@ -626,10 +700,10 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
         std::vector<int32_t> nodes_a((size_t)nb, 0), nodes_b((size_t)nb, 0);
         for (int pass = 0; pass < 2; pass++) {
             const bool is_max = pass == 0;
-            const MipGeom g = mip_geom<R32>(ctx, nb, rmax, n, is_max);
+            const MipGeom g = mip_geom<R32>(ctx, nb, rmax, n + extra, is_max);
             const size_t lds = g.lds;
             const int threads = g.threads, grid = g.grid;
-            const size_t ws_words = mip_ws_words(rmax, cols, depth);
+            const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
             const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
             if (pass == 0) XPG_TRY(dws.alloc(ctx, (size_t)(cus * 32 < nb ? cus * 32 : nb) * ws_words * 8));   // the largest grid of either pass
             XPG_TRY(hipMemsetAsync(dn.p, 0, (size_t)nb * 4, ctx->stream));
@@ -637,7 +711,7 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
             hipLaunchKernelGGL((k_mip_tree<R32>), dim3(grid), dim3(threads), lds, ctx->stream, nb, (const R32 *)dt.p, (const R32 *)dm.p,
                                rows, cols, is_max ? 1 : 0, 0, rmax, depth, (unsigned long long *)dws.p, ws_words,
                                (int32_t *)dst.p, (R32 *)dv.p, (R32 *)0, (int *)dn.p, (const int *)dk.p, (const int *)dact.p, (const uint8_t *)0,
-                               (const R32 *)0, 0, grid, (int *)0);
+                               (const R32 *)0, 0, grid, (int *)0, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
             XPG_TRY(hipGetLastError());
             XPG_TRY(hipMemcpyAsync(pass == 0 ? nodes_a.data() : nodes_b.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
             hipLaunchKernelGGL(k_dep_update, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, (const int32_t *)dst.p,
@@ -646,6 +720,9 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
         XPG_TRY(hipMemcpyAsync(out_empty, demp.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
         if (out_nodes) { long t = 0; for (int b = 0; b < nb; b++) t += nodes_a[(size_t)b] + nodes_b[(size_t)b]; *out_nodes = t; }
+        MipRoute & rt = mip_route();                     // a tree that was walked counted at least its root
+        for (int b = 0; b < nb; b++) rt.device_trees += (nodes_a[(size_t)b] > 0) + (nodes_b[(size_t)b] > 0);
+        if (extra > rt.free_vars) rt.free_vars = extra;
         return 0;
     }
     std::vector<R32> work((size_t)nb * rows * cols);

@@ -11,10 +11,12 @@
 // LPs (1024 knapsacks of 24 variables: 22-29 ms, against 13 ms for the reference arithmetic restated on all 256 host cores). Here a tree
 // never leaves its workgroup and the trees do not wait for each other.
 //
-// Scope: x >= 0 (the caller's vc is -I: what xpg_mip_batch_* and the reference's own caller, PolyTran::FeaSchedule,
-// src/eng/poly.cpp:5118-5130, pass), inequalities and -- round 3 -- equalities at the root, binary or integer
-// branching, with or without a rational_indicator (lpsol.h:2369-2393). General variable constraints (free
-// variables, bounds other than x >= 0) keep the host controller.
+// Scope: a vc that is a SIGN PATTERN -- every variable either x >= 0 (diagonal -1: all of them is what xpg_mip_batch_* and
+// PolyTran::FeaSchedule, src/eng/poly.cpp:5118-5130, pass) or free (diagonal 0: what Lineq::initVarConstraint,
+// src/com/linsys.cpp:803-819, makes for a variable without a sign) --, inequalities and -- round 3 -- equalities at the
+// root, binary or integer branching, with or without a rational_indicator (lpsol.h:2369-2393). A free variable is split
+// v = v' - v'' in front of every node LP as SIX::normalize does (mip_split_free). Any other vc (bounds other than
+// x >= 0, rows that couple variables) keeps the host controller.
 #pragma once
 #include "batch_kernels.hip.h"
 
@@ -34,26 +36,31 @@ template <class S> struct MipWs {
     int * ctl;        // have_best, top, nodes, final_status, speculation sequence number
     S * spec_y;       // [depth][cols] raw LP solution of frame f's CEILING child, solved ahead by a helper workgroup
     int * spec_ctl;   // [depth][2]: (sequence number << 3) | state, the child's SIX status
+    S * N;            // [rmax][cols + extra]  with free variables: the node's inequalities widened by their twins
+    S * wobj;         // [cols + extra]        and the objective widened the same way (y then has cols + extra entries)
 };
-__host__ __device__ inline size_t mip_ws_words(int rmax, int cols, int depth)
+__host__ __device__ inline size_t mip_ws_words(int rmax, int cols, int depth, int extra = 0)
 {
     size_t w = (size_t)rmax * cols + 3 * (size_t)cols + (size_t)depth * cols + depth + 2;
     w += (size_t)depth * cols;                                   // spec_y
+    if (extra > 0) w += (size_t)rmax * (cols + extra) + (size_t)(cols + extra) + extra;   // N, wobj, the twins' entries of y
     w += ((size_t)depth * 6 + cols + 8 + (size_t)depth * 2 + 1) / 2;
     return (w + 1) & ~(size_t)1;
 }
-template <class S> __device__ __forceinline__ MipWs<S> mip_ws_carve(unsigned long long * base, int rmax, int cols, int depth)
+template <class S> __device__ __forceinline__ MipWs<S> mip_ws_carve(unsigned long long * base, int rmax, int cols, int depth, int extra = 0)
 {
     MipWs<S> w;
     S * p = (S *)base;
     w.L = p; p += (size_t)rmax * cols;
-    w.y = p; p += cols;
+    w.y = p; p += cols + extra;
     w.sol = p; p += cols;
     w.best_sol = p; p += cols;
     w.kept_sol = p; p += (size_t)depth * cols;
     w.kept_v = p; p += depth;
     w.vals = p; p += 2;
     w.spec_y = p; p += (size_t)depth * cols;
+    w.N = p; w.wobj = p;
+    if (extra > 0) { p += (size_t)rmax * (cols + extra); w.wobj = p; p += cols + extra; }
     int * q = (int *)p;
     w.frame = q; q += depth * 6;
     w.forks = q; q += cols;
@@ -372,11 +379,59 @@ template <class S> __device__ bool mip_feed(const MipWs<S> & w, int cols, bool i
     }
 }
 
+// The free-variable split of SIX::normalize (lpsol.h:1365-1392) for the node mip_build_node left in w.L -- AFTER the fold
+// of the equalities, as normalize_cells_host (six_host.hip.h) does it: N = the node's columns as they are, behind them one
+// twin per free variable = its column times -1 with Matrix::mulOfColumn's arithmetic (scaled(): what k_normal_form does;
+// for fp64 it decides the sign of zeros), the constant column last; the objective likewise (normalize_plan). One pass
+// over the cells by all threads.
+template <class S> __device__ __forceinline__ void mip_split_free(const MipWs<S> & w, const S * tgtf, int rows, int cols,
+                                                                  const int * free_var, int extra)
+{
+    const int n0 = cols - 1, wc = cols + extra;
+    const S m1 = minus_one<S>();
+    const int mode = scale_mode(m1);
+    for (int t = threadIdx.x; t < rows * wc; t += blockDim.x) {
+        const int i = t / wc, c = t - i * wc;
+        const bool twin = c >= n0 && c < wc - 1;
+        const int sc = c < n0 ? c : (twin ? free_var[c - n0] : n0);
+        S x = w.L[(size_t)i * cols + sc];
+        if (twin) x = scaled(x, m1, mode);
+        w.N[t] = x;
+    }
+    for (int c = threadIdx.x; c < wc; c += blockDim.x) {
+        const bool twin = c >= n0 && c < wc - 1;
+        S x = tgtf[c < n0 ? c : (twin ? free_var[c - n0] : n0)];
+        if (twin) x = scaled(x, m1, mode);
+        w.wobj[c] = x;
+    }
+    __syncthreads();
+}
+// The LP of the node in w.L [rows x cols], by all threads: the SIX status, and on success the raw values of the ORIGINAL
+// variables in w.y[0 .. cols - 1). With free variables the LP is the widened one and its answer is folded back,
+// y[v] = y[v'] - y[v''] in the order of the list (finish_host, six_host.hip.h).
+template <class S> __device__ __forceinline__ int mip_solve_node(Small<S> & P, const MipWs<S> & w, const S * tgtf, int rows, int cols,
+                                                                 int is_max, const int * free_var, int extra, S * v_scratch)
+{
+    Source<S> src;
+    src.leq = w.L; src.tgtf = tgtf; src.m = rows; src.cols = cols; src.is_max = is_max;
+    if (extra > 0) {
+        mip_split_free<S>(w, tgtf, rows, cols, free_var, extra);
+        src.leq = w.N; src.tgtf = w.wobj; src.cols = cols + extra;
+    }
+    const int st = sm_solve_lp<S>(P, src, 10000u, /*raw_sol=*/1, w.y, v_scratch);
+    if (extra > 0 && st == XPG_SIX_SUCC) {
+        if (threadIdx.x == 0)
+            for (int k = 0; k < extra; k++) w.y[free_var[k]] = sub(w.y[free_var[k]], w.y[cols - 1 + k]);
+        __syncthreads();
+    }
+    return st;
+}
+
 template <class S> __global__ __launch_bounds__(256, 2)
 void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int cols, int is_max, int is_bin, int rmax,
                 int depth, unsigned long long * ws_all, size_t ws_words, int32_t * out_status, S * out_v, S * out_sol,
                 int * out_nodes, const int * rows_of, const int * active, const uint8_t * allow, const S * eq_all, int eq_rows,
-                int nmain, int * spq)
+                int nmain, int * spq, const int * free_var, int extra)
 {
     // eq_all / eq_rows (may be NULL / 0): eq_rows equalities per problem at the root.
     // allow (may be NULL): MIP's rational_indicator, one row of cols flags shared by the batch -- variables whose flag is
@@ -386,16 +441,18 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
     // are left alone.
     // nmain: the first nmain workgroups walk trees (tree b by workgroup b % nmain); spq != NULL: speculation (see SP_*): then
     // nmain == nb (one tree per walking workgroup, its workspace never reused) and the workgroups behind them are helpers.
+    // free_var / extra (may be NULL / 0): the batch's free variables, ascending; every node LP then has cols - 1 + extra
+    // variables (mip_split_free), which rmax-row workspace and LDS are sized for; the recursion keeps the original cols.
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int sh_ctl[8];
     __shared__ unsigned long long sh_v;                      // the node's own objective: recomputed by mip_feed
-    const int n = cols - 1;
+    const int n = cols - 1 + extra;                          // variables of a node LP
     Small<S> P;
     sm_carve(P, lds, is_max ? rmax : n, is_max ? n : rmax);
     if ((int)blockIdx.x >= nmain) {
         // ================================ a helper ======================================================
         if (!spq) return;
-        const MipWs<S> hw = mip_ws_carve<S>(ws_all + (size_t)blockIdx.x * ws_words, rmax, cols, depth);
+        const MipWs<S> hw = mip_ws_carve<S>(ws_all + (size_t)blockIdx.x * ws_words, rmax, cols, depth, extra);
         for (;;) {
             if (threadIdx.x == 0) {
                 int verdict = 0, blk = 0, f = 0, seq = 0;   // 0: leave, 1: next task, 2: solve
@@ -411,7 +468,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
                     __threadfence();
                     const int * e = spq_entry(spq, my);
                     blk = sp_load(&e[0]); f = sp_load(&e[1]); seq = sp_load(&e[2]);
-                    const MipWs<S> tw = mip_ws_carve<S>(ws_all + (size_t)blk * ws_words, rmax, cols, depth);
+                    const MipWs<S> tw = mip_ws_carve<S>(ws_all + (size_t)blk * ws_words, rmax, cols, depth, extra);
                     if (sp_cas(&tw.spec_ctl[2 * f], (seq << 3) | SP_REQ, (seq << 3) | SP_CLAIMED)) verdict = 2;   // (else: cancelled)
                 }
                 sh_ctl[4] = verdict; sh_ctl[5] = blk; sh_ctl[6] = f; sh_ctl[7] = seq;
@@ -422,7 +479,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
             if (verdict == 0) return;
             if (verdict == 1) continue;
             __threadfence();                                 // acquire: the walk's frames (published before the request)
-            const MipWs<S> tw = mip_ws_carve<S>(ws_all + (size_t)blk * ws_words, rmax, cols, depth);
+            const MipWs<S> tw = mip_ws_carve<S>(ws_all + (size_t)blk * ws_words, rmax, cols, depth, extra);
             const int b = blk;                               // (one tree per walking workgroup)
             // the frames of the path, copied; frame f in its ceiling stage
             for (int t = threadIdx.x; t < (f + 1) * 6; t += blockDim.x) {
@@ -435,11 +492,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
             const S * root = leq_all + (size_t)b * leq_rows * cols;
             const int my_rows = rows_of ? rows_of[b] : leq_rows;
             int st = mip_build_node<S>(hw, root, my_rows, (const S *)0, 0, cols, is_bin != 0, f + 1, &sh_ctl[1]);
-            if (st >= 0) {
-                Source<S> src;
-                src.leq = hw.L; src.tgtf = tgtf; src.m = st; src.cols = cols; src.is_max = is_max;
-                st = sm_solve_lp<S>(P, src, 10000u, /*raw_sol=*/1, hw.y, (S *)&sh_v);
-            }
+            if (st >= 0) st = mip_solve_node<S>(P, hw, tgtf, st, cols, is_max, free_var, extra, (S *)&sh_v);
             __syncthreads();
             for (int j = threadIdx.x; j < cols; j += blockDim.x) tw.spec_y[(size_t)f * cols + j] = hw.y[j];
             if (threadIdx.x == 0) tw.spec_ctl[2 * f + 1] = st;
@@ -454,7 +507,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
         const S * root = leq_all + (size_t)b * leq_rows * cols;
         const S * root_eq = eq_rows > 0 ? eq_all + (size_t)b * eq_rows * cols : (const S *)0;
         const int my_rows = rows_of ? rows_of[b] : leq_rows;
-        const MipWs<S> w = mip_ws_carve<S>(ws_all + (size_t)blockIdx.x * ws_words, rmax, cols, depth);
+        const MipWs<S> w = mip_ws_carve<S>(ws_all + (size_t)blockIdx.x * ws_words, rmax, cols, depth, extra);
         // MipTask::start
         for (int j = threadIdx.x; j < cols; j += blockDim.x) w.forks[j] = 0;
         for (int j = threadIdx.x; j < 2 * depth; j += blockDim.x) w.spec_ctl[j] = 0;
@@ -507,11 +560,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
             if (!parked) {
                 st = mip_build_node<S>(w, root, my_rows, root_eq, eq_rows, cols, is_bin != 0, top, &sh_ctl[1]);
                 MIP_T(0)
-                if (st >= 0) {
-                    Source<S> src;
-                    src.leq = w.L; src.tgtf = tgtf; src.m = st; src.cols = cols; src.is_max = is_max;
-                    st = sm_solve_lp<S>(P, src, 10000u, /*raw_sol=*/1, w.y, (S *)&sh_v);
-                }
+                if (st >= 0) st = mip_solve_node<S>(P, w, tgtf, st, cols, is_max, free_var, extra, (S *)&sh_v);
             }
             MIP_T(1)
             if (st == XPG_SIX_SUCC) mip_feed_products<S>(w, tgtf, cols);       // (st is the same in every thread)

@@ -170,6 +170,25 @@ int normalize_plan(const S * tgtf, const S * vc, int vc_rows, const S * eqs, int
     return 0;
 }
 
+// Which vc the device tree walk of MIP takes (mip_kernels.hip.h). A vc [cols - 1][cols] is a SIGN PATTERN when every
+// off-diagonal cell and the whole constant column are zero and every diagonal cell is -1 (x_j >= 0) or 0 (x_j free): what
+// Lineq::initVarConstraint makes (src/com/linsys.cpp:803-819). Its free variables -- the zero diagonals, ascending -- are
+// then exactly normalize_plan's "column without a nonzero" (lpsol.h:1322). Anything else is general: false.
+template <class S> bool vc_sign_pattern(const S * vc, int vc_rows, int cols, std::vector<int> & free_var)
+{
+    free_var.clear();
+    for (int i = 0; i < vc_rows; i++) {
+        const S * row = vc + (size_t)i * cols;
+        for (int j = 0; j < cols; j++) {
+            if (j == i) continue;
+            if (!eq(row[j], zero<S>())) return false;
+        }
+        if (eq(row[i], zero<S>())) free_var.push_back(i);
+        else if (!eq(row[i], minus_one<S>())) return false;
+    }
+    return true;
+}
+
 // The cells of the normal form on the host (the LDS route's small problems).
 template <class S>
 int normalize_cells_host(const S * eqs, const S * leq, NormalForm<S> & F)

@@ -1131,6 +1131,7 @@ int xpg_mip_maxm_rat32(xpg_ctx * ctx, const xpg_rat32 * tgtf, const xpg_rat32 * 
                        int is_bin, const uint8_t * ind, xpg_rat32 * out_v, xpg_rat32 * out_sol)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_solve<R32>(ctx, 1, true, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, vc_rows, (const R32 *)eq,
                           eq_rows, (const R32 *)leq, leq_rows, cols, ind, (R32 *)out_v, (R32 *)out_sol, 0);
 }
@@ -1139,6 +1140,7 @@ int xpg_mip_minm_rat32(xpg_ctx * ctx, const xpg_rat32 * tgtf, const xpg_rat32 * 
                        int is_bin, const uint8_t * ind, xpg_rat32 * out_v, xpg_rat32 * out_sol)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_solve<R32>(ctx, 1, false, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, vc_rows, (const R32 *)eq,
                           eq_rows, (const R32 *)leq, leq_rows, cols, ind, (R32 *)out_v, (R32 *)out_sol, 0);
 }
@@ -1147,6 +1149,7 @@ int xpg_mip_maxm_f64(xpg_ctx * ctx, const double * tgtf, const double * vc, int 
                      double * out_v, double * out_sol)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_solve<F64>(ctx, 0, true, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, vc_rows, (const F64 *)eq,
                           eq_rows, (const F64 *)leq, leq_rows, cols, ind, (F64 *)out_v, (F64 *)out_sol, 0);
 }
@@ -1155,6 +1158,7 @@ int xpg_mip_minm_f64(xpg_ctx * ctx, const double * tgtf, const double * vc, int 
                      double * out_v, double * out_sol)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_solve<F64>(ctx, 0, false, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, vc_rows, (const F64 *)eq,
                           eq_rows, (const F64 *)leq, leq_rows, cols, ind, (F64 *)out_v, (F64 *)out_sol, 0);
 }
@@ -1163,6 +1167,7 @@ int xpg_has_solution_rat32(xpg_ctx * ctx, const xpg_rat32 * leq, int leq_rows, c
                            int is_unique_sol)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return has_solution(ctx, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols,
                         rhs_idx, is_int_sol != 0, is_unique_sol != 0);
 }
@@ -1172,6 +1177,7 @@ int xpg_mip_batch_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg
                         long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_batch<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)leq, leq_rows, cols,
                           out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
@@ -1179,6 +1185,7 @@ int xpg_mip_batch_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const doubl
                       int leq_rows, int cols, int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_batch<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)leq, leq_rows, cols,
                           out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
@@ -1187,6 +1194,7 @@ int xpg_mip_batch_eq_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const 
                            xpg_rat32 * out_sol, long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_batch_eq<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows,
                              cols, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
@@ -1195,6 +1203,7 @@ int xpg_mip_batch_eq_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const do
                          long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     return mip_batch_eq<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)leq, leq_rows, (const F64 *)eq, eq_rows,
                              cols, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
@@ -1202,6 +1211,7 @@ int xpg_dep_is_empty_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, 
                                  int32_t * out_empty, long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, cols - 1, (const R32 *)0, out_empty, &n);
     if (out_nodes) *out_nodes = n;
@@ -1211,6 +1221,7 @@ int xpg_dep_is_empty_batch_ex_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mat
                                     const xpg_rat32 * vc, int32_t * out_empty, long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, (const R32 *)vc, out_empty, &n);
     if (out_nodes) *out_nodes = n;
@@ -1220,11 +1231,56 @@ int xpg_dep_is_empty_batch_mode_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * m
                                       const xpg_rat32 * vc, int mode, int32_t * out_empty, long long * out_nodes)
 {
     XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
     if (mode != XPG_DEP_PARITY && mode != XPG_DEP_SYMBOLS_AS_VARS) return XPG_ERR_SHAPE;
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, (const R32 *)vc, out_empty, &n, mode == XPG_DEP_SYMBOLS_AS_VARS ? 1 : 0);
     if (out_nodes) *out_nodes = n;
     return rc;
+}
+int xpg_mip_batch_vc_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                           const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, const uint8_t * ind,
+                           int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol, long long * out_nodes)
+{
+    XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
+    return mip_batch_vc<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows,
+                             (const R32 *)leq, leq_rows, cols, ind, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
+}
+int xpg_mip_batch_vc_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf, const double * vc,
+                         const double * eq, int eq_rows, const double * leq, int leq_rows, int cols, const uint8_t * ind,
+                         int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
+{
+    XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
+    return mip_batch_vc<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows,
+                             (const F64 *)leq, leq_rows, cols, ind, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
+}
+// which route the trees of the calling thread's last MIP / has_solution / dep_is_empty call took (mip_host.hip.h MipRoute)
+int xpg_mip_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const MipRoute & r = mip_route();
+    const long long f[3] = { r.device_trees, r.host_trees, r.free_vars };
+    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test views: the vc classifier and the LDS fit test the MIP entry points route by
+int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free)
+{
+    if (!vc || !out_free || cols < 2 || vc_rows != cols - 1 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
+    std::vector<int> fv;
+    const bool pat = kind == 0 ? vc_sign_pattern((const F64 *)vc, vc_rows, cols, fv) : vc_sign_pattern((const R32 *)vc, vc_rows, cols, fv);
+    for (int j = 0; j < cols - 1; j++) out_free[j] = 0;
+    if (!pat) return 0;
+    for (size_t k = 0; k < fv.size(); k++) out_free[fv[k]] = 1;
+    return 1;
+}
+int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin, int extra)
+{
+    if (cols < 2 || leq_rows < 0 || eq_rows < 0 || extra < 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
+    return (kind == 0 ? mip_device_fits<F64>(leq_rows, cols, is_bin != 0, eq_rows, extra)
+                      : mip_device_fits<R32>(leq_rows, cols, is_bin != 0, eq_rows, extra)) ? 1 : 0;
 }
 } // extern "C"
 #endif

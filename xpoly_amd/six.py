@@ -400,6 +400,39 @@ def mip_batch_eq(ctx, is_max, is_bin, tgtf, leq, eq, kind=RAT):
     return st, v, sol, nodes.value
 
 
+def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator=None, kind=RAT):
+    """nb independent MIPs under the variable constraints vc [cols - 1, cols(,2)] shared by the batch: tgtf [nb, cols(,2)],
+    leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)] or None (not both None), rational_indicator cols bytes or None.
+    A vc that is a sign pattern (diagonal -1 = x >= 0, 0 = free, nothing else) is walked on the device, free variables split
+    v = v' - v'' in front of every node LP; any other vc by the host controller. Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
+    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
+    leq = None if leq is None else as_kind(leq, kind, 3)
+    eq = None if eq is None else as_kind(eq, kind, 3)
+    nb, cols = tgtf.shape[0], tgtf.shape[1]
+    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
+        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
+    for a in (leq, eq):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq is None else leq.shape[1]
+    eq_rows = 0 if eq is None else eq.shape[1]
+    ind = None if rational_indicator is None else np.ascontiguousarray(rational_indicator, dtype=np.uint8)
+    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    nodes = C.c_longlong()
+    fn = lib().xpg_mip_batch_vc_rat32 if kind == RAT else lib().xpg_mip_batch_vc_f64
+    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(vc), vp(eq), C.c_int(eq_rows),
+                 vp(leq), C.c_int(rows), C.c_int(cols), vp(ind), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch_vc")
+    return st, v, sol, nodes.value
+
+
+def mip_last_route():
+    """Which route the trees of the calling thread's last MIP / has_solution / dep_is_empty call took (xpg_mip_last_route):
+    device_trees walked by the tree-walk kernel, host_trees by the host controller, free_vars split per tree on the device."""
+    out = (C.c_longlong * 3)()
+    lib().xpg_mip_last_route(out, C.c_int(3))
+    return dict(device_trees=int(out[0]), host_trees=int(out[1]), free_vars=int(out[2]))
+
+
 def dep_is_empty_batch(ctx, mats, rhs_idx=None, vc=None):
     """DepPoly::is_empty(keepit, vc) (src/eng/poly.cpp:530-573) for a stack of dependence polyhedra
     [nb, rows, cols(,2)]: the constant is column rhs_idx (default: the last), the columns behind it are constant
