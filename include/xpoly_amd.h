@@ -346,6 +346,13 @@ int xpg_mip_last_route(long long * out, int n);
  * variables (the LDS budget of its largest node LP). */
 int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free);
 int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin, int extra);
+/* Host-only view for tests (no device needed): the launch geometry of the batched LP kernel (xpg_six_batch_*) for nb LPs
+ * that are solved as R rows x V variables (maxm: R = m, V = cols - 1; minm solves the dual: the two swap) on a device of
+ * num_cus compute units.  Fills min(n, 10) entries: out[0] LDS bytes of one LP, [1] 1 when the call is refused
+ * (XPG_ERR_UNSUPPORTED), [2] cells, [3] threads per workgroup, [4] LPs per compute unit by LDS, [5] 1 for the five-per-CU
+ * kernel instance, [6] workgroups (before continuation workgroups), [7] seats, [8] 1 when the shape can run in time
+ * slices, [9] 1 when nb is large enough for them. */
+int xpg_test_batch_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n);
 /* DepPoly::is_empty(keepit, vc = NULL), src/eng/poly.cpp:530-573, for nb dependence polyhedra
  * mats[nb][rows][cols] without constant symbols (constant in the last column):
  * Lineq::reduce pre-filter, then Lineq::has_solution(is_int_sol, is_unique_sol) = MIP::maxm

@@ -936,6 +936,14 @@ template <class S> __host__ __device__ inline size_t small_lds_bytes(int R, int 
     return (b + 15) & ~(size_t)15;
 }
 
+// What k_batch / k_batch_ragged hold in LDS besides the arrays above: the reduction scratch of the inlined helpers (256 bytes)
+// and k_batch's sh_next (the code object reports group_segment_fixed_size = 272 / 256). An LP fits one CU when its arrays
+// and these fit 160 KB together; a rule on small_lds_bytes alone accepted shapes within 272 bytes of the limit (Rational
+// 126 x 24: 163 808 bytes) and their launch then failed with XPG_ERR_HIP instead of a clean XPG_ERR_UNSUPPORTED.
+enum { SMALL_LDS_STATIC = 272 };
+template <class S> __host__ __device__ inline bool small_lds_fits(int R, int V)
+{ return small_lds_bytes<S>(R, V) + SMALL_LDS_STATIC <= (size_t)160 * 1024; }
+
 #ifdef XPG_STAMPS
 static __device__ unsigned long long g_lp_ticks[8];     // diagnostic builds: ticks in phase one / plain build / main solve, pivots, counts
 #endif
@@ -1240,7 +1248,7 @@ int batch_dev_ragged(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S 
         return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     const size_t lds = small_lds_bytes<S>(max_R, max_V);
-    if (lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    if (!small_lds_fits<S>(max_R, max_V)) return XPG_ERR_UNSUPPORTED;
     const int cells = max_R * (max_V + max_R + 2);
     int threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);
     const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
@@ -1253,6 +1261,36 @@ int batch_dev_ragged(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S 
     return 0;
 }
 
+// The launch geometry of k_batch for LPs solved as R rows x V variables, nb of them on a device of num_cus compute units:
+// what batch_dev launches with, and what xpg_test_batch_geometry shows the tests (host only).
+struct BatchGeom {
+    size_t lds;             // small_lds_bytes: the LDS of one LP
+    int refused;            // one LP (its arrays and the kernel's own LDS) must fit one CU's 160 KB (XPG_ERR_UNSUPPORTED)
+    int cells, threads, per_cu, five, grid, seats;
+    int slice_shape;        // time slices: the shape's pivot loop can hand an LP back (sm_solve's `overlapped`)
+    int slice_crowded;      // ... and the launch holds more LPs than the chip seats at once
+};
+template <class S> inline BatchGeom batch_geometry(int R, int V, int nb, int num_cus)
+{
+    BatchGeom g;
+    g.lds = small_lds_bytes<S>(R, V);
+    g.refused = small_lds_fits<S>(R, V) ? 0 : 1;
+    // measured on MI355X (32x64 LPs): 64 / 128 / 256 threads -> 61k / 91k / 118k LPs/s
+    g.cells = R * (V + R + 2);
+    g.threads = g.cells >= 2048 ? 256 : (g.cells >= 1024 ? 128 : 64);
+    g.per_cu = (int)((160 * 1024) / g.lds) > 0 ? (int)((160 * 1024) / g.lds) : 1;
+    // One workgroup per LP up to 64 per CU-slot: the hardware's dispatcher then balances LPs of very different
+    // lengths (the dependence-test family mixes phase-1 failures of a few dozen pivots with runs of thousands)
+    // better than a fixed grid-stride assignment does.
+    g.grid = 256 * (g.per_cu > 16 ? 16 : g.per_cu) * 64;
+    if (g.grid > nb) g.grid = nb;
+    g.five = g.per_cu >= 5 ? 1 : 0;
+    g.seats = num_cus * (g.five ? (g.per_cu < 5 ? g.per_cu : 5) : (g.per_cu < 4 ? g.per_cu : 4));
+    g.slice_shape = g.threads >= 128 && R <= 64 && R + V <= 127 ? 1 : 0;
+    g.slice_crowded = nb > g.seats + g.seats / 4 ? 1 : 0;
+    return g;
+}
+
 template <class S>
 int batch_dev(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * leq, int m, int cols,
               unsigned max_iter, int32_t * out_status, S * out_v, S * out_sol, uint32_t * out_pivots,
@@ -1263,19 +1301,13 @@ int batch_dev(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * leq, 
     if (nb == 0) return 0;
     const int n = cols - 1;
     const int R = is_max ? m : n, V = is_max ? n : m;
-    const size_t lds = small_lds_bytes<S>(R, V);
-    if (lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;     // one LP must fit one CU's LDS
-    // measured on MI355X (32x64 LPs): 64 / 128 / 256 threads -> 61k / 91k / 118k LPs/s
-    const int cells = R * (V + R + 2);
-    const int threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);
+    const BatchGeom g = batch_geometry<S>(R, V, nb, ctx->num_cus);
+    const size_t lds = g.lds;
+    if (g.refused) return XPG_ERR_UNSUPPORTED;            // one LP must fit one CU's LDS
+    const int threads = g.threads, seats = g.seats;
     if (const char * c = xpg_hook("XPG_BATCH_COUNT_CLOSES")) { if (c[0] == '1') raw_sol |= 2; }   // profiling aid
-    const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
-    // One workgroup per LP up to 64 per CU-slot: the hardware's dispatcher then balances LPs of very different
-    // lengths (the dependence-test family mixes phase-1 failures of a few dozen pivots with runs of thousands)
-    // better than a fixed grid-stride assignment does.
-    int grid = 256 * (per_cu > 16 ? 16 : per_cu) * 64;
-    if (grid > nb) grid = nb;
-    const bool five = per_cu >= 5;
+    int grid = g.grid;
+    const bool five = g.five != 0;
     // Time slices (k_batch): where the pivot loop can hand an LP back (sm_solve's `overlapped` shapes) and the launch holds
     // more LPs than the chip seats at once, so that LPs wait for slots at all. XPG_BATCH_SLICE=0 turns them off, =n sets
     // the slice (iterations of the LP's own solve per turn; 8192 dense LPs: 416.6 k LPs/s at 256, 418.4 k at 384-512, 414.6 k
@@ -1283,9 +1315,8 @@ int batch_dev(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * leq, 
     static const unsigned slice_env = [] { const char * e = xpg_env("XPG_BATCH_SLICE"); return e ? (unsigned)atoi(e) : 512u; }();
     BatchSlices Q;
     Q.slice = SM_NO_SLICE; Q.slice1 = SM_NO_SLICE; Q.nmain = grid; Q.ckpt = nullptr; Q.stride = 0; Q.queue = nullptr; Q.qmask = 0; Q.ctl = nullptr;
-    const int seats = ctx->num_cus * (five ? (per_cu < 5 ? per_cu : 5) : (per_cu < 4 ? per_cu : 4));
     static const bool slice_force = [] { const char * e = xpg_hook("XPG_BATCH_SLICE_FORCE"); return e && e[0] == '1'; }();   // tests: also when every LP has a seat
-    if (slice_env != 0u && threads >= 128 && R <= 64 && R + V <= 127 && (nb > seats + seats / 4 || slice_force) && grid == nb) {
+    if (slice_env != 0u && g.slice_shape && (g.slice_crowded || slice_force) && grid == nb) {
         const size_t stride = (CK_HEADER + lds + 255) & ~(size_t)255;
         size_t qcap = 1; while (qcap < (size_t)2 * nb) qcap <<= 1;
         const size_t need = stride * nb + qcap * 8 + 256;

@@ -976,7 +976,7 @@ int six_batch_ragged(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S 
         const long long le = leq_off[b] + (long long)rows[b] * cols[b], te = tg_off[b] + cols[b];
         leq_cells = le > leq_cells ? le : leq_cells; tg_cells = te > tg_cells ? te : tg_cells;
     }
-    if (small_lds_bytes<S>(max_R, max_V) <= 160 * 1024) {
+    if (small_lds_fits<S>(max_R, max_V)) {
         const size_t bl = (size_t)leq_cells * 8, bt = (size_t)tg_cells * 8;
         DevBuf dl, dt, ds, dv, dst, dr, dc, dlo, dto;
         XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(ds.alloc(ctx, bt)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8));
@@ -1281,6 +1281,15 @@ int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin,
     if (cols < 2 || leq_rows < 0 || eq_rows < 0 || extra < 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
     return (kind == 0 ? mip_device_fits<F64>(leq_rows, cols, is_bin != 0, eq_rows, extra)
                       : mip_device_fits<R32>(leq_rows, cols, is_bin != 0, eq_rows, extra)) ? 1 : 0;
+}
+// what batch_dev would launch nb LPs solved as R rows x V variables with, on a device of num_cus compute units
+int xpg_test_batch_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n)
+{
+    if (!out || n < 0 || R <= 0 || V <= 0 || nb <= 0 || num_cus <= 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
+    const BatchGeom g = kind == 0 ? batch_geometry<F64>(R, V, nb, num_cus) : batch_geometry<R32>(R, V, nb, num_cus);
+    const long long f[10] = { (long long)g.lds, g.refused, g.cells, g.threads, g.per_cu, g.five, g.grid, g.seats, g.slice_shape, g.slice_crowded };
+    for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
+    return 0;
 }
 } // extern "C"
 #endif
