@@ -236,6 +236,47 @@ int xpg_six_batch_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 *
                             int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol,
                             uint32_t * out_pivots);
 
+/* The same batches for problems WITH equalities and free variables -- what SIX::maxm / minm is called with elsewhere
+ * (Lineq::has_solution with is_int_sol = false, src/com/linsys.cpp:852-904, under the vc Lineq::initVarConstraint builds,
+ * :803-819): nb problems of one shape, tgtf[nb][cols], eq[nb][eq_rows][cols], leq[nb][leq_rows][cols] (either may be NULL
+ * with 0 rows, not both), vc[cols-1][cols] SHARED by the batch.  With a vc that is a sign pattern (see xpg_mip_*) and the
+ * largest normal form of the shape -- leq_rows + 2 eq_rows inequalities, one more variable per free one -- within 64 KB
+ * of LDS in the direction asked, SIX::normalize (src/com/lpsol.h:1290-1394, convertEq2Ineq :1197-1278), the solve and
+ * calcFinalSolution (:1851-1899) run on the device for the whole batch, one workgroup per LP in one launch; the call
+ * synchronises once.  Any other vc, or a larger shape: xpg_six_{maxm,minm}_* per problem, so the call is defined wherever
+ * SIX::maxm / minm is.  Same results on both routes, bit for bit those of the single-problem entry points.
+ * out_status[b] = SIX_* status, or XPG_ERR_REF_UNDEFINED for that problem alone (the reference reads past an equality's
+ * row, lpsol.h:1232; stage 1's undefined case); out_v[b] = 0 unless the status is 0; out_sol[b][cols] (trailing 1) is
+ * written on status 0 only.  Shape errors as the single-problem entry points (XPG_ERR_SHAPE); nb == 0 returns 0.
+ * The _dev forms take device pointers for EVERY array, vc included, and only enqueue (results after xpg_sync; a scratch
+ * area that has to grow waits for the stream first).  The host never sees vc there, so nothing falls back: the kernel
+ * derives the free variables itself, and out_status[b] = XPG_ERR_UNSUPPORTED for every b when vc is no sign pattern or
+ * the shape needs more than 64 KB (the call returns XPG_ERR_UNSUPPORTED when no vc could make the shape fit). */
+int xpg_six_batch_vc_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc,
+                         const double * eq, int eq_rows, const double * leq, int leq_rows, int cols,
+                         unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol);
+int xpg_six_batch_vc_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                           const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
+                           unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol);
+int xpg_six_batch_vc_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc,
+                             const double * eq, int eq_rows, const double * leq, int leq_rows, int cols,
+                             unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol);
+int xpg_six_batch_vc_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                               const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
+                               unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol);
+/* Evidence, no reference counterpart: which route the LPs of the calling thread's last xpg_six_batch_vc_* call took
+ * (answers are identical on both).  out[0] LPs reshaped and solved on the device, out[1] LPs that took the per-problem
+ * fallback, out[2] free variables split per LP on the device route (-1 after a _dev call: only the device has read vc).
+ * Fills min(n, 3) entries. */
+int xpg_six_batch_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the route rule of xpg_six_batch_vc_* for a vc [vc_rows][cols] of kind
+ * (0 fp64, 1 rational) and a shape.  Fills min(n, 5) entries: out[0] 1 for the device route, 0 for the fallback; [1] free
+ * variables (columns of vc without a nonzero); [2] rows of the largest normal form, leq_rows + 2 eq_rows; [3] its
+ * variables, cols - 1 + out[1]; [4] LDS bytes of that shape in the direction asked.  XPG_ERR_SHAPE unless
+ * vc_rows == cols - 1. */
+int xpg_test_six_batch_vc_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max,
+                               long long * out, int n);
+
 /* The same batches spread over the GPUs of one node from ONE caller thread -- what a C++ xpoly
  * caller of Lineq::has_solution (src/com/linsys.cpp:860-904) gets when it hands a SCoP's worth of
  * problems over at once.  devices[ndev] lists the HIP devices (NULL: 0 .. ndev-1; a device may be
@@ -471,7 +512,8 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
                                         const xpg_rat32 ** out_view, long long * row_offsets, int32_t * out_rows,
                                         int32_t * out_ok);
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
- * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks). */
+ * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
+ * scratch slots of xpg_six_batch_vc_*. */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the

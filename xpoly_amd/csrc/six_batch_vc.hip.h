@@ -1,0 +1,341 @@
+// Batches of small LPs WITH equalities and free variables (xpg_six_batch_vc_*): SIX::maxm / minm as the reference's callers
+// use it -- eq and leq per problem, one vc shared by the batch -- for nb problems in ONE launch. What six_solve does on the
+// host around a batch launch of one LP moves onto the device: SIX::normalize (src/com/lpsol.h:1290-1394) with
+// convertEq2Ineq (:1197-1278) in front of the LDS-resident solve, calcFinalSolution (:1851-1899) behind it. One workgroup
+// owns one LP from the caller's arrays to the answer:
+//   plan     convertEq2Ineq's choices (:1209-1222) from this LP's eq alone, by wave 0: column by column, a ballot over the
+//            equalities (lane = equality) finds the not yet used ones with a nonzero there; exactly one -> it is substituted
+//   fold     the substitutions on this LP's inequalities -- the cells of fold_eq / k_fold_eq (six_host.hip.h), the :1232
+//            quirk included: the leading value is read at the INEQUALITY's row index; where that leaves the row the LP ends
+//            XPG_ERR_REF_UNDEFINED and never meets the pivot loop
+//   form     the normal form N [rows x (n + 1)] (kept equalities as pairs -e / e, twins of the free variables) and the
+//            normalised objective, as k_normal_form / normalize_plan make them, into the workgroup's scratch slot
+//   solve    sm_solve_lp (batch_kernels.hip.h) on N, raw solution
+//   finish   finish_host: undo the split, the objective on the ORIGINAL tgtf in column order, reduce
+// The caller's leq / eq are staged in the LP's LDS block BEFORE sm_carve claims it and reshaped there. They always fit: the
+// solver's tableau alone holds (leq_rows + 2 eq_rows) x (n + rows + 2) cells for maxm, and for minm its three rows of
+// n + rows + 2 cells, three counters per column and n rows of the tableau outweigh the (leq_rows + eq_rows) x (cols + 2) cells
+// staged (the kernel checks, and refuses instead of writing past the block). The number of equalities kept as pairs differs per LP, so
+// the normal forms of a batch are ragged in rows: the slot is sized for the largest (leq_rows + 2 eq_rows), the LDS is
+// carved per LP for the rows it has -- the arrays a single call (six_solve -> k_batch, nb = 1) carves, so both give the same
+// bits. Slots belong to the WORKGROUP, not the LP (a workgroup walks its LPs one after the other): the scratch of a launch
+// is grid x slot whatever nb is, the grid is cut so that it stays under SIX_VC_SCRATCH_MAX, and nothing is chunked.
+#pragma once
+#include "six_host.hip.h"
+
+namespace xpg {
+
+// Which route the LPs of the calling thread's last xpg_six_batch_vc_* call took (xpg_six_batch_last_route).
+struct SixVcRoute { long long device, fallback, free_vars; };
+inline SixVcRoute & six_vc_route() { static thread_local SixVcRoute r = {0, 0, 0}; return r; }
+
+enum { SIX_VC_LDS_MAX = 64 * 1024, SIX_VC_MAX_EQ = 4096 };
+#define SIX_VC_SCRATCH_MAX ((size_t)256 << 20)
+
+// THE route rule (the launch and xpg_test_six_batch_vc_plan both ask it): the batch is reshaped and solved on the device
+// when vc is a sign pattern (vc_sign_pattern) and the largest normal form a problem of the batch can have --
+// leq_rows + 2 eq_rows inequalities (no equality substituted), cols - 1 + nfree variables -- fits 64 KB of LDS in the
+// direction asked: NormalForm::fits_lds's bound, so a problem the device route takes is one six_solve solves LDS-resident.
+struct SixVcPlan { int device, nfree, rows_max, n; size_t lds; };
+template <class S> __host__ __device__ inline SixVcPlan six_vc_plan(bool pattern, int nfree, int leq_rows, int eq_rows, int cols, bool is_max)
+{
+    SixVcPlan p;
+    p.nfree = nfree; p.rows_max = leq_rows + 2 * eq_rows; p.n = cols - 1 + nfree;
+    p.lds = small_lds_bytes<S>(is_max ? p.rows_max : p.n, is_max ? p.n : p.rows_max);
+    p.device = pattern && p.lds <= (size_t)SIX_VC_LDS_MAX && eq_rows <= SIX_VC_MAX_EQ ? 1 : 0;
+    return p;
+}
+
+// The scratch slot of one workgroup in HBM, in 8-byte cells: fv (the free variables, ascending) | N | obj | y | v.
+// And what the reshaping holds in LDS while it runs (work_cells): L (the inequalities, folded in place) | E | coef, inv (per
+// inequality, the step's coefficient and 1 / lead) | steps (pairs of int) | rest (int).
+struct SixVcSlot { size_t fv, N, obj, y, v, cells; size_t L, E, coef, inv, steps, rest, work_cells; };
+__host__ __device__ inline SixVcSlot six_vc_slot(int leq_rows, int eq_rows, int cols, int nfree)
+{
+    const size_t n0 = (size_t)cols - 1, n = n0 + (size_t)nfree, rows_max = (size_t)leq_rows + 2 * (size_t)eq_rows;
+    const size_t nst = (size_t)eq_rows < n0 ? (size_t)eq_rows : n0;
+    SixVcSlot s;
+    size_t o = 0;
+    s.fv = o; o += (n0 + 1) / 2;
+    s.N = o; o += rows_max * (n + 1);
+    s.obj = o; o += n + 1;
+    s.y = o; o += n + 1;
+    s.v = o; o += 1;
+    size_t w = 0;
+    s.L = w; w += (size_t)leq_rows * cols;
+    s.E = w; w += (size_t)eq_rows * cols;
+    s.coef = w; w += (size_t)leq_rows;
+    s.inv = w; w += (size_t)leq_rows;
+    s.steps = w; w += nst;                       // 2 ints per step
+    s.rest = w; w += ((size_t)eq_rows + 1) / 2;
+    s.work_cells = w;
+    s.cells = (o + 31) & ~(size_t)31;        // slots start on 256-byte lines
+    return s;
+}
+
+// One workgroup per LP, grid-stride over the batch. vc is read on the device (the _dev entry points hold it there): every
+// workgroup derives the free list once; a vc that is no sign pattern, or a normal form beyond the launch's LDS, ends
+// every LP XPG_ERR_UNSUPPORTED (the host-array entry point has sent such a batch to six_solve instead and never launches).
+template <class S> __global__ __launch_bounds__(256, 4)
+void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ vc, const S * __restrict__ eqs, int eq_rows,
+                    const S * __restrict__ leq, int leq_rows, int cols, int is_max, unsigned max_iter, unsigned lds_bytes,
+                    unsigned long long * __restrict__ slots, unsigned long long slot_cells,
+                    int32_t * __restrict__ out_status, S * __restrict__ out_v, S * __restrict__ out_sol)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int hdr[4];                                       // free variables, undefined flag, steps, kept equalities
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
+    const int n0 = cols - 1;
+    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
+    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
+    const S m1 = minus_one<S>();
+    const int mode1 = scale_mode(m1);
+
+    // ---- vc: sign pattern? which variables are free (lpsol.h:1321-1339: a column of vc without a nonzero) ----
+    bool bad = false;
+    for (int t = tid; t < n0 * cols; t += nt) {
+        const int i = t / cols, j = t - i * cols;
+        const S c = vc[t];
+        if (j == i) bad |= !eq(c, zero<S>()) && !eq(c, m1);
+        else bad |= !eq(c, zero<S>());
+    }
+    if (tid < 64) {
+        int cnt = 0;
+        for (int base = 0; base < n0; base += 64) {
+            const int j = base + lane;
+            const bool fr = j < n0 && eq(vc[(size_t)j * cols + j], zero<S>());
+            const unsigned long long mask = __ballot(fr);
+            if (fr) fv[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = j;
+            cnt += __popcll(mask);
+        }
+        if (tid == 0) hdr[0] = cnt;
+    }
+    const bool general = __syncthreads_or(bad ? 1 : 0) != 0;     // (a barrier: hdr[0] and fv are the workgroup's now)
+    const int nfree = hdr[0], n = n0 + nfree;
+    const SixVcPlan plan = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, is_max != 0);
+    const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree);
+    if (!plan.device || plan.lds > (size_t)lds_bytes || sl.work_cells * 8 > (size_t)lds_bytes) {
+        for (int lp = (int)blockIdx.x * nt + tid; lp < nb; lp += (int)gridDim.x * nt) { out_status[lp] = XPG_ERR_UNSUPPORTED; out_v[lp] = zero<S>(); }
+        return;
+    }
+    S * const N = slot + sl.N; S * const obj = slot + sl.obj; S * const y = slot + sl.y; S * const vout = slot + sl.v;
+    S * const work = (S *)lds;
+    S * const L = work + sl.L; S * const E = work + sl.E; S * const coef = work + sl.coef; S * const inv = work + sl.inv;
+    int * const steps = (int *)(work + sl.steps); int * const rest = (int *)(work + sl.rest);
+    const int lcells = leq_rows * cols, ecells = eq_rows * cols;
+
+    for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
+        const S * tg = tgtf + (size_t)lp * cols;
+        __syncthreads();                                         // the LP before is through with the LDS block and the slot
+        // ---- stage: the caller's cells as they lie, whole rows by consecutive lanes
+        {
+            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
+            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
+            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
+            if (tid == 0) hdr[1] = 0;
+        }
+        __syncthreads();
+        // ---- plan (lpsol.h:1209-1222) by wave 0: lane l holds equalities l, l + 64, ...; bit c of `used`: equality 64 c + l
+        if (tid < 64) {
+            unsigned long long used = 0ull;
+            int ns = 0, nrest = 0;
+            if (leq_rows > 0)
+                for (int j = 0; j < n0; j++) {
+                    int hits = 0;
+                    for (int c = 0; c * 64 < eq_rows; c++) {
+                        const int i = c * 64 + lane;
+                        const bool hit = i < eq_rows && !((used >> c) & 1ull) && ne(E[i * cols + j], zero<S>());
+                        hits += __popcll(__ballot(hit));
+                    }
+                    if (hits != 1) continue;
+                    for (int c = 0; c * 64 < eq_rows; c++) {     // the one hit: its lane marks it, lane 0 of the wave records the step
+                        const int i = c * 64 + lane;
+                        const bool hit = i < eq_rows && !((used >> c) & 1ull) && ne(E[i * cols + j], zero<S>());
+                        const unsigned long long mask = __ballot(hit);
+                        if (hit) used |= 1ull << c;
+                        if (mask && lane == 0) { steps[2 * ns] = j; steps[2 * ns + 1] = c * 64 + __ffsll((long long)mask) - 1; }
+                    }
+                    ns++;
+                }
+            for (int c = 0; c * 64 < eq_rows; c++) {
+                const int i = c * 64 + lane;
+                const bool keep = i < eq_rows && !((used >> c) & 1ull);
+                const unsigned long long mask = __ballot(keep);
+                if (keep) rest[nrest + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+                nrest += __popcll(mask);
+            }
+            if (tid == 0) { hdr[2] = ns; hdr[3] = nrest; }
+        }
+        __syncthreads();
+        const int ns = hdr[2], nrest = hdr[3], rows = leq_rows + 2 * nrest;
+        // ---- fold (lpsol.h:1224-1250): a step changes inequality q from its own cells and the equality's alone
+        for (int s = 0; s < ns; s++) {
+            const int j = steps[2 * s], at = steps[2 * s + 1];
+            const S * e = E + at * cols;
+            for (int q = tid; q < leq_rows; q += nt) {
+                const S c = L[q * cols + j];
+                coef[q] = c;
+                if (eq(c, zero<S>())) continue;
+                if (q >= cols) hdr[1] = 1;                       // lpsol.h:1232 reads past the equality's row: undefined
+                else inv[q] = div(one<S>(), e[q]);
+            }
+            __syncthreads();
+            for (int t = tid; t < lcells; t += nt) {
+                const int q = t / cols, k = t - q * cols;
+                const S c = coef[q];
+                if (eq(c, zero<S>()) || q >= cols) continue;
+                const S iv = inv[q];
+                const int md1 = ne(e[q], one<S>()) ? scale_mode(iv) : (int)SCALE_KEEP, md2 = scale_mode(c);
+                S x = scaled(scaled(e[k], iv, md1), c, md2);
+                const S cur = k == j ? zero<S>() : L[t];
+                if (k >= n0) x = neg(x);
+                L[t] = add(x, cur);
+            }
+            __syncthreads();
+        }
+        if (hdr[1]) {                                            // this LP alone; it never meets the pivot loop
+            if (tid == 0) { out_status[lp] = XPG_ERR_REF_UNDEFINED; out_v[lp] = zero<S>(); }
+            continue;
+        }
+        // ---- form: N and the normalised objective (lpsol.h:1254-1268, :1365-1392), whole rows by consecutive lanes
+        for (int t = tid; t < rows * (n + 1); t += nt) {
+            const int i = t / (n + 1), c = t - i * (n + 1);
+            const bool from_eq = i >= leq_rows;
+            const S * src = from_eq ? E + rest[(i - leq_rows) >> 1] * cols : L + i * cols;
+            const int sc = c < n0 ? c : (c == n ? n0 : fv[c - n0]);
+            S x = src[sc];
+            if (from_eq && ((i - leq_rows) & 1) == 0) x = scaled(x, m1, mode1);
+            if (c >= n0 && c < n) x = scaled(x, m1, mode1);
+            N[t] = x;
+        }
+        for (int c = tid; c <= n; c += nt) {
+            S x = tg[c < n0 ? c : (c == n ? n0 : fv[c - n0])];
+            if (c >= n0 && c < n) x = scaled(x, m1, mode1);
+            obj[c] = x;
+        }
+        __syncthreads();                                         // L / E are read, N / obj written: the LDS block is the solver's
+        // ---- solve: the arrays and the code of a single call's launch (k_batch with nb = 1 on this normal form)
+        Small<S> P;
+        sm_carve(P, lds, is_max ? rows : n, is_max ? n : rows);
+        Source<S> src;
+        src.leq = N; src.tgtf = obj; src.m = rows; src.cols = n + 1; src.is_max = is_max;
+        const int status = sm_solve_lp<S>(P, src, max_iter, /*raw_sol=*/1, y, vout);
+        if (status != 0) {
+            if (tid == 0) { out_status[lp] = status; out_v[lp] = zero<S>(); }
+            continue;
+        }
+        // ---- finish (lpsol.h:1851-1899, finish_host): y[j] - y[twin], constant slot 1, tgtf . sol in column order, reduce
+        for (int k = tid; k < nfree; k += nt) y[fv[k]] = sub(y[fv[k]], y[n0 + k]);
+        __syncthreads();
+        S * const prod = obj;                                    // (the normalised objective has done its work)
+        for (int j = tid; j < cols; j += nt) {
+            S x = j < n0 ? y[j] : one<S>();
+            prod[j] = mul(x, tg[j]);
+            reduce(x);
+            out_sol[(size_t)lp * cols + j] = x;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            S v = zero<S>();
+            for (int j = 0; j < cols; j++) v = add(v, prod[j]);
+            reduce(v);
+            out_v[lp] = v;
+            out_status[lp] = 0;
+        }
+    }
+}
+
+// Enqueue only; every pointer is a device pointer. nfree >= 0: the caller has read vc (the host-array form); -1: vc is known
+// to the device alone -- LDS and slots are sized for the worst vc can hold (every variable free), the kernel sizes each LP
+// by what it finds.
+template <class S>
+int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S * vc, const S * eqs, int eq_rows, const S * leq,
+                     int leq_rows, int cols, unsigned max_iter, int nfree, int32_t * out_status, S * out_v, S * out_sol)
+{
+    if (!ctx || nb < 0 || !tgtf || !vc || cols < 2 || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) ||
+        (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq) || !out_status || !out_v || !out_sol)
+        return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    const int nfree_cap = nfree >= 0 ? nfree : cols - 1;
+    const SixVcPlan least = six_vc_plan<S>(true, nfree >= 0 ? nfree : 0, leq_rows, eq_rows, cols, is_max);
+    if (!least.device) return XPG_ERR_UNSUPPORTED;               // (no vc makes this shape fit)
+    const SixVcPlan most = six_vc_plan<S>(true, nfree_cap, leq_rows, eq_rows, cols, is_max);
+    const size_t lds = most.lds < (size_t)SIX_VC_LDS_MAX ? most.lds : (size_t)SIX_VC_LDS_MAX;
+    const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree_cap);
+    const int R = is_max ? least.rows_max : least.n, V = is_max ? least.n : least.rows_max;
+    const int cells = R * (V + R + 2);
+    const int threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);     // batch_geometry's rule
+    const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
+    long long grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
+    if (grid > nb) grid = nb;
+    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / (sl.cells * 8));
+    if (grid > by_scratch) grid = by_scratch > 0 ? by_scratch : 1;
+    static const int grid_cap = [] { const char * e = xpg_hook("XPG_SIX_VC_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
+    if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
+    const size_t need = (size_t)grid * sl.cells * 8;
+    if (need > ctx->six_vc_cap) {
+        if (ctx->six_vc_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = nullptr; ctx->six_vc_cap = 0; }
+        const size_t cap = need + need / 2 < SIX_VC_SCRATCH_MAX ? need + need / 2 : need;
+        if (hipMalloc(&ctx->six_vc_buf, cap) != hipSuccess) { ctx->six_vc_buf = nullptr; (void)hipGetLastError(); ctx->err = "hipMalloc(six_batch_vc scratch)"; return XPG_ERR_ALLOC; }
+        ctx->six_vc_cap = cap;
+    }
+    XPG_HIP(ctx, lds_limit((const void *)k_six_batch_vc<S>, ctx->device, lds));
+    hipLaunchKernelGGL((k_six_batch_vc<S>), dim3((unsigned)grid), dim3(threads), lds, ctx->stream, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows,
+                       cols, is_max ? 1 : 0, max_iter, (unsigned)lds, (unsigned long long *)ctx->six_vc_buf, (unsigned long long)sl.cells,
+                       out_status, out_v, out_sol);
+    XPG_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// Host arrays; synchronises once. The route rule decides: the device for the whole batch, or six_solve per problem (a
+// general vc, a normal form beyond 64 KB), so the call is defined wherever SIX::maxm / minm is. Same results either way.
+template <class S>
+int six_batch_vc_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S * tgtf, const S * vc, const S * eqs, int eq_rows, const S * leq,
+                      int leq_rows, int cols, unsigned max_iter, int32_t * out_status, S * out_v, S * out_sol)
+{
+    if (!ctx || nb < 0 || !tgtf || !vc || cols < 2 || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) ||
+        (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq) || !out_status || !out_v || !out_sol)
+        return XPG_ERR_SHAPE;
+    SixVcRoute & rt = six_vc_route();
+    rt = SixVcRoute{0, 0, 0};
+    if (nb == 0) return 0;
+    std::vector<int> fvar;
+    const bool pattern = vc_sign_pattern(vc, cols - 1, cols, fvar);
+    const SixVcPlan plan = six_vc_plan<S>(pattern, (int)fvar.size(), leq_rows, eq_rows, cols, is_max);
+    if (!plan.device) {
+        for (int b = 0; b < nb; b++) {
+            out_v[b] = zero<S>();
+            const int st = six_solve<S>(ctx, kind, is_max, tgtf + (size_t)b * cols, vc, cols - 1, eq_rows > 0 ? eqs + (size_t)b * eq_rows * cols : (const S *)0,
+                                        eq_rows, leq_rows > 0 ? leq + (size_t)b * leq_rows * cols : (const S *)0, leq_rows, cols, max_iter,
+                                        out_v + b, out_sol + (size_t)b * cols);
+            if (st < 0 && st != XPG_ERR_REF_UNDEFINED) return st;
+            out_status[b] = st;
+            if (st != 0) out_v[b] = zero<S>();
+            rt.fallback++;
+        }
+        return 0;
+    }
+    const size_t bt = (size_t)nb * cols * 8, bv = (size_t)(cols - 1) * cols * 8, be = (size_t)nb * eq_rows * cols * 8,
+                 bl = (size_t)nb * leq_rows * cols * 8;
+    DevBuf dt, dvc, de, dl, dst, dv, ds;
+    XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dvc.alloc(ctx, bv)); XPG_TRY(de.alloc(ctx, be)); XPG_TRY(dl.alloc(ctx, bl));
+    XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(ds.alloc(ctx, bt));
+    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(dvc.p, vc, bv, hipMemcpyHostToDevice, ctx->stream));
+    if (eq_rows > 0) XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
+    if (leq_rows > 0) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = six_batch_vc_dev<S>(ctx, is_max, nb, (const S *)dt.p, (const S *)dvc.p, (const S *)de.p, eq_rows, (const S *)dl.p, leq_rows, cols,
+                                       max_iter, plan.nfree, (int32_t *)dst.p, (S *)dv.p, (S *)ds.p);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    std::vector<S> sol((size_t)nb * cols);
+    XPG_TRY(hipMemcpyAsync(out_status, dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(out_v, dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(sol.data(), ds.p, bt, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < nb; b++)                                 // (out_sol is written on success only, include/xpoly_amd.h)
+        if (out_status[b] == 0) memcpy(out_sol + (size_t)b * cols, sol.data() + (size_t)b * cols, (size_t)cols * 8);
+    rt.device = nb; rt.free_vars = plan.nfree;
+    return 0;
+}
+
+} // namespace xpg

@@ -37,6 +37,9 @@
 #include "six_host.hip.h"
 #include "batch_kernels.hip.h"
 #endif
+#if XPG_IN(1)
+#include "six_batch_vc.hip.h"
+#endif
 #if XPG_IN(3)
 #include "lineq_host.hip.h"
 #endif
@@ -133,6 +136,7 @@ void xpg_destroy(xpg_ctx * ctx)
     if (ctx->hpack) (void)hipHostFree(ctx->hpack);
     if (ctx->hred) (void)hipHostFree(ctx->hred);
     if (ctx->slice_buf) (void)hipFree(ctx->slice_buf);
+    if (ctx->six_vc_buf) (void)hipFree(ctx->six_vc_buf);
     for (xpg_ctx * l : ctx->lanes) xpg_destroy(l);
     ctx->lanes.clear();
     for (auto & b : ctx->dev_cache) (void)hipFree(b.first);
@@ -605,6 +609,7 @@ int xpg_trim(xpg_ctx * ctx)
     ctx->dev_cache.clear(); ctx->dev_cache_bytes = 0;
     if (ctx->hpack) { (void)hipHostFree(ctx->hpack); ctx->hpack = 0; ctx->hpack_cap = 0; }
     if (ctx->hred) { (void)hipHostFree(ctx->hred); ctx->hred = 0; ctx->hred_cap = 0; }
+    if (ctx->six_vc_buf) { (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = 0; ctx->six_vc_cap = 0; }
     return 0;
 }
 
@@ -756,6 +761,77 @@ int xpg_six_batch_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgt
     XPG_BIND(ctx);
     return batch_host<R32>(ctx, is_max, nb, (const R32 *)tgtf, (const R32 *)leq, m, cols, max_iter,
                            out_status, (R32 *)out_v, (R32 *)out_sol);
+}
+
+// ---- the same for problems with equalities and free variables: SIX::normalize and calcFinalSolution on the device ----
+int xpg_six_batch_vc_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc, const double * eq, int eq_rows,
+                         const double * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status, double * out_v,
+                         double * out_sol)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_host<F64>(ctx, 0, is_max != 0, nb, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows, (const F64 *)leq,
+                                  leq_rows, cols, max_iter, out_status, (F64 *)out_v, (F64 *)out_sol);
+}
+int xpg_six_batch_vc_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc, const xpg_rat32 * eq,
+                           int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status,
+                           xpg_rat32 * out_v, xpg_rat32 * out_sol)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_host<R32>(ctx, 1, is_max != 0, nb, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows, (const R32 *)leq,
+                                  leq_rows, cols, max_iter, out_status, (R32 *)out_v, (R32 *)out_sol);
+}
+int xpg_six_batch_vc_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc, const double * eq, int eq_rows,
+                             const double * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status, double * out_v,
+                             double * out_sol)
+{
+    XPG_BIND(ctx);
+    const int rc = six_batch_vc_dev<F64>(ctx, is_max != 0, nb, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows, (const F64 *)leq,
+                                         leq_rows, cols, max_iter, -1, out_status, (F64 *)out_v, (F64 *)out_sol);
+    six_vc_route() = SixVcRoute{rc == 0 ? nb : 0, 0, -1};
+    return rc;
+}
+int xpg_six_batch_vc_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc, const xpg_rat32 * eq,
+                               int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status,
+                               xpg_rat32 * out_v, xpg_rat32 * out_sol)
+{
+    XPG_BIND(ctx);
+    const int rc = six_batch_vc_dev<R32>(ctx, is_max != 0, nb, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows, (const R32 *)leq,
+                                         leq_rows, cols, max_iter, -1, out_status, (R32 *)out_v, (R32 *)out_sol);
+    six_vc_route() = SixVcRoute{rc == 0 ? nb : 0, 0, -1};
+    return rc;
+}
+// which route the LPs of the calling thread's last xpg_six_batch_vc_* call took (six_batch_vc.hip.h SixVcRoute)
+int xpg_six_batch_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const SixVcRoute & r = six_vc_route();
+    const long long f[3] = { r.device, r.fallback, r.free_vars };
+    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test view: the route rule of xpg_six_batch_vc_* and the sizes it decides by
+int xpg_test_six_batch_vc_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max, long long * out, int n)
+{
+    if (!vc || !out || n < 0 || cols < 2 || vc_rows != cols - 1 || leq_rows < 0 || eq_rows < 0 || (leq_rows == 0 && eq_rows == 0) ||
+        (kind != 0 && kind != 1))
+        return XPG_ERR_SHAPE;
+    std::vector<int> fv;
+    SixVcPlan p;
+    int nfree = 0;
+    if (kind == 0) {
+        const F64 * c = (const F64 *)vc;
+        const bool pat = vc_sign_pattern(c, vc_rows, cols, fv);
+        for (int j = 0; j < cols - 1; j++) { bool nz = false; for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<F64>()); nfree += nz ? 0 : 1; }
+        p = six_vc_plan<F64>(pat, nfree, leq_rows, eq_rows, cols, is_max != 0);
+    } else {
+        const R32 * c = (const R32 *)vc;
+        const bool pat = vc_sign_pattern(c, vc_rows, cols, fv);
+        for (int j = 0; j < cols - 1; j++) { bool nz = false; for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<R32>()); nfree += nz ? 0 : 1; }
+        p = six_vc_plan<R32>(pat, nfree, leq_rows, eq_rows, cols, is_max != 0);
+    }
+    const long long f[5] = { p.device, p.nfree, p.rows_max, p.n, (long long)p.lds };
+    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
+    return 0;
 }
 
 } // extern "C"

@@ -155,6 +155,21 @@ class Context:
                       C.c_void_p(v_ptr), C.c_void_p(sol_ptr),
                       C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_dev")
 
+    def six_batch_vc_dev(self, kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr, v_ptr,
+                         sol_ptr, max_iter=0xFFFFFFFF):
+        """xpg_six_batch_vc_*_dev: device pointers for every array (vc included), enqueue only -- results after sync().
+        eq_ptr / leq_ptr may be None with 0 rows (not both). Nothing falls back here: a vc that is no sign pattern, or a shape
+        beyond 64 KB of LDS, ends every LP with status -4."""
+        fn = lib().xpg_six_batch_vc_f64_dev if kind == F64 else lib().xpg_six_batch_vc_rat32_dev
+        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(vc_ptr),
+                      C.c_void_p(eq_ptr) if eq_ptr else None, C.c_int(eq_rows), C.c_void_p(leq_ptr) if leq_ptr else None,
+                      C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
+                      C.c_void_p(sol_ptr)), "xpg_six_batch_vc_dev")
+
+    def trim(self):
+        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc go back to the runtime."""
+        self.check(lib().xpg_trim(self._h), "xpg_trim")
+
 
 def _check_multi(rc, what):
     if rc < 0:
@@ -431,6 +446,41 @@ def mip_last_route():
     out = (C.c_longlong * 3)()
     lib().xpg_mip_last_route(out, C.c_int(3))
     return dict(device_trees=int(out[0]), host_trees=int(out[1]), free_vars=int(out[2]))
+
+
+def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF):
+    """SIX::maxm / minm for nb problems of one shape WITH equalities and free variables in one call (xpg_six_batch_vc_*):
+    tgtf [nb, cols(,2)], vc [cols - 1, cols(,2)] shared by the batch, leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)]
+    or None (not both None). A vc that is a sign pattern (diagonal -1 = x >= 0, 0 = free, nothing else) and a shape within
+    64 KB of LDS: SIX::normalize, the solve and calcFinalSolution run on the device for the whole batch; anything else is
+    solved per problem as SIX.maxm / minm would. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); status -7 marks the
+    problems the reference is undefined on; sol rows are written on status 0 only."""
+    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
+    leq = None if leq is None else as_kind(leq, kind, 3)
+    eq = None if eq is None else as_kind(eq, kind, 3)
+    nb, cols = tgtf.shape[0], tgtf.shape[1]
+    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
+        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
+    for a in (leq, eq):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq is None else leq.shape[1]
+    eq_rows = 0 if eq is None else eq.shape[1]
+    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    fn = lib().xpg_six_batch_vc_f64 if kind == F64 else lib().xpg_six_batch_vc_rat32
+    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
+                 vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
+              "xpg_six_batch_vc")
+    return st, v, sol
+
+
+def six_batch_last_route():
+    """Which route the LPs of the calling thread's last six_batch_vc call took (xpg_six_batch_last_route): device = LPs
+    reshaped and solved on the device, fallback = LPs solved one by one, free = free variables split per LP on the device
+    route (-1 after a _dev call: only the device has read vc)."""
+    out = (C.c_longlong * 3)()
+    lib().xpg_six_batch_last_route(out, C.c_int(3))
+    return dict(device=int(out[0]), fallback=int(out[1]), free=int(out[2]))
 
 
 def dep_is_empty_batch(ctx, mats, rhs_idx=None, vc=None):
