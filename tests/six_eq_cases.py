@@ -25,6 +25,22 @@ PER_SHAPE = 256
 # columns, where convertEq2Ineq's leading value (lpsol.h:1232, read at the inequality's row index) leaves the row for some LPs;
 # and two sizes at which the batch runs 128 and 256 threads per LP (the shapes above all run 64)
 EXTRA_SHAPES = ((0, 2, 4, 1), (9, 2, 4, 0), (20, 2, 20, 1), (30, 2, 30, 2))
+# 66 equalities, so that the choice of the substitutions (wave-wide ballots, 64 equalities a time) meets a second chunk:
+# column 0 is nonzero in equality 65 alone and column 1 in equality 64 alone -- both are substituted, from behind the first
+# 64 --, the other 64 stay as pairs. 64 problems, minm only: maximising, the largest normal form (135 rows) needs 163 552 B
+# of LDS and takes the per-problem fallback; minimising it needs 14 320 B (fp64; 14 256 B Rational) and runs on the device.
+# Rational: the solutions are compared (oracle_answers holds at least 8 of the 64 to status 0); fp64 ends almost all of
+# them 2 and checks statuses and the normal form's path only.
+WIDE_EQ = (3, 66, 4, 1)
+
+
+def cases_of(shape):
+    return 64 if shape == WIDE_EQ else PER_SHAPE
+
+
+def directions(shape):
+    """is_max of the batch calls a shape is tested with."""
+    return (False,) if shape == WIDE_EQ else (True, False)
 
 
 def one_problem(rng, m, me, nv, nfree):
@@ -42,18 +58,33 @@ def one_problem(rng, m, me, nv, nfree):
     leq = np.concatenate([A, b[:, None]], axis=1).astype(np.int32)
     eq = np.concatenate([Ae, be[:, None]], axis=1).astype(np.int32)
     tgtf = np.concatenate([c, [0]]).astype(np.int32)
-    return tgtf, eq, leq
+    return tgtf, eq, leq, xs
+
+
+def wide_eq_problem(rng):
+    """one_problem of WIDE_EQ with columns 0 and 1 made private to equalities 65 and 64; the constants are the equalities at
+    xs again, so the 66 of them stay consistent."""
+    m, me, nv, nfree = WIDE_EQ
+    tgtf, eq, leq, xs = one_problem(rng, m, me, nv, nfree)
+    for col, row in ((0, 65), (1, 64)):
+        keep = eq[row, col] if eq[row, col] != 0 else 1
+        eq[:, col] = 0
+        eq[row, col] = keep
+    eq[:, nv] = eq[:, :nv] @ xs
+    return tgtf, eq, leq, xs
 
 
 _problem_cache = {}
 
 
-def shape_arrays(shape, kind, count=PER_SHAPE):
+def shape_arrays(shape, kind, count=None):
     """(tgtf [count, cols(,2)], vc [nv, cols(,2)], eq [count, eq_rows, cols(,2)] or None, leq [count, leq_rows, cols(,2)] or None)."""
     m, me, nv, nfree = shape
+    count = cases_of(shape) if count is None else count
     if shape not in _problem_cache:
         rng = np.random.default_rng(6100 + 10 * nv + nfree)
-        probs = [one_problem(rng, m, me, nv, nfree) for _ in range(PER_SHAPE)]
+        make = (lambda: wide_eq_problem(rng)) if shape == WIDE_EQ else (lambda: one_problem(rng, m, me, nv, nfree))
+        probs = [make() for _ in range(cases_of(shape))]
         tg = gen.to_rat(np.stack([p[0] for p in probs]))
         eq = gen.to_rat(np.stack([p[1] for p in probs])) if me else None
         leq = gen.to_rat(np.stack([p[2] for p in probs])) if m else None
@@ -72,8 +103,9 @@ def shape_arrays(shape, kind, count=PER_SHAPE):
 _oracle_cache = {}
 
 
-def oracle_answers(port, shape, kind, is_max, count=PER_SHAPE):
+def oracle_answers(port, shape, kind, is_max, count=None):
     """[(status, v, sol)] of the first `count` problems of the shape from the CPU restatement, computed once."""
+    count = cases_of(shape) if count is None else count
     key = (shape, kind, is_max)
     have = _oracle_cache.setdefault(key, [])
     if len(have) < count:
@@ -86,6 +118,8 @@ def oracle_answers(port, shape, kind, is_max, count=PER_SHAPE):
             with non_strict(port):
                 for i in range(len(have), count):
                     have.append(solve(i))
+        if shape == WIDE_EQ and kind == RAT and count == cases_of(shape):
+            assert sum(a[0] == 0 for a in have) >= 8, [a[0] for a in have]     # a changed seed must not empty the comparison
     return have[:count]
 
 

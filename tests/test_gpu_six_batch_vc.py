@@ -40,18 +40,18 @@ def _singles(ctx, kind, is_max, tg, vc, eq, leq, max_iter=0xFFFFFFFF):
 
 @pytest.mark.parametrize("kind", [RAT, F64])
 def test_batches_match_the_oracle(ctx, port, kind):
-    """Every shape x direction is one batch call of 256 LPs. A problem is skipped only where the oracle itself returns -7,
-    at most 4 of the 512 per shape (the generator's measured maximum is 1)."""
+    """Every shape x direction is one batch call of 256 LPs (64 for the shape with 66 equalities, minm only). A problem is
+    skipped only where the oracle itself returns -7, at most 4 of the 512 per shape (the generator's measured maximum is 1)."""
     from xpoly_amd.six import six_batch_last_route
     seen, negative = set(), 0
-    for shape in sc.SHAPES:
-        skipped = 0
-        for is_max in (True, False):
+    for shape in sc.SHAPES + (sc.WIDE_EQ,):
+        skipped, nb = 0, sc.cases_of(shape)
+        for is_max in sc.directions(shape):
             want = sc.oracle_answers(port, shape, kind, is_max)
-            st, v, sol = _batch(ctx, shape, kind, is_max)
+            st, v, sol = _batch(ctx, shape, kind, is_max, nb)
             r = six_batch_last_route()
-            assert r == dict(device=sc.PER_SHAPE, fallback=0, free=shape[3]), (shape, is_max, r)
-            for i in range(sc.PER_SHAPE):
+            assert r == dict(device=nb, fallback=0, free=shape[3]), (shape, is_max, r)
+            for i in range(nb):
                 if want[i][0] == -7:
                     skipped += 1
                     continue
@@ -60,7 +60,7 @@ def test_batches_match_the_oracle(ctx, port, kind):
                 if want[i][0] == 0 and shape[3] > 0:
                     s = np.asarray(want[i][2])
                     negative += bool(((s[..., 0] if kind == RAT else s)[:-1] < 0).any())
-        print("shape %s kind %d: skipped %d of 512" % (shape, kind, skipped))
+        print("shape %s kind %d: skipped %d of %d" % (shape, kind, skipped, nb * len(sc.directions(shape))))
         assert skipped <= 4, (shape, kind, skipped)
     assert seen == {0, 1, 2, 3}, seen
     assert negative >= 40, negative                              # the free variables do go below zero
@@ -71,13 +71,14 @@ def test_batch_equals_single_calls_bit_for_bit(ctx, kind):
     """The first 64 problems of every shape, and of four more: no inequalities at all (leq = None); more inequality rows
     than columns, where the reference's leading-value index (lpsol.h:1232) leaves the row for some LPs -- those alone end -7,
     in the batch as in their single calls; and two sizes at which the batch runs 128 and 256 threads per LP (a single call
-    picks its threads by the rows its own normal form has). Statuses of -7 are compared like any other."""
+    picks its threads by the rows its own normal form has); and the shape with 66 equalities, minm only. Statuses of -7 are
+    compared like any other."""
     count = 64
     statuses = {}
-    for shape in sc.SHAPES + sc.EXTRA_SHAPES:
+    for shape in sc.SHAPES + sc.EXTRA_SHAPES + (sc.WIDE_EQ,):
         tg, vc, eq, leq = sc.shape_arrays(shape, kind, count)
         assert (leq is None) == (shape[0] == 0)
-        for is_max in (True, False):
+        for is_max in sc.directions(shape):
             st, v, sol = _batch(ctx, shape, kind, is_max, count)
             one = _singles(ctx, kind, is_max, tg, vc, eq, leq)
             for i in range(count):

@@ -24,6 +24,8 @@ def test_sign_patterns_take_the_device_with_their_free_count_and_sizes(kind):
             assert rc == 0
             assert out == [1, nfree, leq_rows + 2 * eq_rows, nv + nfree, sc.plan_bytes(leq_rows, eq_rows, nv, nfree, is_max, kind)], \
                 (leq_rows, eq_rows, nv, nfree, is_max, out)
+    # 66 equalities (sc.WIDE_EQ): the largest normal form leaves the device maximising, fits it minimising (the dual)
+    assert [_plan(gen.vc_nonneg(4, False, (0,)), kind, 3, 66, is_max)[1][0] for is_max in (True, False)] == [0, 1]
     # the free variables need not come first
     rc, out = _plan(gen.vc_nonneg(6, False, (1, 4)), kind, 3, 2, True)
     assert rc == 0 and out[:4] == [1, 2, 7, 8]

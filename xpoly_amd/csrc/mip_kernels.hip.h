@@ -1,7 +1,7 @@
 // MIP<Mat,T>::RecusivePart (src/com/lpsol.h:2427-2612) for a batch of independent problems, one WORKGROUP per
 // problem and the whole depth-first tree walk on the device: the node's problem is rebuilt from the root and the
-// branch rows of the path, normalised as SIX::normalize would (for 0-1 problems that is convertEq2Ineq's
-// substitution of the branch equalities, lpsol.h:1197-1278, quirks included), solved in LDS by the same code the
+// branch rows of the path, normalised as SIX::normalize would (normalize_dev.hip.h; for 0-1 problems that is
+// convertEq2Ineq's substitution of the branch equalities, lpsol.h:1197-1278, quirks included), solved in LDS by the same code the
 // batch kernel runs (sm_solve_lp), and the answer is fed to the reference's recursion written as a stack machine
 // -- the very logic of MipTask::on_lp (mip_host.hip.h), statement for statement, run by thread 0 on state that
 // lives in a per-problem workspace in HBM.
@@ -15,10 +15,11 @@
 // PolyTran::FeaSchedule, src/eng/poly.cpp:5118-5130, pass) or free (diagonal 0: what Lineq::initVarConstraint,
 // src/com/linsys.cpp:803-819, makes for a variable without a sign) --, inequalities and -- round 3 -- equalities at the
 // root, binary or integer branching, with or without a rational_indicator (lpsol.h:2369-2393). A free variable is split
-// v = v' - v'' in front of every node LP as SIX::normalize does (mip_split_free). Any other vc (bounds other than
+// v = v' - v'' in front of every node LP as SIX::normalize does (normalize_dev.hip.h). Any other vc (bounds other than
 // x >= 0, rows that couple variables) keeps the host controller.
 #pragma once
 #include "batch_kernels.hip.h"
+#include "normalize_dev.hip.h"
 
 namespace xpg {
 
@@ -100,37 +101,38 @@ __device__ __forceinline__ bool sp_cas(int * p, int expect, int want)
 __device__ __forceinline__ bool mip_int_cast_ok(F64) { return true; }
 __device__ __forceinline__ bool mip_int_cast_ok(R32 a) { return a.den != 0; }
 
-// The node's problem (MipTask::push_branch + normalize_host): root inequalities, then -- integer branching -- one
-// bound row per ancestor, or -- 0-1 branching -- the ancestors' equalities x_col = b substituted into the
-// inequalities column by column (fold_eq of six_host.hip.h; every branch equality has one variable, so each is
-// "the only nonzero of its column" and none is left to become a pair of inequalities). All threads; returns the
-// row count, or a negative status where the reference's behaviour is undefined.
-template <class S> __device__ int mip_build_node_eq(const MipWs<S> & w, const S * root_eq, int eq_rows, int cols, bool is_bin,
-                                                     int top, int rows, int * sh_flag);
-template <class S> __device__ int mip_build_node(const MipWs<S> & w, const S * root_leq, int leq_rows, const S * root_eq, int eq_rows,
-                                                  int cols, bool is_bin, int top, int * sh_flag)
-{   // (a helper builds the ceiling child of frame f from a COPY of the frames with frame f's stage set to 2, top = f + 1)
+// The equalities of a node as nf_convert_eq takes them (normalize_dev.hip.h): the root's rows, then -- 0-1 branching --
+// one x_col = b row per ancestor: 1 in its column, b in the constant column (lpsol.h:2506-2512, :2548-2553).
+// MIP_EQ_MAX bounds the list (root rows + depth: mip_device_fits).
+enum { MIP_EQ_MAX = 256 };
+template <class S> struct MipNodeEq {
+    const S * root_eq; int eq_rows, cols; const int * frame;
+    __device__ __forceinline__ S operator()(int i, int k) const
+    {
+        if (i < eq_rows) return root_eq[(size_t)i * cols + k];
+        const int * fr = frame + (i - eq_rows) * 6;
+        if (k == fr[MF_COL]) return one<S>();
+        if (k == cols - 1) return S::from_int(fr[MF_STAGE] == 2 ? fr[MF_HI] : fr[MF_LO]);
+        return zero<S>();
+    }
+};
+
+// The node's problem (MipTask::push_branch + normalize_host), by all threads: the root's inequalities, under integer
+// branching one bound row per ancestor behind them, then SIX::normalize as normalize_dev.hip.h states it over the node's
+// equalities. Without equalities at the root a 0-1 node leaves none over: forks[] lets a column branch once, so every
+// branch equality is the one unused hit of its column (and the workspace has no rows for pairs then, mip_rmax). With free
+// variables the node is widened into w.N and the objective into w.wobj; else it stays in w.L. Returns the row count, or a
+// negative status where the reference's behaviour is undefined.
+// (a helper builds the ceiling child of frame f from a COPY of the frames with frame f's stage set to 2, top = f + 1)
+template <class S> __device__ int mip_build_node(const MipWs<S> & w, const S * tgtf, const S * root_leq, int leq_rows, const S * root_eq,
+                                                  int eq_rows, int cols, bool is_bin, int top, const int * free_var, int extra)
+{
+    __shared__ short sh_left[MIP_EQ_MAX];
+    __shared__ int sh_nf[4];
     const int rhs0 = cols - 1;
     for (int t = threadIdx.x; t < leq_rows * cols; t += blockDim.x) w.L[t] = root_leq[t];
-    if (threadIdx.x == 0) *sh_flag = 0;
     int rows = leq_rows;
-    if (eq_rows > 0) {                                       // equalities at the root: the general convertEq2Ineq
-        if (!is_bin)
-            for (int f = 0; f < top; f++) {
-                const int * fr = w.frame + f * 6;
-                const bool ceiling = fr[MF_STAGE] == 2;
-                for (int j = threadIdx.x; j < cols; j += blockDim.x) {
-                    S val = zero<S>();
-                    if (j == fr[MF_COL]) val = ceiling ? minus_one<S>() : one<S>();
-                    if (j == rhs0) val = S::from_int(ceiling ? -fr[MF_HI] : fr[MF_LO]);
-                    w.L[(size_t)rows * cols + j] = val;
-                }
-                rows++;
-            }
-        __syncthreads();
-        return mip_build_node_eq<S>(w, root_eq, eq_rows, cols, is_bin, top, rows, sh_flag);
-    }
-    if (!is_bin) {
+    if (!is_bin)
         for (int f = 0; f < top; f++) {                      // frame f's child row (lpsol.h:2514-2520, :2555-2559)
             const int * fr = w.frame + f * 6;
             const bool ceiling = fr[MF_STAGE] == 2;
@@ -142,148 +144,18 @@ template <class S> __device__ int mip_build_node(const MipWs<S> & w, const S * r
             }
             rows++;
         }
-        __syncthreads();
-        return rows;
-    }
     __syncthreads();
-    for (int j = 0; j < rhs0; j++) {                         // convertEq2Ineq, lpsol.h:1218-1262
-        int at = -1;
-        for (int f = 0; f < top; f++) if (w.frame[f * 6 + MF_COL] == j) { at = f; break; }
-        if (at < 0) continue;
-        const int * fr = w.frame + at * 6;
-        const S b = S::from_int(fr[MF_STAGE] == 2 ? fr[MF_HI] : fr[MF_LO]);   // lpsol.h:2506-2512, :2548-2553
-        for (int q = threadIdx.x; q < rows; q += blockDim.x) {
-            S * Lq = w.L + (size_t)q * cols;
-            const S coef = Lq[j];
-            if (eq(coef, zero<S>())) continue;
-            if (q >= cols) { *sh_flag = 1; continue; }       // the reference reads the equality at the ROW's index
-            // the equality row: 1 in column j, b in the constant column
-            const S lead = q == j ? one<S>() : (q == rhs0 ? b : zero<S>());
-            const bool rescale = ne(lead, one<S>());
-            const S x1 = rescale ? q_div(false, one<S>(), lead) : one<S>();
-            const int m1 = rescale ? scale_mode(x1) : SCALE_KEEP, m2 = scale_mode(coef);
-            Lq[j] = zero<S>();
-            for (int k = 0; k < cols; k++) {
-                S t = k == j ? one<S>() : (k == rhs0 ? b : zero<S>());
-                t = q_scaled(false, t, x1, m1);
-                t = q_scaled(false, t, coef, m2);
-                if (k >= rhs0) t = neg(t);
-                Lq[k] = q_add(false, t, Lq[k]);
-            }
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    return *sh_flag ? XPG_ERR_REF_UNDEFINED : rows;
-}
-
-// The same with equalities at the root (MipTask::push_branch + fold_eq of six_host.hip.h = SIX::convertEq2Ineq,
-// lpsol.h:1197-1278, on the node's equality list: the root's rows, then -- 0-1 branching -- one x_col = b row per
-// ancestor). Columns are visited in order; a column in which exactly ONE not-yet-used equality has a nonzero is
-// substituted into every inequality that mentions it (the reference reads the equality's leading entry at the
-// INEQUALITY's row index, lpsol.h:1232: reproduced, refused once it would leave the row), and the equalities left
-// over become pairs of opposite inequalities below the others. Wave 0 finds the next (column, equality) with
-// ballots over the equality rows; the substitution runs over the inequality rows in parallel. MIP_EQ_MAX bounds the
-// equality list (root rows + depth).
-enum { MIP_EQ_MAX = 256 };
-template <class S> __device__ __forceinline__ S mip_eq_cell(const S * root_eq, int eq_rows, int cols, const int * frame, int i, int k)
-{
-    if (i < eq_rows) return root_eq[(size_t)i * cols + k];
-    const int * fr = frame + (i - eq_rows) * 6;              // a branch equality: 1 in its column, b in the constant column
-    if (k == fr[MF_COL]) return one<S>();
-    if (k == cols - 1) return S::from_int(fr[MF_STAGE] == 2 ? fr[MF_HI] : fr[MF_LO]);   // lpsol.h:2506-2512, :2548-2553
-    return zero<S>();
-}
-template <class S> __device__ int mip_build_node_eq(const MipWs<S> & w, const S * root_eq, int eq_rows, int cols, bool is_bin,
-                                                     int top, int rows, int * sh_flag)
-{
-    __shared__ unsigned char sh_used[MIP_EQ_MAX];
-    __shared__ short sh_left[MIP_EQ_MAX];
-    __shared__ int sh_pick[3];                               // column, equality, equalities left over
-    const int rhs0 = cols - 1, lane = threadIdx.x & 63;
+    const MipNodeEq<S> eqs = {root_eq, eq_rows, cols, w.frame};
     const int ne_rows = eq_rows + (is_bin ? top : 0);
-    for (int i = threadIdx.x; i < ne_rows; i += blockDim.x) sh_used[i] = 0;
-    __syncthreads();
-    int from = 0;
-    while (rows > 0) {                                       // (no inequality at all: nothing to substitute into)
-        if (threadIdx.x < 64) {
-            int fj = -1, fat = -1;
-            for (int j = from; j < rhs0 && fj < 0; j++) {
-                int hits = 0, at = -1;
-                for (int base = 0; base < ne_rows; base += 64) {
-                    const int i = base + lane;
-                    const bool nz = i < ne_rows && !sh_used[i] && ne(mip_eq_cell<S>(root_eq, eq_rows, cols, w.frame, i, j), zero<S>());
-                    const unsigned long long bal = __ballot(nz);
-                    hits += __popcll(bal);
-                    if (bal) at = base + 63 - __clzll((long long)bal);
-                }
-                if (hits == 1) { fj = j; fat = at; }
-            }
-            if (lane == 0) { sh_pick[0] = fj; sh_pick[1] = fat; if (fat >= 0) sh_used[fat] = 1; }
-        }
-        __syncthreads();
-        const int j = sh_pick[0], at = sh_pick[1];
-        if (j < 0) break;
-        for (int q = threadIdx.x; q < rows; q += blockDim.x) {
-            S * Lq = w.L + (size_t)q * cols;
-            const S coef = Lq[j];
-            if (eq(coef, zero<S>())) continue;
-            if (q >= cols) { *sh_flag = 1; continue; }       // the reference reads the equality at the ROW's index
-            const S lead = mip_eq_cell<S>(root_eq, eq_rows, cols, w.frame, at, q);
-            const bool rescale = ne(lead, one<S>());
-            const S x1 = rescale ? q_div(false, one<S>(), lead) : one<S>();
-            const int m1 = rescale ? scale_mode(x1) : SCALE_KEEP, m2 = scale_mode(coef);
-            Lq[j] = zero<S>();
-            for (int k = 0; k < cols; k++) {
-                S t = mip_eq_cell<S>(root_eq, eq_rows, cols, w.frame, at, k);
-                t = q_scaled(false, t, x1, m1);
-                t = q_scaled(false, t, coef, m2);
-                if (k >= rhs0) t = neg(t);
-                Lq[k] = q_add(false, t, Lq[k]);
-            }
-        }
-        __syncthreads();
-        from = j + 1;
+    int left = 0;
+    if (ne_rows > 0) {
+        left = nf_convert_eq<S>(w.L, rows, cols, eqs, ne_rows, sh_left, sh_nf);
+        if (left < 0) return XPG_ERR_REF_UNDEFINED;
+        if (rows + 2 * left == 0) return XPG_ERR_SHAPE;
     }
-    // the equalities left over, in order: -row then +row (lpsol.h:1264-1277)
-    if (threadIdx.x < 64) {
-        int left = 0;
-        for (int base = 0; base < ne_rows; base += 64) {
-            const int i = base + lane;
-            const bool open = i < ne_rows && !sh_used[i];
-            const unsigned long long bal = __ballot(open);
-            if (open) sh_left[left + __popcll(bal & ((1ull << lane) - 1ull))] = (short)i;
-            left += __popcll(bal);
-        }
-        if (lane == 0) sh_pick[2] = left;
-    }
-    __syncthreads();
-    const int left = sh_pick[2];
-    for (int t = threadIdx.x; t < left * cols; t += blockDim.x) {
-        const int u = t / cols, k = t - u * cols;
-        const S c = mip_eq_cell<S>(root_eq, eq_rows, cols, w.frame, sh_left[u], k);
-        w.L[(size_t)(rows + 2 * u) * cols + k] = q_mul(false, c, minus_one<S>());
-        w.L[(size_t)(rows + 2 * u + 1) * cols + k] = c;
-    }
-    rows += 2 * left;
-    __syncthreads();
-    if (*sh_flag) return XPG_ERR_REF_UNDEFINED;
-    return rows > 0 ? rows : XPG_ERR_SHAPE;
-}
-
-// First half of finish_host for a solved node, by all threads: sol = (y, 1); the products sol[j] * tgtf[j] of the objective
-// (into y: the raw values are not needed again) and the reduced solution entries. The sum of the products keeps the
-// reference's order and stays with thread 0 (mip_feed); a third of the feed-back's serial time was these loops.
-template <class S> __device__ __forceinline__ void mip_feed_products(const MipWs<S> & w, const S * tgtf, int cols)
-{
-    const int n0 = cols - 1;
-    for (int j = threadIdx.x; j < cols; j += blockDim.x) {
-        const S x = j < n0 ? w.y[j] : one<S>();
-        w.y[j] = q_mul(false, x, tgtf[j]);
-        S t = x; reduce(t);
-        w.sol[j] = t;
-    }
-    __syncthreads();
+    if (extra > 0) nf_objective<S>(tgtf, cols, free_var, extra, w.wobj);
+    if (extra > 0 || left > 0) nf_form<S>(w.L, rows, cols, eqs, sh_left, left, free_var, extra, extra > 0 ? w.N : w.L);
+    return rows + 2 * left;
 }
 
 // MipTask::on_lp: feeds the node's answer to the recursion and runs it until the next LP is needed (returns
@@ -296,7 +168,7 @@ template <class S> __device__ bool mip_feed(const MipWs<S> & w, int cols, bool i
     {
         int * f = w.frame + top * 6;
         if (st == XPG_SIX_SUCC) {                            // finish_host (SIX::calcFinalSolution, lpsol.h:1851-1899), second half:
-            for (int j = 0; j < cols; j++) v = q_add(false, v, w.y[j]);   // the sum, in order, of the products mip_feed_products left
+            for (int j = 0; j < cols; j++) v = q_add(false, v, w.y[j]);   // the sum, in order, of the products nf_products left in y
             reduce(v);
         }
         if (st < 0) ret = st;
@@ -379,51 +251,15 @@ template <class S> __device__ bool mip_feed(const MipWs<S> & w, int cols, bool i
     }
 }
 
-// The free-variable split of SIX::normalize (lpsol.h:1365-1392) for the node mip_build_node left in w.L -- AFTER the fold
-// of the equalities, as normalize_cells_host (six_host.hip.h) does it: N = the node's columns as they are, behind them one
-// twin per free variable = its column times -1 with Matrix::mulOfColumn's arithmetic (scaled(): what k_normal_form does;
-// for fp64 it decides the sign of zeros), the constant column last; the objective likewise (normalize_plan). One pass
-// over the cells by all threads.
-template <class S> __device__ __forceinline__ void mip_split_free(const MipWs<S> & w, const S * tgtf, int rows, int cols,
-                                                                  const int * free_var, int extra)
-{
-    const int n0 = cols - 1, wc = cols + extra;
-    const S m1 = minus_one<S>();
-    const int mode = scale_mode(m1);
-    for (int t = threadIdx.x; t < rows * wc; t += blockDim.x) {
-        const int i = t / wc, c = t - i * wc;
-        const bool twin = c >= n0 && c < wc - 1;
-        const int sc = c < n0 ? c : (twin ? free_var[c - n0] : n0);
-        S x = w.L[(size_t)i * cols + sc];
-        if (twin) x = scaled(x, m1, mode);
-        w.N[t] = x;
-    }
-    for (int c = threadIdx.x; c < wc; c += blockDim.x) {
-        const bool twin = c >= n0 && c < wc - 1;
-        S x = tgtf[c < n0 ? c : (twin ? free_var[c - n0] : n0)];
-        if (twin) x = scaled(x, m1, mode);
-        w.wobj[c] = x;
-    }
-    __syncthreads();
-}
-// The LP of the node in w.L [rows x cols], by all threads: the SIX status, and on success the raw values of the ORIGINAL
-// variables in w.y[0 .. cols - 1). With free variables the LP is the widened one and its answer is folded back,
-// y[v] = y[v'] - y[v''] in the order of the list (finish_host, six_host.hip.h).
+// The LP of the node mip_build_node left in w.L [rows x cols] -- with free variables: widened in w.N, w.wobj --, by all
+// threads: the SIX status, and on success the raw values of the ORIGINAL variables in w.y[0 .. cols - 1).
 template <class S> __device__ __forceinline__ int mip_solve_node(Small<S> & P, const MipWs<S> & w, const S * tgtf, int rows, int cols,
                                                                  int is_max, const int * free_var, int extra, S * v_scratch)
 {
     Source<S> src;
-    src.leq = w.L; src.tgtf = tgtf; src.m = rows; src.cols = cols; src.is_max = is_max;
-    if (extra > 0) {
-        mip_split_free<S>(w, tgtf, rows, cols, free_var, extra);
-        src.leq = w.N; src.tgtf = w.wobj; src.cols = cols + extra;
-    }
+    src.leq = extra > 0 ? w.N : w.L; src.tgtf = extra > 0 ? w.wobj : tgtf; src.m = rows; src.cols = cols + extra; src.is_max = is_max;
     const int st = sm_solve_lp<S>(P, src, 10000u, /*raw_sol=*/1, w.y, v_scratch);
-    if (extra > 0 && st == XPG_SIX_SUCC) {
-        if (threadIdx.x == 0)
-            for (int k = 0; k < extra; k++) w.y[free_var[k]] = sub(w.y[free_var[k]], w.y[cols - 1 + k]);
-        __syncthreads();
-    }
+    if (extra > 0 && st == XPG_SIX_SUCC) nf_unsplit<S>(w.y, cols, free_var, extra);
     return st;
 }
 
@@ -442,7 +278,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
     // nmain: the first nmain workgroups walk trees (tree b by workgroup b % nmain); spq != NULL: speculation (see SP_*): then
     // nmain == nb (one tree per walking workgroup, its workspace never reused) and the workgroups behind them are helpers.
     // free_var / extra (may be NULL / 0): the batch's free variables, ascending; every node LP then has cols - 1 + extra
-    // variables (mip_split_free), which rmax-row workspace and LDS are sized for; the recursion keeps the original cols.
+    // variables (mip_build_node), which rmax-row workspace and LDS are sized for; the recursion keeps the original cols.
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int sh_ctl[8];
     __shared__ unsigned long long sh_v;                      // the node's own objective: recomputed by mip_feed
@@ -491,7 +327,7 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
             const S * tgtf = tgtf_all + (size_t)b * cols;
             const S * root = leq_all + (size_t)b * leq_rows * cols;
             const int my_rows = rows_of ? rows_of[b] : leq_rows;
-            int st = mip_build_node<S>(hw, root, my_rows, (const S *)0, 0, cols, is_bin != 0, f + 1, &sh_ctl[1]);
+            int st = mip_build_node<S>(hw, tgtf, root, my_rows, (const S *)0, 0, cols, is_bin != 0, f + 1, free_var, extra);
             if (st >= 0) st = mip_solve_node<S>(P, hw, tgtf, st, cols, is_max, free_var, extra, (S *)&sh_v);
             __syncthreads();
             for (int j = threadIdx.x; j < cols; j += blockDim.x) tw.spec_y[(size_t)f * cols + j] = hw.y[j];
@@ -558,12 +394,14 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
                 __syncthreads();
             }
             if (!parked) {
-                st = mip_build_node<S>(w, root, my_rows, root_eq, eq_rows, cols, is_bin != 0, top, &sh_ctl[1]);
+                st = mip_build_node<S>(w, tgtf, root, my_rows, root_eq, eq_rows, cols, is_bin != 0, top, free_var, extra);
                 MIP_T(0)
                 if (st >= 0) st = mip_solve_node<S>(P, w, tgtf, st, cols, is_max, free_var, extra, (S *)&sh_v);
             }
             MIP_T(1)
-            if (st == XPG_SIX_SUCC) mip_feed_products<S>(w, tgtf, cols);       // (st is the same in every thread)
+            // finish_host's products into y (the raw values are not needed again) and the reduced solution, by all threads;
+            // their sum, in the reference's order, stays with thread 0 (mip_feed): a third of the feed-back's serial time was these loops
+            if (st == XPG_SIX_SUCC) nf_products<S>(w.y, tgtf, cols, w.y, w.sol);    // (st is the same in every thread)
             if (threadIdx.x == 0) {
                 const bool ended = mip_feed<S>(w, cols, is_max != 0, is_bin != 0, st, allow);
                 sh_ctl[0] = ended ? 1 : 0;

@@ -3,15 +3,13 @@
 // host around a batch launch of one LP moves onto the device: SIX::normalize (src/com/lpsol.h:1290-1394) with
 // convertEq2Ineq (:1197-1278) in front of the LDS-resident solve, calcFinalSolution (:1851-1899) behind it. One workgroup
 // owns one LP from the caller's arrays to the answer:
-//   plan     convertEq2Ineq's choices (:1209-1222) from this LP's eq alone, by wave 0: column by column, a ballot over the
-//            equalities (lane = equality) finds the not yet used ones with a nonzero there; exactly one -> it is substituted
-//   fold     the substitutions on this LP's inequalities -- the cells of fold_eq / k_fold_eq (six_host.hip.h), the :1232
-//            quirk included: the leading value is read at the INEQUALITY's row index; where that leaves the row the LP ends
-//            XPG_ERR_REF_UNDEFINED and never meets the pivot loop
-//   form     the normal form N [rows x (n + 1)] (kept equalities as pairs -e / e, twins of the free variables) and the
-//            normalised objective, as k_normal_form / normalize_plan make them, into the workgroup's scratch slot
+//   reshape  SIX::normalize as normalize_dev.hip.h states it for every device route: convertEq2Ineq's choices from this LP's
+//            eq alone, each substitution folded into this LP's inequalities as it is chosen (where the reference's leading
+//            value, :1232, leaves the row the LP ends XPG_ERR_REF_UNDEFINED and never meets the pivot loop), then the normal
+//            form N [rows x (n + 1)] (kept equalities as pairs, twins of the free variables) and the normalised objective
+//            into the workgroup's scratch slot
 //   solve    sm_solve_lp (batch_kernels.hip.h) on N, raw solution
-//   finish   finish_host: undo the split, the objective on the ORIGINAL tgtf in column order, reduce
+//   finish   calcFinalSolution: undo the split, the objective on the ORIGINAL tgtf in column order, reduce
 // The caller's leq / eq are staged in the LP's LDS block BEFORE sm_carve claims it and reshaped there. They always fit: the
 // solver's tableau alone holds (leq_rows + 2 eq_rows) x (n + rows + 2) cells for maxm, and for minm its three rows of
 // n + rows + 2 cells, three counters per column and n rows of the tableau outweigh the (leq_rows + eq_rows) x (cols + 2) cells
@@ -47,13 +45,11 @@ template <class S> __host__ __device__ inline SixVcPlan six_vc_plan(bool pattern
 }
 
 // The scratch slot of one workgroup in HBM, in 8-byte cells: fv (the free variables, ascending) | N | obj | y | v.
-// And what the reshaping holds in LDS while it runs (work_cells): L (the inequalities, folded in place) | E | coef, inv (per
-// inequality, the step's coefficient and 1 / lead) | steps (pairs of int) | rest (int).
-struct SixVcSlot { size_t fv, N, obj, y, v, cells; size_t L, E, coef, inv, steps, rest, work_cells; };
+// And what the reshaping holds in LDS while it runs (work_cells): L (the inequalities, folded in place) | E | rest (int).
+struct SixVcSlot { size_t fv, N, obj, y, v, cells; size_t L, E, rest, work_cells; };
 __host__ __device__ inline SixVcSlot six_vc_slot(int leq_rows, int eq_rows, int cols, int nfree)
 {
     const size_t n0 = (size_t)cols - 1, n = n0 + (size_t)nfree, rows_max = (size_t)leq_rows + 2 * (size_t)eq_rows;
-    const size_t nst = (size_t)eq_rows < n0 ? (size_t)eq_rows : n0;
     SixVcSlot s;
     size_t o = 0;
     s.fv = o; o += (n0 + 1) / 2;
@@ -64,9 +60,6 @@ __host__ __device__ inline SixVcSlot six_vc_slot(int leq_rows, int eq_rows, int 
     size_t w = 0;
     s.L = w; w += (size_t)leq_rows * cols;
     s.E = w; w += (size_t)eq_rows * cols;
-    s.coef = w; w += (size_t)leq_rows;
-    s.inv = w; w += (size_t)leq_rows;
-    s.steps = w; w += nst;                       // 2 ints per step
     s.rest = w; w += ((size_t)eq_rows + 1) / 2;
     s.work_cells = w;
     s.cells = (o + 31) & ~(size_t)31;        // slots start on 256-byte lines
@@ -83,13 +76,12 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
                     int32_t * __restrict__ out_status, S * __restrict__ out_v, S * __restrict__ out_sol)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ int hdr[4];                                       // free variables, undefined flag, steps, kept equalities
+    __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
     const int n0 = cols - 1;
     S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
     int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
     const S m1 = minus_one<S>();
-    const int mode1 = scale_mode(m1);
 
     // ---- vc: sign pattern? which variables are free (lpsol.h:1321-1339: a column of vc without a nonzero) ----
     bool bad = false;
@@ -120,100 +112,29 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
     }
     S * const N = slot + sl.N; S * const obj = slot + sl.obj; S * const y = slot + sl.y; S * const vout = slot + sl.v;
     S * const work = (S *)lds;
-    S * const L = work + sl.L; S * const E = work + sl.E; S * const coef = work + sl.coef; S * const inv = work + sl.inv;
-    int * const steps = (int *)(work + sl.steps); int * const rest = (int *)(work + sl.rest);
+    S * const L = work + sl.L; S * const E = work + sl.E; int * const rest = (int *)(work + sl.rest);
     const int lcells = leq_rows * cols, ecells = eq_rows * cols;
 
     for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
         const S * tg = tgtf + (size_t)lp * cols;
-        __syncthreads();                                         // the LP before is through with the LDS block and the slot
+        __syncthreads();                                         // the LP before is through with the LDS block, the slot and hdr
         // ---- stage: the caller's cells as they lie, whole rows by consecutive lanes
         {
             const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
             for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
             for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
-            if (tid == 0) hdr[1] = 0;
         }
         __syncthreads();
-        // ---- plan (lpsol.h:1209-1222) by wave 0: lane l holds equalities l, l + 64, ...; bit c of `used`: equality 64 c + l
-        if (tid < 64) {
-            unsigned long long used = 0ull;
-            int ns = 0, nrest = 0;
-            if (leq_rows > 0)
-                for (int j = 0; j < n0; j++) {
-                    int hits = 0;
-                    for (int c = 0; c * 64 < eq_rows; c++) {
-                        const int i = c * 64 + lane;
-                        const bool hit = i < eq_rows && !((used >> c) & 1ull) && ne(E[i * cols + j], zero<S>());
-                        hits += __popcll(__ballot(hit));
-                    }
-                    if (hits != 1) continue;
-                    for (int c = 0; c * 64 < eq_rows; c++) {     // the one hit: its lane marks it, lane 0 of the wave records the step
-                        const int i = c * 64 + lane;
-                        const bool hit = i < eq_rows && !((used >> c) & 1ull) && ne(E[i * cols + j], zero<S>());
-                        const unsigned long long mask = __ballot(hit);
-                        if (hit) used |= 1ull << c;
-                        if (mask && lane == 0) { steps[2 * ns] = j; steps[2 * ns + 1] = c * 64 + __ffsll((long long)mask) - 1; }
-                    }
-                    ns++;
-                }
-            for (int c = 0; c * 64 < eq_rows; c++) {
-                const int i = c * 64 + lane;
-                const bool keep = i < eq_rows && !((used >> c) & 1ull);
-                const unsigned long long mask = __ballot(keep);
-                if (keep) rest[nrest + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-                nrest += __popcll(mask);
-            }
-            if (tid == 0) { hdr[2] = ns; hdr[3] = nrest; }
-        }
-        __syncthreads();
-        const int ns = hdr[2], nrest = hdr[3], rows = leq_rows + 2 * nrest;
-        // ---- fold (lpsol.h:1224-1250): a step changes inequality q from its own cells and the equality's alone
-        for (int s = 0; s < ns; s++) {
-            const int j = steps[2 * s], at = steps[2 * s + 1];
-            const S * e = E + at * cols;
-            for (int q = tid; q < leq_rows; q += nt) {
-                const S c = L[q * cols + j];
-                coef[q] = c;
-                if (eq(c, zero<S>())) continue;
-                if (q >= cols) hdr[1] = 1;                       // lpsol.h:1232 reads past the equality's row: undefined
-                else inv[q] = div(one<S>(), e[q]);
-            }
-            __syncthreads();
-            for (int t = tid; t < lcells; t += nt) {
-                const int q = t / cols, k = t - q * cols;
-                const S c = coef[q];
-                if (eq(c, zero<S>()) || q >= cols) continue;
-                const S iv = inv[q];
-                const int md1 = ne(e[q], one<S>()) ? scale_mode(iv) : (int)SCALE_KEEP, md2 = scale_mode(c);
-                S x = scaled(scaled(e[k], iv, md1), c, md2);
-                const S cur = k == j ? zero<S>() : L[t];
-                if (k >= n0) x = neg(x);
-                L[t] = add(x, cur);
-            }
-            __syncthreads();
-        }
-        if (hdr[1]) {                                            // this LP alone; it never meets the pivot loop
+        // ---- reshape (normalize_dev.hip.h): L folded in place, then N and the normalised objective
+        const EqRows<S> eq_lds = {E, cols};
+        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_lds, eq_rows, rest, hdr);
+        if (nrest < 0) {                                         // this LP alone; it never meets the pivot loop
             if (tid == 0) { out_status[lp] = XPG_ERR_REF_UNDEFINED; out_v[lp] = zero<S>(); }
             continue;
         }
-        // ---- form: N and the normalised objective (lpsol.h:1254-1268, :1365-1392), whole rows by consecutive lanes
-        for (int t = tid; t < rows * (n + 1); t += nt) {
-            const int i = t / (n + 1), c = t - i * (n + 1);
-            const bool from_eq = i >= leq_rows;
-            const S * src = from_eq ? E + rest[(i - leq_rows) >> 1] * cols : L + i * cols;
-            const int sc = c < n0 ? c : (c == n ? n0 : fv[c - n0]);
-            S x = src[sc];
-            if (from_eq && ((i - leq_rows) & 1) == 0) x = scaled(x, m1, mode1);
-            if (c >= n0 && c < n) x = scaled(x, m1, mode1);
-            N[t] = x;
-        }
-        for (int c = tid; c <= n; c += nt) {
-            S x = tg[c < n0 ? c : (c == n ? n0 : fv[c - n0])];
-            if (c >= n0 && c < n) x = scaled(x, m1, mode1);
-            obj[c] = x;
-        }
-        __syncthreads();                                         // L / E are read, N / obj written: the LDS block is the solver's
+        const int rows = leq_rows + 2 * nrest;
+        nf_objective<S>(tg, cols, fv, nfree, obj);
+        nf_form<S>(L, leq_rows, cols, eq_lds, rest, nrest, fv, nfree, N);    // (its barrier: L / E are read, the LDS block is the solver's)
         // ---- solve: the arrays and the code of a single call's launch (k_batch with nb = 1 on this normal form)
         Small<S> P;
         sm_carve(P, lds, is_max ? rows : n, is_max ? n : rows);
@@ -224,17 +145,10 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
             if (tid == 0) { out_status[lp] = status; out_v[lp] = zero<S>(); }
             continue;
         }
-        // ---- finish (lpsol.h:1851-1899, finish_host): y[j] - y[twin], constant slot 1, tgtf . sol in column order, reduce
-        for (int k = tid; k < nfree; k += nt) y[fv[k]] = sub(y[fv[k]], y[n0 + k]);
-        __syncthreads();
-        S * const prod = obj;                                    // (the normalised objective has done its work)
-        for (int j = tid; j < cols; j += nt) {
-            S x = j < n0 ? y[j] : one<S>();
-            prod[j] = mul(x, tg[j]);
-            reduce(x);
-            out_sol[(size_t)lp * cols + j] = x;
-        }
-        __syncthreads();
+        // ---- finish (calcFinalSolution): the products into obj, which has done its work; their sum in column order
+        nf_unsplit<S>(y, cols, fv, nfree);
+        S * const prod = obj;
+        nf_products<S>(y, tg, cols, prod, out_sol + (size_t)lp * cols);
         if (tid == 0) {
             S v = zero<S>();
             for (int j = 0; j < cols; j++) v = add(v, prod[j]);

@@ -11,6 +11,7 @@
 #include <time.h>
 #include "ctx.hip.h"
 #include "batch_kernels.hip.h"
+#include "normalize_dev.hip.h"
 
 namespace xpg {
 
@@ -32,44 +33,32 @@ template <class S> inline void scale_run(S * p, int n, int stride, S x)
     for (int k = 0; k < n; k++) p[(size_t)k * stride] = scaled(p[(size_t)k * stride], x, mode);
 }
 
-// SIX::convertEq2Ineq (lpsol.h:1197-1278): an equality whose column j is the
-// only nonzero among the remaining equalities is substituted into the
-// inequalities; the rest become a pair of opposite inequalities. The reference
-// reads the equality row at the *inequality's row index* (lpsol.h:1232); that is
-// reproduced, and refused once it would leave the row.
-template <class S> int fold_eq(HostMat<S> & L, const HostMat<S> & E, int rhs)
+// SIX::convertEq2Ineq (lpsol.h:1197-1278) on the host, from the choices normalize_plan has made: the equalities of
+// `steps` are substituted into the inequalities in that order, those of `rest` become a pair of opposite inequalities.
+// The reference reads the equality row at the *inequality's row index* (lpsol.h:1232); that is reproduced, and refused
+// once it would leave the row. These cells -- the reference's Matrix calls on a copied row -- are what the device's
+// (normalize_dev.hip.h) are held against (xpg_test_normalize).
+struct FoldStep { int j, at; };           // convertEq2Ineq: equality `at` is substituted for variable j (lpsol.h:1209-1252)
+template <class S> int fold_eq(HostMat<S> & L, const HostMat<S> & E, int rhs, const std::vector<FoldStep> & steps, const std::vector<int> & rest)
 {
-    if (E.r == 0) return 0;
-    std::vector<char> used(E.r, 0);
-    int remaining = E.r;
-    if (L.r > 0) {
-        for (int j = 0; j < rhs; j++) {
-            int hits = 0, at = 0;
-            for (int i = 0; i < E.r; i++)
-                if (!used[i] && ne(E(i, j), zero<S>())) { hits++; at = i; }
-            if (hits != 1) continue;
-            used[at] = 1; remaining--;
-            for (int q = 0; q < L.r; q++) {
-                const S coef = L(q, j);
-                if (eq(coef, zero<S>())) continue;
-                if (q >= E.c) return XPG_ERR_REF_UNDEFINED;
-                std::vector<S> t(&E.a[(size_t)at * E.c], &E.a[(size_t)at * E.c] + E.c);
-                const S lead = t[q];
-                if (ne(lead, one<S>())) scale_run(t.data(), E.c, 1, div(one<S>(), lead));
-                scale_run(t.data(), E.c, 1, coef);
-                L(q, j) = zero<S>();
-                for (int k = rhs; k < E.c; k++) t[k] = neg(t[k]);
-                for (int k = 0; k < E.c; k++) L(q, k) = add(t[k], L(q, k));
-            }
+    for (const FoldStep & st : steps)
+        for (int q = 0; q < L.r; q++) {
+            const S coef = L(q, st.j);
+            if (eq(coef, zero<S>())) continue;
+            if (q >= E.c) return XPG_ERR_REF_UNDEFINED;
+            std::vector<S> t(&E.a[(size_t)st.at * E.c], &E.a[(size_t)st.at * E.c] + E.c);
+            const S lead = t[q];
+            if (ne(lead, one<S>())) scale_run(t.data(), E.c, 1, div(one<S>(), lead));
+            scale_run(t.data(), E.c, 1, coef);
+            L(q, st.j) = zero<S>();
+            for (int k = rhs; k < E.c; k++) t[k] = neg(t[k]);
+            for (int k = 0; k < E.c; k++) L(q, k) = add(t[k], L(q, k));
         }
-    }
-    if (remaining > 0) {
-        const int base = L.r;
-        HostMat<S> G(base + 2 * remaining, E.c);
+    if (!rest.empty()) {
+        HostMat<S> G(L.r + 2 * (int)rest.size(), E.c);
         for (size_t k = 0; k < L.a.size(); k++) G.a[k] = L.a[k];
-        int at = base;
-        for (int i = 0; i < E.r; i++) {
-            if (used[i]) continue;
+        int at = L.r;
+        for (int i : rest) {
             for (int k = 0; k < E.c; k++) { G(at, k) = E(i, k); G(at + 1, k) = E(i, k); }
             scale_run(&G(at, 0), E.c, 1, minus_one<S>());
             at += 2;
@@ -81,7 +70,6 @@ template <class S> int fold_eq(HostMat<S> & L, const HostMat<S> & E, int rhs)
 
 // The result of SIX::normalize (lpsol.h:1290-1394): inequalities only, every variable
 // non-negative, free variables split v = v' - v''.
-struct FoldStep { int j, at; };           // convertEq2Ineq: equality `at` is substituted for variable j (lpsol.h:1209-1252)
 template <class S> struct NormalForm {
     int n0, n, cols;                      // original / normalised variable counts
     int rows;                             // inequalities after normalisation
@@ -197,7 +185,7 @@ int normalize_cells_host(const S * eqs, const S * leq, NormalForm<S> & F)
     const int cols = F.cols, n0 = F.n0, n = F.n, extra = (int)F.free_var.size();
     HostMat<S> L = F.leq_rows ? HostMat<S>(leq, F.leq_rows, cols) : HostMat<S>();
     const HostMat<S> E = F.eq_rows ? HostMat<S>(eqs, F.eq_rows, cols) : HostMat<S>();
-    int rc = fold_eq(L, E, n0);
+    int rc = fold_eq(L, E, n0, F.steps, F.rest);
     if (rc) return rc;
     if (L.r == 0) return XPG_ERR_SHAPE;
     F.N = HostMat<S>(L.r, n + 1);
@@ -224,11 +212,11 @@ int normalize_host(const S * tgtf, const S * vc, int vc_rows, const S * eqs, int
 
 // ---- the same cells made ON THE DEVICE (round 6: the HBM route; a 4096 x 8192 call with a hundred equalities spent seconds
 // in fold_eq on one host core in front of a 13 ms device solve) ---------------------------------------------------------
-// convertEq2Ineq's substitutions (lpsol.h:1224-1250). A substitution changes inequality q only, from its own cells and the
-// equality's (which nothing changes): rows are independent, so ONE launch runs every step on every row -- a workgroup per
-// row, thread t owning the columns k = t (mod 256), the step's coefficient L(q, j) handed round through LDS by the thread
-// that owns column j. The reference reads the equality at the INEQUALITY's row index for the leading value (:1232); that is
-// reproduced, and flagged once it would leave the row (the host form returns XPG_ERR_REF_UNDEFINED there).
+// convertEq2Ineq's substitutions (lpsol.h:1224-1250), the cells of normalize_dev.hip.h. A substitution changes inequality q
+// only, from its own cells and the equality's (which nothing changes): rows are independent, so ONE launch runs every step
+// on every row -- a workgroup per row, thread t owning the columns k = t (mod 256), the step's coefficient L(q, j) handed
+// round through LDS by the thread that owns column j. Where the leading value's index (:1232) leaves the row the launch
+// raises the flag (the host form returns XPG_ERR_REF_UNDEFINED there).
 template <class S> __global__ __launch_bounds__(256)
 void k_fold_eq(S * __restrict__ L, int lrows, int cols, int rhs, const S * __restrict__ E, const FoldStep * __restrict__ steps, int nsteps,
                int * __restrict__ flag)
@@ -246,41 +234,23 @@ void k_fold_eq(S * __restrict__ L, int lrows, int cols, int rhs, const S * __res
             if (eq(coef, zero<S>())) continue;
             if (q >= cols) { if (tid == 0) atomicOr(flag, 1); break; }
             const S * e = E + (size_t)at * cols;
-            const S lead = e[q];
-            const bool rescale = ne(lead, one<S>());
-            const S inv = div(one<S>(), lead);
-            const int m1 = rescale ? scale_mode(inv) : (int)SCALE_KEEP, m2 = scale_mode(coef);
-            for (int k = tid; k < cols; k += 256) {
-                S t = scaled(scaled(e[k], inv, m1), coef, m2);
-                const S cur = k == j ? zero<S>() : row[k];
-                if (k >= rhs) t = neg(t);
-                row[k] = add(t, cur);
-            }
+            const FoldScale<S> f = nf_fold_scale(e[q], coef);
+            for (int k = tid; k < cols; k += 256) row[k] = nf_fold_cell(e[k], f, row[k], k, j, rhs);
         }
         __syncthreads();
     }
 }
-// The normal form N [rows x (n + 1)] from the folded inequalities L [lrows x cols], the kept equalities as pairs -e / e
-// (lpsol.h:1254-1268) and the twins of the free variables (-column, lpsol.h:1380-1386).
+// The normal form N [rows x (n + 1)] from the folded inequalities L [lrows x cols], the kept equalities as pairs and the
+// twins of the free variables (nf_form_cell), a workgroup per row.
 template <class S> __global__ __launch_bounds__(256)
 void k_normal_form(const S * __restrict__ L, int lrows, int cols, const S * __restrict__ E, const int * __restrict__ rest, int nrest,
                    const int * __restrict__ free_var, int extra, S * __restrict__ N)
 {
     const int rows = lrows + 2 * nrest, n0 = cols - 1, n = n0 + extra;
-    const S m1 = minus_one<S>();
-    const int mode = scale_mode(m1);
     for (int i = (int)blockIdx.x; i < rows; i += (int)gridDim.x) {
-        const bool from_eq = i >= lrows;
-        const S * src = from_eq ? E + (size_t)rest[(i - lrows) >> 1] * cols : L + (size_t)i * cols;
-        const bool negate = from_eq && (((i - lrows) & 1) == 0);
+        const S * src = i >= lrows ? E + (size_t)rest[(i - lrows) >> 1] * cols : L + (size_t)i * cols;
         S * dst = N + (size_t)i * (n + 1);
-        for (int c = (int)threadIdx.x; c <= n; c += 256) {
-            const int sc = c < n0 ? c : (c == n ? n0 : free_var[c - n0]);
-            S x = src[sc];
-            if (negate) x = scaled(x, m1, mode);
-            if (c >= n0 && c < n) x = scaled(x, m1, mode);
-            dst[c] = x;
-        }
+        for (int c = (int)threadIdx.x; c <= n; c += 256) dst[c] = nf_form_cell(src[nf_src_col(c, n0, n, free_var)], i, lrows, c, n0, n);
     }
 }
 
