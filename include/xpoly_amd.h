@@ -236,6 +236,47 @@ int xpg_six_batch_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 *
                             int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol,
                             uint32_t * out_pivots);
 
+/* The same batches for LPs of ANY size the device can hold, not only those whose slack form fits one CU's LDS (the first
+ * fp64 shape xpg_six_batch_* refuses is about 100 inequalities x 100 variables).  Arguments, statuses and output rules are
+ * those of xpg_six_batch_*: leq[nb][m][cols], tgtf[nb][cols], x >= 0, no equalities; out_status[nb], out_v[nb] (0 unless
+ * the status is 0), out_sol[nb][cols] (rows of LPs whose status is not 0 untouched); nb == 0 returns 0.
+ * The route is decided by the shape alone, for the whole batch:
+ *   - the LP fits LDS (the rule of xpg_six_batch_*): the launch xpg_six_batch_* makes, unchanged;
+ *   - otherwise one workgroup per LP with the tableau [R][ld] in a scratch slot in device memory that belongs to the
+ *     workgroup (ld = V + R + 2 rounded up to an even number of cells; slots on 256-byte lines; grid x slot <= 256 MB, the
+ *     grid is cut to stay under it; the handle keeps the area, xpg_trim returns it) and everything else -- objective row,
+ *     basis maps, pair counters, the pivot-pair table -- in LDS;
+ *   - XPG_ERR_UNSUPPORTED before any launch, outputs untouched, when those side arrays do not fit 160 KB of LDS (about
+ *     R + V > 960) or one slot exceeds the 256 MB.
+ * Status, optimum and solution are bit for bit those of xpg_six_batch_* where that accepts the shape and of
+ * xpg_six_{maxm,minm}_* with vc = -I everywhere.  The _dev forms take device pointers for every array, only enqueue
+ * (results after xpg_sync; a scratch area that has to grow waits for the stream first) and fill out_pivots[nb] (may be
+ * NULL) with each LP's pivot count. */
+int xpg_six_batch_hbm_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf,
+                          const double * leq, int m, int cols, unsigned max_iter,
+                          int32_t * out_status, double * out_v, double * out_sol);
+int xpg_six_batch_hbm_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf,
+                            const xpg_rat32 * leq, int m, int cols, unsigned max_iter,
+                            int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol);
+int xpg_six_batch_hbm_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf,
+                              const double * leq, int m, int cols, unsigned max_iter,
+                              int32_t * out_status, double * out_v, double * out_sol,
+                              uint32_t * out_pivots);
+int xpg_six_batch_hbm_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf,
+                                const xpg_rat32 * leq, int m, int cols, unsigned max_iter,
+                                int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol,
+                                uint32_t * out_pivots);
+/* Evidence, no reference counterpart: the route of the calling thread's last xpg_six_batch_hbm_* call.  out[0] LPs solved
+ * LDS-resident, out[1] LPs solved on tableaux in device memory, out[2] the grid of the launch (all 0 after a refused or
+ * empty call).  Fills min(n, 3) entries. */
+int xpg_six_batch_hbm_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): what xpg_six_batch_hbm_* does with nb LPs of kind (0 fp64, 1 rational)
+ * solved as R rows x V variables on a device of num_cus compute units -- the function the launch itself asks.  Fills
+ * min(n, 7) entries: out[0] route (0 LDS-resident, 1 tableau in device memory, 2 refused); [1] LDS bytes per workgroup
+ * (route 0: the whole LP; else the side arrays); [2] bytes of one slot (0 on route 0); [3] ld; [4] threads per
+ * workgroup; [5] grid (0 when refused); [6] scratch bytes of the launch, grid x slot. */
+int xpg_test_batch_hbm_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n);
+
 /* The same batches for problems WITH equalities and free variables -- what SIX::maxm / minm is called with elsewhere
  * (Lineq::has_solution with is_int_sol = false, src/com/linsys.cpp:852-904, under the vc Lineq::initVarConstraint builds,
  * :803-819): nb problems of one shape, tgtf[nb][cols], eq[nb][eq_rows][cols], leq[nb][leq_rows][cols] (either may be NULL
@@ -513,7 +554,7 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
                                         int32_t * out_ok);
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
  * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
- * scratch slots of xpg_six_batch_vc_*. */
+ * scratch slots of xpg_six_batch_vc_* and xpg_six_batch_hbm_*. */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the

@@ -39,7 +39,13 @@ template <class S> struct Small {
     unsigned pivots;
     unsigned closes;                // iterations that ended in disableNV (no pivot), for profiling
     bool cn;                        // Rational: every input cell canonical -> the 32-bit forms (rat_ops.hip.h)
+    S * bcol;                       // k_batch_hbm only (batch_hbm.hip.h): the constant column mirrored in LDS, one entry per row
 };
+
+// HBM = true (k_batch_hbm, batch_hbm.hip.h): P.tab is a scratch slot in global memory. The control flow below is the
+// same; the pivot takes its global-memory form, the ratio test reads the constant column from its LDS mirror (whoever
+// writes that column keeps P.bcol equal to it), and the wave-level loops for R <= 64 are compiled out (such an LP fits LDS).
+template <class S> __device__ __forceinline__ void sm_pivot_hbm(Small<S> & P, int nv, int bv);
 
 template <class S> __device__ __forceinline__ bool sm_seen(const Small<S> & P, int nv, int b)
 { return (P.ppt[nv * P.pw + (b >> 5)] >> (b & 31)) & 1u; }
@@ -86,8 +92,17 @@ template <class S> __device__ __forceinline__ void sm_pivot(Small<S> & P, int nv
     __syncthreads();
 }
 
+template <class S, bool HBM> __device__ __forceinline__ void sm_pivot_on(Small<S> & P, int nv, int bv)
+{
+    if constexpr (HBM) sm_pivot_hbm(P, nv, bv); else sm_pivot(P, nv, bv);
+}
+template <class S, bool HBM> __device__ __forceinline__ S sm_const(const Small<S> & P, int i)
+{
+    if constexpr (HBM) return P.bcol[i]; else return P.tab[i * P.ld + P.rhs];
+}
+
 // SIX::findPivotBV (lpsol.h:553-663)
-template <class S> __device__ __forceinline__ int sm_ratio(const Small<S> & P, int nv)
+template <class S, bool HBM = false> __device__ __forceinline__ int sm_ratio(const Small<S> & P, int nv)
 {
     const int lim = P.rhs - 1;
     for (int pass = 0; pass < 2; pass++) {
@@ -98,7 +113,7 @@ template <class S> __device__ __forceinline__ int sm_ratio(const Small<S> & P, i
             if (pass == 0 ? le(a, zero<S>()) : eq(a, zero<S>())) continue;
             const int b = P.eq2bv[i];
             if (sm_seen(P, nv, b) || P.colcnt[b] >= lim) continue;
-            Cand<S> c; c.q = q_div(P.cn, P.tab[i * P.ld + P.rhs], a); c.idx = i;
+            Cand<S> c; c.q = q_div(P.cn, sm_const<S, HBM>(P, i), a); c.idx = i;
             weird |= unordered_value(c.q);
             best = better(best, c);
         }
@@ -113,7 +128,7 @@ template <class S> __device__ __forceinline__ int sm_ratio(const Small<S> & P, i
                     const int b = P.eq2bv[i];
                     bool ok = base + lane < P.R && !(pass == 0 ? le(a, zero<S>()) : eq(a, zero<S>()));
                     ok = ok && !(sm_seen(P, nv, b) || P.colcnt[b] >= lim);
-                    const S q = ok ? q_div(P.cn, P.tab[i * P.ld + P.rhs], a) : zero<S>();
+                    const S q = ok ? q_div(P.cn, sm_const<S, HBM>(P, i), a) : zero<S>();
                     scan_step_in_order(q, ok, base, sbest, sq);
                 }
                 if (lane == 0) P.sh_i[0] = sbest;
@@ -593,7 +608,7 @@ template <class S> __device__ __noinline__ FastLoopRet sm_fast_loop_32x97x256(__
 // starts from the tableau alone. resume: re-entered after such a hand-back (the pair table and counters are the LP's).
 enum { SM_SUSPEND = -100 };
 #define SM_NO_SLICE 0xFFFFFFFFu
-template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigned max_iter, S & maxv, unsigned & done_io, unsigned slice, bool resume)
+template <class S, bool HBM = false> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigned max_iter, S & maxv, unsigned & done_io, unsigned slice, bool resume)
 {
     const int rhs = P.rhs, lim = rhs - 1;
     if (!resume) {
@@ -603,7 +618,7 @@ template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigne
     maxv = zero<S>();
     __syncthreads();
     unsigned done = resume ? done_io : 0u;
-    const bool fast = rhs <= 128 && P.R <= 64;
+    const bool fast = !HBM && rhs <= 128 && P.R <= 64;
     const bool overlapped = fast && rhs <= 127 && blockDim.x >= 128;
     const bool sliced = slice != SM_NO_SLICE && overlapped;
     const unsigned stop_at = sliced && max_iter - done > slice ? done + slice : max_iter;
@@ -683,6 +698,7 @@ template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigne
                     S b = row[rhs];
                     reduce(b);
                     P.tab[i * P.ld + rhs] = b;
+                    if constexpr (HBM) P.bcol[i] = b;
                     if (ne(sum, b)) P.sh_w[1] = 1;
                 }
                 __syncthreads();
@@ -715,7 +731,7 @@ template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigne
                     while (mask) {
                         const int cand = base + __ffsll((long long)mask) - 1;
                         mask &= mask - 1;
-                        const int b = sm_ratio(P, cand);
+                        const int b = sm_ratio<S, HBM>(P, cand);
                         if (b < 0) continue;
                         enter = cand; leave = b;
                         break;
@@ -723,7 +739,7 @@ template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigne
                 }
             if (enter < 0) return 1;
         } else {
-            leave = sm_ratio(P, first);
+            leave = sm_ratio<S, HBM>(P, first);
             if (leave < 0) {                                            // lpsol.h:1146-1151
                 int add_n = 0;
                 for (int j = threadIdx.x; j < rhs; j += blockDim.x) {
@@ -744,15 +760,15 @@ template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigne
             P.rowcnt[enter] += 1; P.colcnt[leave] += 1;
         }
         __syncthreads();
-        sm_pivot(P, enter, leave);
+        sm_pivot_on<S, HBM>(P, enter, leave);
         done++;
     }
     return 4;
 }
-template <class S> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigned max_iter, S & maxv)
+template <class S, bool HBM = false> __device__ __forceinline__ int sm_solve(Small<S> & P, unsigned max_iter, S & maxv)
 {
     unsigned done = 0;
-    return sm_solve<S>(P, max_iter, maxv, done, SM_NO_SLICE, false);
+    return sm_solve<S, HBM>(P, max_iter, maxv, done, SM_NO_SLICE, false);
 }
 
 // Source of the slack form: the primal (is_max) or the dual built the way
@@ -769,7 +785,7 @@ template <class S> struct Source {
     __device__ S c0() const { return is_max ? tgtf[cols - 1] : q_mul(cn, zero<S>(), minus_one<S>()); }
 };
 
-template <class S> __device__ __forceinline__ void sm_build(Small<S> & P, const Source<S> & src, int with_xa)
+template <class S, bool HBM = false> __device__ __forceinline__ void sm_build(Small<S> & P, const Source<S> & src, int with_xa)
 {
     const int V = src.vars(), R = src.rows();
     const int first_slack = V + (with_xa ? 1 : 0);
@@ -782,6 +798,7 @@ template <class S> __device__ __forceinline__ void sm_build(Small<S> & P, const 
             else if (j == P.rhs) val = src.b(i);
             else if (j - first_slack == i) val = one<S>();
             P.tab[i * P.ld + j] = val;
+            if constexpr (HBM) { if (j == P.rhs) P.bcol[i] = val; }
         }
     for (int j = threadIdx.x; j < P.W; j += blockDim.x) {
         S val = zero<S>();
@@ -804,10 +821,10 @@ template <class S> __device__ __forceinline__ void sm_build(Small<S> & P, const 
 // reference's behaviour is undefined.
 // In three parts -- the auxiliary LP with x_a pivoted in, its solve, what follows it -- so that k_batch can run the solve
 // in time slices (sm_solve_lp).
-template <class S> __device__ __forceinline__ void sm_phase_one_pre(Small<S> & P, const Source<S> & src)
+template <class S, bool HBM = false> __device__ __forceinline__ void sm_phase_one_pre(Small<S> & P, const Source<S> & src)
 {
     const int V = src.vars(), xa = V;
-    sm_build(P, src, 1);
+    sm_build<S, HBM>(P, src, 1);
     Cand<S> best; best.q = zero<S>(); best.idx = INT_MAX;
     for (int i = threadIdx.x; i < P.R; i += blockDim.x) {
         Cand<S> c; c.q = P.tab[i * P.ld + P.rhs]; c.idx = i;
@@ -831,9 +848,9 @@ template <class S> __device__ __forceinline__ void sm_phase_one_pre(Small<S> & P
             __syncthreads();
         }
     }
-    sm_pivot(P, xa, P.eq2bv[best.idx]);
+    sm_pivot_on<S, HBM>(P, xa, P.eq2bv[best.idx]);
 }
-template <class S> __device__ __forceinline__ int sm_phase_one_post(Small<S> & P, const Source<S> & src, int solve_status, S top)
+template <class S, bool HBM = false> __device__ __forceinline__ int sm_phase_one_post(Small<S> & P, const Source<S> & src, int solve_status, S top)
 {
     const int V = src.vars(), xa = V;
     if (solve_status != 0) return 0;
@@ -855,7 +872,7 @@ template <class S> __device__ __forceinline__ int sm_phase_one_post(Small<S> & P
         __syncthreads();
         const int cand = P.sh_w[2];
         if (cand >= P.rhs) return -7;
-        sm_pivot(P, cand, xa);
+        sm_pivot_on<S, HBM>(P, cand, xa);
     }
     // objective rebuild (lpsol.h:944-953; substit: xmat.cpp:571-599 / :1491-1519)
     const int W = P.W, rhs = P.rhs;
@@ -982,7 +999,7 @@ template <class S, int CR, int CLD, int CT> __device__ __forceinline__ void sm_c
 // Time slices (k_batch): slice != SM_NO_SLICE lets the two solves -- stage 1's auxiliary LP and the LP's own -- hand the
 // LP back as SM_SUSPEND with (*stage_io, *done_io) saying where; a call with *stage_io != 0 goes on from there (the LDS
 // arrays and P's scalars restored by the caller).
-template <class S> __device__ __forceinline__ int sm_solve_lp(Small<S> & P, Source<S> & src, unsigned max_iter, int raw_sol,
+template <class S, bool HBM = false> __device__ __forceinline__ int sm_solve_lp(Small<S> & P, Source<S> & src, unsigned max_iter, int raw_sol,
                                                               S * sol, S * v_out, unsigned slice = SM_NO_SLICE, unsigned * done_io = nullptr,
                                                               int * stage_io = nullptr, unsigned slice1 = SM_NO_SLICE)
 {
@@ -1009,8 +1026,8 @@ template <class S> __device__ __forceinline__ int sm_solve_lp(Small<S> & P, Sour
         __syncthreads();
         const bool phase1 = !P.sh_w[3] || P.sh_w[4];
         __syncthreads();
-        if (phase1) { sm_phase_one_pre(P, src); stage = 1; }
-        else { sm_build(P, src, 0); stage = 2; }
+        if (phase1) { sm_phase_one_pre<S, HBM>(P, src); stage = 1; }
+        else { sm_build<S, HBM>(P, src, 0); stage = 2; }
     }
 #ifdef XPG_STAMPS
     unsigned long long lp_t_ = wall_clock64();
@@ -1018,9 +1035,9 @@ template <class S> __device__ __forceinline__ int sm_solve_lp(Small<S> & P, Sour
     if (stage == 1) {
         S top1 = zero<S>();
         unsigned done = entry == 1 ? *done_io : 0u;
-        const int st1 = sm_solve<S>(P, max_iter, top1, done, slice1, entry == 1);
+        const int st1 = sm_solve<S, HBM>(P, max_iter, top1, done, slice1, entry == 1);
         if (st1 == SM_SUSPEND) { *done_io = done; *stage_io = 1; return SM_SUSPEND; }
-        const int ok = sm_phase_one_post<S>(P, src, st1, top1);
+        const int ok = sm_phase_one_post<S, HBM>(P, src, st1, top1);
         if (ok == 0) status = 2;
         else if (ok < 0) status = XPG_ERR_REF_UNDEFINED;
         stage = 2;
@@ -1031,7 +1048,7 @@ template <class S> __device__ __forceinline__ int sm_solve_lp(Small<S> & P, Sour
     S top = zero<S>();
     if (status == -1) {
         unsigned done = entry == 2 ? *done_io : 0u;
-        status = sm_solve<S>(P, max_iter, top, done, slice, entry == 2);
+        status = sm_solve<S, HBM>(P, max_iter, top, done, slice, entry == 2);
         if (status == SM_SUSPEND) { *done_io = done; *stage_io = 2; return SM_SUSPEND; }
     }
 #ifdef XPG_STAMPS

@@ -12,13 +12,14 @@
 #include <thread>
 #include <vector>
 #include "../../include/xpoly_amd.h"
-// The library is ONE shared object built from this file compiled four times in parallel (-DXPG_PART=0..3, build.py):
+// The library is ONE shared object built from this file compiled five times in parallel (-DXPG_PART=0..4, build.py):
 // the device code of all kernels together takes four minutes in one translation unit, and every part only includes
 // the kernel headers its entry points launch. XPG_PART undefined = everything in one translation unit.
 //   part 0  handle, K1 pivot, the device-resident LP (every loop of lp_*.hip.h), warm-started MIP, test and debug hooks
 //   part 1  SIX::maxm / minm, the LDS-resident LP batches (k_batch), their multi-device and ragged forms
 //   part 2  MIP (device tree walk + host controller), has_solution, DepPoly::is_empty front end
 //   part 3  rational / integer row elimination (Lineq, rank / det / inv / null, hnf, gcd)
+//   part 4  LP batches beyond one CU's LDS (k_batch_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -37,6 +38,9 @@
 #include "six_host.hip.h"
 #include "batch_kernels.hip.h"
 #endif
+#if XPG_IN(4)
+#include "batch_hbm.hip.h"
+#endif
 #if XPG_IN(1)
 #include "six_batch_vc.hip.h"
 #endif
@@ -50,8 +54,8 @@
 using namespace xpg;
 
 // batch_dev<S> launches k_batch<S>: part 1 compiles it, part 2 (the MIP controller's node batches, has_solution's
-// LPs) calls part 1's instance
-#if XPG_PART == 2
+// LPs) and part 4 (LPs that do fit LDS) call part 1's instance
+#if XPG_PART == 2 || XPG_PART == 4
 namespace xpg {
 extern template int batch_dev<F64>(xpg_ctx *, int, int, const F64 *, const F64 *, int, int, unsigned, int32_t *, F64 *, F64 *, uint32_t *, int);
 extern template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *, int, int, unsigned, int32_t *, R32 *, R32 *, uint32_t *, int);
@@ -137,6 +141,7 @@ void xpg_destroy(xpg_ctx * ctx)
     if (ctx->hred) (void)hipHostFree(ctx->hred);
     if (ctx->slice_buf) (void)hipFree(ctx->slice_buf);
     if (ctx->six_vc_buf) (void)hipFree(ctx->six_vc_buf);
+    if (ctx->batch_hbm_buf) (void)hipFree(ctx->batch_hbm_buf);
     for (xpg_ctx * l : ctx->lanes) xpg_destroy(l);
     ctx->lanes.clear();
     for (auto & b : ctx->dev_cache) (void)hipFree(b.first);
@@ -610,6 +615,7 @@ int xpg_trim(xpg_ctx * ctx)
     if (ctx->hpack) { (void)hipHostFree(ctx->hpack); ctx->hpack = 0; ctx->hpack_cap = 0; }
     if (ctx->hred) { (void)hipHostFree(ctx->hred); ctx->hred = 0; ctx->hred_cap = 0; }
     if (ctx->six_vc_buf) { (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = 0; ctx->six_vc_cap = 0; }
+    if (ctx->batch_hbm_buf) { (void)hipFree(ctx->batch_hbm_buf); ctx->batch_hbm_buf = 0; ctx->batch_hbm_cap = 0; }
     return 0;
 }
 
@@ -1365,6 +1371,55 @@ int xpg_test_batch_geometry(int kind, int R, int V, int nb, int num_cus, long lo
     const BatchGeom g = kind == 0 ? batch_geometry<F64>(R, V, nb, num_cus) : batch_geometry<R32>(R, V, nb, num_cus);
     const long long f[10] = { (long long)g.lds, g.refused, g.cells, g.threads, g.per_cu, g.five, g.grid, g.seats, g.slice_shape, g.slice_crowded };
     for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
+    return 0;
+}
+} // extern "C"
+#endif
+#if XPG_IN(4)
+extern "C" {
+// ---- batches of LPs beyond one CU's LDS: a workgroup per LP on a tableau in global memory (batch_hbm.hip.h) ----
+int xpg_six_batch_hbm_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * leq, int m, int cols,
+                          unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol)
+{
+    XPG_BIND(ctx);
+    return batch_hbm_host<F64>(ctx, is_max, nb, (const F64 *)tgtf, (const F64 *)leq, m, cols, max_iter, out_status, (F64 *)out_v, (F64 *)out_sol);
+}
+int xpg_six_batch_hbm_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * leq, int m, int cols,
+                            unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol)
+{
+    XPG_BIND(ctx);
+    return batch_hbm_host<R32>(ctx, is_max, nb, (const R32 *)tgtf, (const R32 *)leq, m, cols, max_iter, out_status, (R32 *)out_v, (R32 *)out_sol);
+}
+int xpg_six_batch_hbm_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * leq, int m, int cols,
+                              unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol, uint32_t * out_pivots)
+{
+    XPG_BIND(ctx);
+    return batch_hbm_dev<F64>(ctx, is_max, nb, (const F64 *)tgtf, (const F64 *)leq, m, cols, max_iter, out_status, (F64 *)out_v, (F64 *)out_sol,
+                              out_pivots);
+}
+int xpg_six_batch_hbm_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * leq, int m, int cols,
+                                unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol, uint32_t * out_pivots)
+{
+    XPG_BIND(ctx);
+    return batch_hbm_dev<R32>(ctx, is_max, nb, (const R32 *)tgtf, (const R32 *)leq, m, cols, max_iter, out_status, (R32 *)out_v, (R32 *)out_sol,
+                              out_pivots);
+}
+// which route the LPs of the calling thread's last xpg_six_batch_hbm_* call took (batch_hbm.hip.h BatchHbmRoute)
+int xpg_six_batch_hbm_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const BatchHbmRoute & r = batch_hbm_route();
+    const long long f[3] = { r.lds, r.hbm, r.grid };
+    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test view: what xpg_six_batch_hbm_* would do with nb LPs solved as R rows x V variables on num_cus compute units
+int xpg_test_batch_hbm_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n)
+{
+    if (!out || n < 0 || R <= 0 || V <= 0 || nb <= 0 || num_cus <= 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
+    const HbmGeom g = kind == 0 ? batch_hbm_geometry<F64>(R, V, nb, num_cus) : batch_hbm_geometry<R32>(R, V, nb, num_cus);
+    const long long f[7] = { g.route, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
+    for (int k = 0; k < n && k < 7; k++) out[k] = f[k];
     return 0;
 }
 } // extern "C"

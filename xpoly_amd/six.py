@@ -166,8 +166,18 @@ class Context:
                       C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
                       C.c_void_p(sol_ptr)), "xpg_six_batch_vc_dev")
 
+    def six_batch_hbm_dev(self, kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr,
+                          pivots_ptr=None, max_iter=0xFFFFFFFF):
+        """xpg_six_batch_hbm_*_dev: six_batch_dev for LPs of any size (device pointers, enqueue only)."""
+        fn = lib().xpg_six_batch_hbm_f64_dev if kind == F64 else lib().xpg_six_batch_hbm_rat32_dev
+        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(leq_ptr),
+                      C.c_int(m), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr),
+                      C.c_void_p(v_ptr), C.c_void_p(sol_ptr),
+                      C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_hbm_dev")
+
     def trim(self):
-        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc go back to the runtime."""
+        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm go back to the
+        runtime."""
         self.check(lib().xpg_trim(self._h), "xpg_trim")
 
 
@@ -472,6 +482,46 @@ def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF)
                  vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
               "xpg_six_batch_vc")
     return st, v, sol
+
+
+def six_batch_hbm(ctx, kind, is_max, tgtf, leq, max_iter=0xFFFFFFFF, out=None):
+    """xpg_six_batch_hbm_*: Context.six_batch for LPs of any size -- an LP that fits one CU's LDS is solved as six_batch
+    solves it, a larger one by a workgroup of its own on a tableau in device memory. tgtf [nb, cols], leq [nb, m, cols].
+    Returns (status[nb], v[nb], sol[nb, cols]); `out`: such a triple to write into (rows of sol whose status is not 0 are
+    left alone). A shape beyond the kernel's limits raises XpgError (XPG_ERR_UNSUPPORTED) and writes nothing."""
+    tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
+    nb, m, cols = leq.shape[0], leq.shape[1], leq.shape[2]
+    if out is None:
+        out = (np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind))
+    status, v, sol = out
+    fn = lib().xpg_six_batch_hbm_f64 if kind == F64 else lib().xpg_six_batch_hbm_rat32
+    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq), C.c_int(m), C.c_int(cols),
+                 C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_six_batch_hbm")
+    return status, v, sol
+
+
+def six_batch_hbm_last_route():
+    """{'lds', 'hbm', 'grid'}: LPs of this thread's last six_batch_hbm call solved LDS-resident / on tableaux in device
+    memory, and the grid of its launch."""
+    out = (C.c_longlong * 3)()
+    rc = lib().xpg_six_batch_hbm_last_route(out, C.c_int(3))
+    if rc != 0:
+        raise XpgError("xpg_six_batch_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
+    return {"lds": out[0], "hbm": out[1], "grid": out[2]}
+
+
+BATCH_HBM_FIELDS = ("route", "lds", "slot", "ld", "threads", "grid", "scratch")
+
+
+def six_batch_hbm_geometry(kind, R, V, nb, num_cus=256):
+    """xpg_test_batch_hbm_geometry (host only, no device): what six_batch_hbm does with nb LPs solved as R rows x V
+    variables -- route (0 LDS-resident, 1 tableau in device memory, 2 refused), LDS bytes, slot bytes, ld, threads, grid,
+    scratch bytes of the launch."""
+    out = (C.c_longlong * 7)()
+    rc = lib().xpg_test_batch_hbm_geometry(C.c_int(kind), C.c_int(R), C.c_int(V), C.c_int(nb), C.c_int(num_cus), out, C.c_int(7))
+    if rc != 0:
+        raise XpgError("xpg_test_batch_hbm_geometry: %s" % _capi.ERRORS.get(rc, rc))
+    return dict(zip(BATCH_HBM_FIELDS, (int(x) for x in out)))
 
 
 def six_batch_last_route():
