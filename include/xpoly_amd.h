@@ -318,6 +318,55 @@ int xpg_six_batch_last_route(long long * out, int n);
 int xpg_test_six_batch_vc_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max,
                                long long * out, int n);
 
+/* xpg_six_batch_vc_* for shapes of ANY size: where the largest normal form is past 64 KB of LDS the batch is still one launch.
+ * Arguments, statuses and output rules are those of xpg_six_batch_vc_*.  The route is decided for the whole batch:
+ *   - vc is a sign pattern and the shape fits 64 KB: the launch xpg_six_batch_vc_* makes, unchanged;
+ *   - vc is a sign pattern and the shape is past 64 KB: one workgroup per LP stages eq / leq in a slot in device memory that
+ *     belongs to the workgroup, runs SIX::normalize there, solves on a tableau [R][ld] in the same slot (as
+ *     xpg_six_batch_hbm_* does: ld = the widest width V + R + 2 rounded up to an even number of cells, everything else of
+ *     the solver in LDS) and finishes calcFinalSolution.  Slots start on 256-byte lines; grid x slot <= 256 MB, the grid is
+ *     cut to stay under it; the handle keeps the area, xpg_trim returns it.  Taken when eq_rows <= 4096, the solver's side
+ *     arrays for the largest normal form fit 160 KB of LDS beside the kernel's own (about R + V <= 960) and one slot fits
+ *     the 256 MB;
+ *   - anything else (a general vc, a shape beyond those limits): xpg_six_{maxm,minm}_* per problem, as xpg_six_batch_vc_*.
+ * Same results on every route, bit for bit those of the single-problem entry points.
+ * The _dev forms take device pointers for EVERY array, vc included, and only enqueue (results after xpg_sync; a scratch
+ * area that has to grow waits for the stream first).  The host never sees vc there, so everything is sized for every
+ * variable being free: a shape that then fits 64 KB takes xpg_six_batch_vc_*_dev's launch untouched, any other takes the
+ * device-memory kernel for every LP (same bits at any size); where that kernel's limits are exceeded the call returns
+ * XPG_ERR_UNSUPPORTED before any launch and writes nothing.  A vc that turns out to be no sign pattern ends every LP
+ * XPG_ERR_UNSUPPORTED.  out_pivots[nb] (may be NULL): each LP's pivot count on the device-memory route; the LDS-resident
+ * kernel does not count, so on that route every entry is set to 0xFFFFFFFF, "not counted". */
+int xpg_six_batch_vc_hbm_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc,
+                             const double * eq, int eq_rows, const double * leq, int leq_rows, int cols,
+                             unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol);
+int xpg_six_batch_vc_hbm_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                               const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
+                               unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol);
+int xpg_six_batch_vc_hbm_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc,
+                                 const double * eq, int eq_rows, const double * leq, int leq_rows, int cols,
+                                 unsigned max_iter, int32_t * out_status, double * out_v, double * out_sol,
+                                 uint32_t * out_pivots);
+int xpg_six_batch_vc_hbm_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                                   const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
+                                   unsigned max_iter, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol,
+                                   uint32_t * out_pivots);
+/* Evidence, no reference counterpart: the route of the calling thread's last xpg_six_batch_vc_hbm_* call.  out[0] LPs on
+ * the LDS-resident kernel, out[1] LPs on tableaux in device memory, out[2] LPs on the per-problem fallback, out[3] free
+ * variables split per LP (-1 after a _dev call: only the device has read vc), out[4] the grid of the launch (0 without
+ * one).  Fills min(n, 5) entries. */
+int xpg_six_batch_vc_hbm_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the route rule of xpg_six_batch_vc_hbm_* for nb problems under a vc
+ * [vc_rows][cols] of kind (0 fp64, 1 rational) on a device of num_cus compute units -- the function the launch itself
+ * asks.  vc == NULL: the _dev forms' view (every variable taken as free).  Fills min(n, 10) entries: out[0] route (0
+ * LDS-resident kernel, 1 device-memory kernel, 2 neither: per-problem fallback / XPG_ERR_UNSUPPORTED from a _dev form);
+ * [1] free variables (-1 for vc == NULL, 0 for a general vc); [2], [3] rows and variables the largest normal form is
+ * solved with (Rmax, Vmax: under minm the dual's); [4] LDS bytes per workgroup (route 0: the whole LP, else the solver's
+ * side arrays); [5] bytes of one slot; [6] ld; [7] threads per workgroup; [8] grid (0 on route 2); [9] scratch bytes of
+ * the launch, grid x slot.  XPG_ERR_SHAPE unless vc_rows == cols - 1 (where vc is given), nb > 0, num_cus > 0. */
+int xpg_test_six_batch_vc_hbm_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max,
+                                   int nb, int num_cus, long long * out, int n);
+
 /* The same batches spread over the GPUs of one node from ONE caller thread -- what a C++ xpoly
  * caller of Lineq::has_solution (src/com/linsys.cpp:860-904) gets when it hands a SCoP's worth of
  * problems over at once.  devices[ndev] lists the HIP devices (NULL: 0 .. ndev-1; a device may be
@@ -554,7 +603,7 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
                                         int32_t * out_ok);
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
  * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
- * scratch slots of xpg_six_batch_vc_* and xpg_six_batch_hbm_*. */
+ * scratch slots of xpg_six_batch_vc_*, xpg_six_batch_hbm_* and xpg_six_batch_vc_hbm_*. */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the

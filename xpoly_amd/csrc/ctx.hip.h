@@ -32,6 +32,7 @@ struct xpg_ctx {
     void * slice_buf = 0; size_t slice_cap = 0;   // k_batch's time slices: checkpoints, queue and counters (grow-only)
     void * six_vc_buf = 0; size_t six_vc_cap = 0; // k_six_batch_vc's scratch slots, one per workgroup (grow-only; xpg_trim returns them)
     void * batch_hbm_buf = 0; size_t batch_hbm_cap = 0;   // k_batch_hbm's tableau slots, one per workgroup (grow-only; xpg_trim returns them)
+    void * six_vc_hbm_buf = 0; size_t six_vc_hbm_cap = 0; // k_six_batch_vc_hbm's slots, one per workgroup (grow-only; xpg_trim returns them)
     int loop_mode;          // XPG_LOOP: 0 the pipelined loop (2 launches per pivot), 3 the blocked loop (xpg_lp_loop_info's codes)
     int block_len;          // blocked loop: pivots staged per sweep, 1..BLK_MAX
     int loop_auto;          // XPG_LOOP unset: blocked loop where the sweep is what costs (large fp64 tableaux)

@@ -159,6 +159,28 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
     }
 }
 
+// The launch of k_six_batch_vc for a shape the device route takes (six_batch_vc_dev asks it, and the route rule of
+// xpg_six_batch_vc_hbm_* reports it): nfree as six_batch_vc_dev takes it.
+struct SixVcGeom { size_t lds; int threads; long long grid; size_t slot_cells; };
+template <class S> inline SixVcGeom six_vc_geometry(int nfree, int nb, int leq_rows, int eq_rows, int cols, bool is_max)
+{
+    const int nfree_cap = nfree >= 0 ? nfree : cols - 1;
+    const SixVcPlan least = six_vc_plan<S>(true, nfree >= 0 ? nfree : 0, leq_rows, eq_rows, cols, is_max);
+    const SixVcPlan most = six_vc_plan<S>(true, nfree_cap, leq_rows, eq_rows, cols, is_max);
+    SixVcGeom q;
+    q.lds = most.lds < (size_t)SIX_VC_LDS_MAX ? most.lds : (size_t)SIX_VC_LDS_MAX;
+    q.slot_cells = six_vc_slot(leq_rows, eq_rows, cols, nfree_cap).cells;
+    const int R = is_max ? least.rows_max : least.n, V = is_max ? least.n : least.rows_max;
+    const int cells = R * (V + R + 2);
+    q.threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);             // batch_geometry's rule
+    const int per_cu = (int)((160 * 1024) / q.lds) > 0 ? (int)((160 * 1024) / q.lds) : 1;
+    q.grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
+    if (q.grid > nb) q.grid = nb;
+    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / (q.slot_cells * 8));
+    if (q.grid > by_scratch) q.grid = by_scratch > 0 ? by_scratch : 1;
+    return q;
+}
+
 // Enqueue only; every pointer is a device pointer. nfree >= 0: the caller has read vc (the host-array form); -1: vc is known
 // to the device alone -- LDS and slots are sized for the worst vc can hold (every variable free), the kernel sizes each LP
 // by what it finds.
@@ -170,23 +192,15 @@ int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S
         (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq) || !out_status || !out_v || !out_sol)
         return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    const int nfree_cap = nfree >= 0 ? nfree : cols - 1;
     const SixVcPlan least = six_vc_plan<S>(true, nfree >= 0 ? nfree : 0, leq_rows, eq_rows, cols, is_max);
     if (!least.device) return XPG_ERR_UNSUPPORTED;               // (no vc makes this shape fit)
-    const SixVcPlan most = six_vc_plan<S>(true, nfree_cap, leq_rows, eq_rows, cols, is_max);
-    const size_t lds = most.lds < (size_t)SIX_VC_LDS_MAX ? most.lds : (size_t)SIX_VC_LDS_MAX;
-    const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree_cap);
-    const int R = is_max ? least.rows_max : least.n, V = is_max ? least.n : least.rows_max;
-    const int cells = R * (V + R + 2);
-    const int threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);     // batch_geometry's rule
-    const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
-    long long grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
-    if (grid > nb) grid = nb;
-    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / (sl.cells * 8));
-    if (grid > by_scratch) grid = by_scratch > 0 ? by_scratch : 1;
+    const SixVcGeom q = six_vc_geometry<S>(nfree, nb, leq_rows, eq_rows, cols, is_max);
+    const size_t lds = q.lds;
+    const int threads = q.threads;
+    long long grid = q.grid;
     static const int grid_cap = [] { const char * e = xpg_hook("XPG_SIX_VC_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
     if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-    const size_t need = (size_t)grid * sl.cells * 8;
+    const size_t need = (size_t)grid * q.slot_cells * 8;
     if (need > ctx->six_vc_cap) {
         if (ctx->six_vc_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = nullptr; ctx->six_vc_cap = 0; }
         const size_t cap = need + need / 2 < SIX_VC_SCRATCH_MAX ? need + need / 2 : need;
@@ -195,7 +209,7 @@ int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S
     }
     XPG_HIP(ctx, lds_limit((const void *)k_six_batch_vc<S>, ctx->device, lds));
     hipLaunchKernelGGL((k_six_batch_vc<S>), dim3((unsigned)grid), dim3(threads), lds, ctx->stream, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows,
-                       cols, is_max ? 1 : 0, max_iter, (unsigned)lds, (unsigned long long *)ctx->six_vc_buf, (unsigned long long)sl.cells,
+                       cols, is_max ? 1 : 0, max_iter, (unsigned)lds, (unsigned long long *)ctx->six_vc_buf, (unsigned long long)q.slot_cells,
                        out_status, out_v, out_sol);
     XPG_HIP(ctx, hipGetLastError());
     return 0;

@@ -12,7 +12,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/xpoly_amd.h"
-// The library is ONE shared object built from this file compiled five times in parallel (-DXPG_PART=0..4, build.py):
+// The library is ONE shared object built from this file compiled six times in parallel (-DXPG_PART=0..5, build.py):
 // the device code of all kernels together takes four minutes in one translation unit, and every part only includes
 // the kernel headers its entry points launch. XPG_PART undefined = everything in one translation unit.
 //   part 0  handle, K1 pivot, the device-resident LP (every loop of lp_*.hip.h), warm-started MIP, test and debug hooks
@@ -20,6 +20,7 @@
 //   part 2  MIP (device tree walk + host controller), has_solution, DepPoly::is_empty front end
 //   part 3  rational / integer row elimination (Lineq, rank / det / inv / null, hnf, gcd)
 //   part 4  LP batches beyond one CU's LDS (k_batch_hbm)
+//   part 5  the same with equalities and free variables (k_six_batch_vc_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -44,6 +45,9 @@
 #if XPG_IN(1)
 #include "six_batch_vc.hip.h"
 #endif
+#if XPG_IN(5)
+#include "six_batch_vc_hbm.hip.h"
+#endif
 #if XPG_IN(3)
 #include "lineq_host.hip.h"
 #endif
@@ -64,6 +68,23 @@ extern template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *
 namespace xpg {
 template int batch_dev<F64>(xpg_ctx *, int, int, const F64 *, const F64 *, int, int, unsigned, int32_t *, F64 *, F64 *, uint32_t *, int);
 template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *, int, int, unsigned, int32_t *, R32 *, R32 *, uint32_t *, int);
+}
+#endif
+
+// six_batch_vc_host<S> / six_batch_vc_dev<S> (k_six_batch_vc, six_solve): part 1 compiles them, part 5 (shapes that do fit
+// 64 KB, a general vc) calls part 1's instances
+#define XPG_SIX_VC_INSTANCES(X_, S_) \
+    X_ int six_batch_vc_dev<S_>(xpg_ctx *, bool, int, const S_ *, const S_ *, const S_ *, int, const S_ *, int, int, unsigned, int, int32_t *, S_ *, S_ *); \
+    X_ int six_batch_vc_host<S_>(xpg_ctx *, int, bool, int, const S_ *, const S_ *, const S_ *, int, const S_ *, int, int, unsigned, int32_t *, S_ *, S_ *);
+#if XPG_PART == 5
+namespace xpg {
+XPG_SIX_VC_INSTANCES(extern template, F64)
+XPG_SIX_VC_INSTANCES(extern template, R32)
+}
+#elif XPG_PART == 1
+namespace xpg {
+XPG_SIX_VC_INSTANCES(template, F64)
+XPG_SIX_VC_INSTANCES(template, R32)
 }
 #endif
 
@@ -142,6 +163,7 @@ void xpg_destroy(xpg_ctx * ctx)
     if (ctx->slice_buf) (void)hipFree(ctx->slice_buf);
     if (ctx->six_vc_buf) (void)hipFree(ctx->six_vc_buf);
     if (ctx->batch_hbm_buf) (void)hipFree(ctx->batch_hbm_buf);
+    if (ctx->six_vc_hbm_buf) (void)hipFree(ctx->six_vc_hbm_buf);
     for (xpg_ctx * l : ctx->lanes) xpg_destroy(l);
     ctx->lanes.clear();
     for (auto & b : ctx->dev_cache) (void)hipFree(b.first);
@@ -616,6 +638,7 @@ int xpg_trim(xpg_ctx * ctx)
     if (ctx->hred) { (void)hipHostFree(ctx->hred); ctx->hred = 0; ctx->hred_cap = 0; }
     if (ctx->six_vc_buf) { (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = 0; ctx->six_vc_cap = 0; }
     if (ctx->batch_hbm_buf) { (void)hipFree(ctx->batch_hbm_buf); ctx->batch_hbm_buf = 0; ctx->batch_hbm_cap = 0; }
+    if (ctx->six_vc_hbm_buf) { (void)hipFree(ctx->six_vc_hbm_buf); ctx->six_vc_hbm_buf = 0; ctx->six_vc_hbm_cap = 0; }
     return 0;
 }
 
@@ -1420,6 +1443,73 @@ int xpg_test_batch_hbm_geometry(int kind, int R, int V, int nb, int num_cus, lon
     const HbmGeom g = kind == 0 ? batch_hbm_geometry<F64>(R, V, nb, num_cus) : batch_hbm_geometry<R32>(R, V, nb, num_cus);
     const long long f[7] = { g.route, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
     for (int k = 0; k < n && k < 7; k++) out[k] = f[k];
+    return 0;
+}
+} // extern "C"
+#endif
+#if XPG_IN(5)
+extern "C" {
+// ---- batches with equalities and free variables beyond 64 KB of LDS: normalize, solve and finish by a workgroup per LP on
+// ---- a slot in global memory (six_batch_vc_hbm.hip.h) ----
+int xpg_six_batch_vc_hbm_f64(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc, const double * eq, int eq_rows,
+                             const double * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status, double * out_v,
+                             double * out_sol)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_hbm_host<F64>(ctx, 0, is_max != 0, nb, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows, (const F64 *)leq,
+                                      leq_rows, cols, max_iter, out_status, (F64 *)out_v, (F64 *)out_sol);
+}
+int xpg_six_batch_vc_hbm_rat32(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc, const xpg_rat32 * eq,
+                               int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status,
+                               xpg_rat32 * out_v, xpg_rat32 * out_sol)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_hbm_host<R32>(ctx, 1, is_max != 0, nb, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows, (const R32 *)leq,
+                                      leq_rows, cols, max_iter, out_status, (R32 *)out_v, (R32 *)out_sol);
+}
+int xpg_six_batch_vc_hbm_f64_dev(xpg_ctx * ctx, int is_max, int nb, const double * tgtf, const double * vc, const double * eq, int eq_rows,
+                                 const double * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status, double * out_v,
+                                 double * out_sol, uint32_t * out_pivots)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_hbm_dev<F64>(ctx, is_max != 0, nb, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows, (const F64 *)leq,
+                                     leq_rows, cols, max_iter, out_status, (F64 *)out_v, (F64 *)out_sol, out_pivots);
+}
+int xpg_six_batch_vc_hbm_rat32_dev(xpg_ctx * ctx, int is_max, int nb, const xpg_rat32 * tgtf, const xpg_rat32 * vc, const xpg_rat32 * eq,
+                                   int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status,
+                                   xpg_rat32 * out_v, xpg_rat32 * out_sol, uint32_t * out_pivots)
+{
+    XPG_BIND(ctx);
+    return six_batch_vc_hbm_dev<R32>(ctx, is_max != 0, nb, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows, (const R32 *)leq,
+                                     leq_rows, cols, max_iter, out_status, (R32 *)out_v, (R32 *)out_sol, out_pivots);
+}
+// which route the LPs of the calling thread's last xpg_six_batch_vc_hbm_* call took (six_batch_vc_hbm.hip.h SixVcHbmRoute)
+int xpg_six_batch_vc_hbm_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const SixVcHbmRoute & r = six_vc_hbm_route();
+    const long long f[5] = { r.lds, r.hbm, r.fallback, r.free_vars, r.grid };
+    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test view: the route rule of xpg_six_batch_vc_hbm_* and the sizes it decides by; vc == NULL: the _dev forms' view
+int xpg_test_six_batch_vc_hbm_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max, int nb, int num_cus,
+                                   long long * out, int n)
+{
+    if (!out || n < 0 || cols < 2 || (vc && vc_rows != cols - 1) || leq_rows < 0 || eq_rows < 0 || (leq_rows == 0 && eq_rows == 0) || nb <= 0 ||
+        num_cus <= 0 || (kind != 0 && kind != 1))
+        return XPG_ERR_SHAPE;
+    std::vector<int> fv;
+    SixVcHbmPlan g;
+    if (kind == 0) {
+        const bool pat = vc ? vc_sign_pattern((const F64 *)vc, vc_rows, cols, fv) : true;
+        g = six_vc_hbm_plan<F64>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus);
+    } else {
+        const bool pat = vc ? vc_sign_pattern((const R32 *)vc, vc_rows, cols, fv) : true;
+        g = six_vc_hbm_plan<R32>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus);
+    }
+    const long long f[10] = { g.route, g.nfree, g.Rmax, g.Vmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
+    for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
     return 0;
 }
 } // extern "C"

@@ -175,9 +175,21 @@ class Context:
                       C.c_void_p(v_ptr), C.c_void_p(sol_ptr),
                       C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_hbm_dev")
 
+    def six_batch_vc_hbm_dev(self, kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr, v_ptr,
+                             sol_ptr, pivots_ptr=None, max_iter=0xFFFFFFFF):
+        """xpg_six_batch_vc_hbm_*_dev: six_batch_vc_dev for shapes of any size (device pointers for every array, enqueue only).
+        Sized for every variable free: within 64 KB the LDS-resident launch, untouched (pivots_ptr then reads 0xFFFFFFFF, "not
+        counted"), otherwise every LP on a slot in device memory (pivots_ptr: each LP's pivot count). Beyond that kernel's
+        limits: XpgError (XPG_ERR_UNSUPPORTED), nothing launched or written."""
+        fn = lib().xpg_six_batch_vc_hbm_f64_dev if kind == F64 else lib().xpg_six_batch_vc_hbm_rat32_dev
+        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(vc_ptr),
+                      C.c_void_p(eq_ptr) if eq_ptr else None, C.c_int(eq_rows), C.c_void_p(leq_ptr) if leq_ptr else None,
+                      C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
+                      C.c_void_p(sol_ptr), C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_vc_hbm_dev")
+
     def trim(self):
-        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm go back to the
-        runtime."""
+        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm / six_batch_vc_hbm go
+        back to the runtime."""
         self.check(lib().xpg_trim(self._h), "xpg_trim")
 
 
@@ -522,6 +534,62 @@ def six_batch_hbm_geometry(kind, R, V, nb, num_cus=256):
     if rc != 0:
         raise XpgError("xpg_test_batch_hbm_geometry: %s" % _capi.ERRORS.get(rc, rc))
     return dict(zip(BATCH_HBM_FIELDS, (int(x) for x in out)))
+
+
+def six_batch_vc_hbm(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF, out=None):
+    """xpg_six_batch_vc_hbm_*: six_batch_vc for shapes of any size. A sign-pattern vc and a shape within 64 KB of LDS: the
+    launch six_batch_vc makes; a sign-pattern vc past that: still one launch, a workgroup per LP that normalises, solves and
+    finishes on a slot in device memory; anything else per problem as SIX.maxm / minm would. Arrays as six_batch_vc takes
+    them. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); `out`: such a triple to write into (rows of sol whose status is
+    not 0 are left alone)."""
+    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
+    leq = None if leq is None else as_kind(leq, kind, 3)
+    eq = None if eq is None else as_kind(eq, kind, 3)
+    nb, cols = tgtf.shape[0], tgtf.shape[1]
+    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
+        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
+    for a in (leq, eq):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq is None else leq.shape[1]
+    eq_rows = 0 if eq is None else eq.shape[1]
+    if out is None:
+        out = (np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind))
+    st, v, sol = out
+    fn = lib().xpg_six_batch_vc_hbm_f64 if kind == F64 else lib().xpg_six_batch_vc_hbm_rat32
+    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
+                 vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
+              "xpg_six_batch_vc_hbm")
+    return st, v, sol
+
+
+def six_batch_vc_hbm_last_route():
+    """{'lds', 'hbm', 'fallback', 'free', 'grid'}: LPs of this thread's last six_batch_vc_hbm / six_batch_vc_hbm_dev call on the
+    LDS-resident kernel / on slots in device memory / solved one by one, the free variables split per LP (-1 after a _dev
+    call), and the grid of its launch."""
+    out = (C.c_longlong * 5)()
+    rc = lib().xpg_six_batch_vc_hbm_last_route(out, C.c_int(5))
+    if rc != 0:
+        raise XpgError("xpg_six_batch_vc_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
+    return {"lds": out[0], "hbm": out[1], "fallback": out[2], "free": out[3], "grid": out[4]}
+
+
+SIX_BATCH_VC_HBM_FIELDS = ("route", "nfree", "Rmax", "Vmax", "lds", "slot", "ld", "threads", "grid", "scratch")
+
+
+def six_batch_vc_hbm_plan(kind, vc, leq_rows, eq_rows, cols, is_max, nb, num_cus=256):
+    """xpg_test_six_batch_vc_hbm_plan (host only, no device): what six_batch_vc_hbm does with nb problems of a shape under vc
+    [cols - 1, cols(,2)] -- route (0 LDS-resident kernel, 1 device-memory kernel, 2 neither), free variables, the rows and
+    variables the largest normal form is solved with, LDS bytes, slot bytes, ld, threads, grid, scratch bytes. vc=None: the
+    view of six_batch_vc_hbm_dev, which sizes for every variable free."""
+    vc_a = None if vc is None else as_kind(vc, kind, 2)
+    out = (C.c_longlong * 10)()
+    rc = lib().xpg_test_six_batch_vc_hbm_plan(C.c_int(kind), vp(vc_a), C.c_int(0 if vc_a is None else vc_a.shape[0]), C.c_int(leq_rows),
+                                              C.c_int(eq_rows), C.c_int(cols), C.c_int(int(is_max)), C.c_int(nb), C.c_int(num_cus),
+                                              out, C.c_int(10))
+    if rc != 0:
+        raise XpgError("xpg_test_six_batch_vc_hbm_plan: %s" % _capi.ERRORS.get(rc, rc))
+    return dict(zip(SIX_BATCH_VC_HBM_FIELDS, (int(x) for x in out)))
 
 
 def six_batch_last_route():
