@@ -412,8 +412,11 @@ int xpg_mip_minm_f64(xpg_ctx * ctx, const double * tgtf, const double * vc, int 
  * minimise) tgtf . x subject to leq (A | b), x >= 0 and integral (0/1 bounds are rows of leq, as for the parity MIP).
  * The tableau stays in HBM for the whole tree; a child is its parent's solved state plus one bound row.  Best
  * incumbent, bounding by the relaxation, floor child first -- a different (sane) walk from the reference's, so its
- * answers are checked against the optimum itself (tests/test_gpu_warm_mip.py: scipy / HiGHS), not against
- * MIP::RecusivePart.  out_stats (may be NULL): nodes, dual pivots over all nodes, primal pivots of the root, depth. */
+ * answers are checked against the optimum itself (tests/test_gpu_warm_mip.py: scipy / HiGHS;
+ * tests/test_gpu_warm_mip_exact.py: exact references, every end state), not against MIP::RecusivePart.  Returns XPG_IP_SUCC,
+ * XPG_IP_UNBOUND (the relaxation is unbounded), XPG_IP_NO_PRI_FEASIBLE_SOL, or XPG_ERR_UNSUPPORTED where a path needs more
+ * than 2 (cols - 1) + 8 bound rows.  *out_v is the optimum on XPG_IP_SUCC and 0 otherwise; out_sol (may be NULL) is written
+ * on XPG_IP_SUCC only.  out_stats (may be NULL): nodes, dual pivots over all nodes, primal pivots of the root, depth. */
 int xpg_mip_warm_f64(xpg_ctx * ctx, int is_max, const double * tgtf, const double * leq, int leq_rows,
                      int cols, int is_bin, double * out_v, double * out_sol, long long * out_stats);
 /* The same method for a BATCH: nb programs of one shape (tgtf [nb][cols], leq [nb][leq_rows][cols]), each tree walked by ONE
@@ -421,10 +424,20 @@ int xpg_mip_warm_f64(xpg_ctx * ctx, int is_max, const double * tgtf, const doubl
  * depth-first stack, snapshots in HBM, bounding -- as the parity walk does it for MIP::RecusivePart (xpg_mip_batch_*).
  * is_bin: the program is 0-1 (its x_j <= 1 rows are rows of leq): a path then appends at most one bound row per variable,
  * which sizes the LDS block; 0: what 64 KB allow (a tree that needs more ends XPG_ERR_UNSUPPORTED in out_status).
- * out_status[b] = XPG_IP_* (or XPG_ERR_UNSUPPORTED), out_v[b], out_sol[b][cols]; out_stats (may be NULL): nodes, dual
- * pivots and root pivots summed over the batch, the deepest path. */
+ * out_status[b] = XPG_IP_* (or XPG_ERR_UNSUPPORTED), out_v[b], out_sol[b][cols]: a tree that does not end XPG_IP_SUCC has
+ * out_v[b] = 0 and its out_sol row is left as the caller passed it in.  A tree whose relaxation is infeasible or unbounded
+ * counts no node.  The call itself returns XPG_ERR_UNSUPPORTED, and writes nothing, where the LDS block of a tree exceeds
+ * 64 KB even with 4 bound rows; nb = 0 returns 0 and touches nothing.  out_stats (may be NULL): nodes, dual pivots and root
+ * pivots summed over the batch, the deepest path.  Tests: tests/test_gpu_warm_mip.py (HiGHS),
+ * tests/test_gpu_warm_mip_exact.py (exact references, every launch geometry). */
 int xpg_mip_warm_batch_f64(xpg_ctx * ctx, int nb, int is_max, const double * tgtf, const double * leq, int leq_rows, int cols,
                            int is_bin, int32_t * out_status, double * out_v, double * out_sol, long long * out_stats);
+/* Host-only view for tests (no device needed): what xpg_mip_warm_batch_f64 launches nb trees of leq_rows x cols with, from
+ * the function the launch itself calls.  Fills min(n, 9) entries: out[0] LDS bytes of a workgroup, [1] 1 when the call is
+ * refused (XPG_ERR_UNSUPPORTED: more than 64 KB even with 4 bound rows), [2] depth_cap (bound rows a path may append),
+ * [3] mcap (row capacity), [4] wcap (row stride), [5] doubles per snapshot, [6] doubles of workspace per tree, [7] trees per
+ * launch, [8] launches. */
+int xpg_test_warm_batch_geometry(int leq_rows, int cols, int is_bin, int nb, long long * out, int n);
 /* Lineq::has_solution(leq, eq, vc, rhs_idx, is_int_sol, is_unique_sol),
  * src/com/linsys.cpp:830-906.  Returns 1 / 0, or XPG_ERR_*. */
 int xpg_has_solution_rat32(xpg_ctx * ctx, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq,

@@ -182,7 +182,17 @@ public:
         int rc = L.create(leq, rows, cols, tgtf, 0, 0, 0, extra);
         if (rc) return rc;
         L.set_options(1, 1e-9);                             // Dantzig pricing, tolerant feasibility for the root
-        int st = L.two_stage(0xFFFFFFFFu);
+        // phase one only where a constant is negative. SIX's own trigger (two_stage: lpsol.h:1794-1803) also fires where no
+        // objective coefficient is positive, and its auxiliary problem then calls a program infeasible whose optimum is the
+        // origin (maximise -4 y over x + y <= 2): tests/test_gpu_warm_mip_exact.py, mixed-2-1-0-s0
+        bool any_negative = false;
+        for (int i = 0; i < rows; i++) any_negative = any_negative || leq[(size_t)i * cols + cols - 1] < -tol;      // the batch form's test
+        int st;
+        if (any_negative) st = L.two_stage(0xFFFFFFFFu);
+        else {
+            if ((rc = L.begin())) return rc;
+            st = L.final_status = L.run_loop();
+        }
         if (st < 0) return st;
         LoopState hs;
         if ((rc = L.read_state(&hs))) return rc;

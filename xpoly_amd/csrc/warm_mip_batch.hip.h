@@ -18,7 +18,9 @@
 // Depth first, floor child first, best incumbent, bounding by the relaxation; a node on the stack is a snapshot of its
 // solved state in the tree's HBM workspace (live rows only), restored by the workgroup when it comes back to it.
 // Results are checked against the mathematics (scipy's HiGHS milp), not against the reference's walk, whose answers
-// depend on its fork counter (lpsol.h:2474-2497): tests/test_gpu_warm_mip.py.
+// depend on its fork counter (lpsol.h:2474-2497): tests/test_gpu_warm_mip.py, and against exact references (enumeration, a
+// branch and bound on fractions) at every launch geometry, end state and edge of the LDS block: tests/test_gpu_warm_mip_exact.py.
+// A tree that does not end XPG_IP_SUCC has out_v = 0 and its out_sol row as the caller passed it in.
 #pragma once
 #include <vector>
 #include "ctx.hip.h"
@@ -332,14 +334,18 @@ __global__ __launch_bounds__(WB_THREADS) void k_warm_mip_batch(int nb, const dou
     }
 }
 
-// Host side: shapes, workspace, launch, results. Trees are solved `chunk` at a time where the snapshot workspace of the
-// whole batch would exceed 4 GB.
-inline int warm_mip_batch(xpg_ctx * ctx, int nb, int is_max, const double * tgtf, const double * leq, int rows, int cols, int is_bin,
-                          int32_t * out_status, double * out_v, double * out_sol, long long * out_stats)
-{
-    if (!ctx || nb < 0 || !tgtf || !leq || rows <= 0 || cols < 2 || !out_status || !out_v || !out_sol) return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
+// THE shape rule (the launch and xpg_test_warm_batch_geometry both ask it): the LDS block of a tree, the bound rows a path may
+// append, the strides of the snapshot workspace, and how many trees go into one launch. Host only.
+struct WbPlan {
     WbShape S;
+    size_t lds;                   // bytes of LDS per workgroup
+    int refused;                  // 1: the tableau of a tree does not fit 64 KB even with 4 bound rows
+    int chunk, launches;          // trees per launch, launches for nb trees
+};
+inline WbPlan wb_plan(int rows, int cols, int is_bin, int nb)
+{
+    WbPlan P;
+    WbShape & S = P.S;
     S.n0 = cols - 1; S.m0 = rows;
     // bound rows a path may append: a 0-1 program (its x_j <= 1 rows are rows of the problem) branches on a variable at
     // most once per path; a general integer program gets what the one-tree form allows, as far as 64 KB of LDS go
@@ -349,14 +355,36 @@ inline int warm_mip_batch(xpg_ctx * ctx, int nb, int is_max, const double * tgtf
         if (wb_lds_bytes(S) <= 64 * 1024 || depth <= 4) break;
         depth -= 2;
     }
-    if (wb_lds_bytes(S) > 64 * 1024) { ctx->err = "warm-started branch and bound, batch form: the tableau of a tree does not fit 64 KB of LDS"; return XPG_ERR_UNSUPPORTED; }
+    P.lds = wb_lds_bytes(S);
+    P.refused = P.lds > 64 * 1024;
     S.snap_stride = (unsigned long long)S.mcap * S.wcap + S.wcap + 8 + ((unsigned long long)S.wcap + S.mcap + 1) / 2 + 1;
     S.tree_stride = 2 + S.n0 + (unsigned long long)S.depth_cap * S.snap_stride;
     S.tree_stride = (S.tree_stride + 15) & ~15ull;
-    const size_t lds = wb_lds_bytes(S);
+    // trees are solved `chunk` at a time where the snapshot workspace of the whole batch would exceed 4 GB
+    size_t ws_cap = (size_t)4 << 30;
+    if (const char * e = xpg_hook("XPG_WARM_BATCH_WS_CAP")) { const long long c = atoll(e); if (c > 0) ws_cap = (size_t)c; }   // tests: the chunk loop at small nb
     const size_t per_tree = (size_t)S.tree_stride * 8;
     int chunk = nb;
-    while ((size_t)chunk * per_tree > ((size_t)4 << 30) && chunk > 64) chunk = (chunk + 1) / 2;
+    while ((size_t)chunk * per_tree > ws_cap && chunk > 64) chunk = (chunk + 1) / 2;
+    P.chunk = chunk;
+    P.launches = chunk > 0 ? (nb + chunk - 1) / chunk : 0;
+    return P;
+}
+
+// Host side: workspace, launch, results.
+inline int warm_mip_batch(xpg_ctx * ctx, int nb, int is_max, const double * tgtf, const double * leq, int rows, int cols, int is_bin,
+                          int32_t * out_status, double * out_v, double * out_sol, long long * out_stats)
+{
+    if (!ctx || nb < 0 || !tgtf || !leq || rows <= 0 || cols < 2 || !out_status || !out_v || !out_sol) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    const WbPlan P = wb_plan(rows, cols, is_bin, nb);
+    if (P.refused) { ctx->err = "warm-started branch and bound, batch form: the tableau of a tree does not fit 64 KB of LDS"; return XPG_ERR_UNSUPPORTED; }
+    const WbShape S = P.S;
+    const size_t lds = P.lds;
+    const size_t per_tree = (size_t)S.tree_stride * 8;
+    const int chunk = P.chunk;
+    int grid_cap = 0;
+    if (const char * e = xpg_hook("XPG_WARM_BATCH_GRID")) grid_cap = atoi(e);   // tests: a workgroup takes several trees in turn
     const size_t in_l = (size_t)rows * cols * 8, in_t = (size_t)cols * 8;
     char * dev = nullptr;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -371,8 +399,10 @@ inline int warm_mip_batch(xpg_ctx * ctx, int nb, int is_max, const double * tgtf
         const int n = nb - lo < chunk ? nb - lo : chunk;
         e = hipMemcpyAsync(dev + o_leq, leq + (size_t)lo * rows * cols, in_l * n, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dev + o_tg, tgtf + (size_t)lo * cols, in_t * n, hipMemcpyHostToDevice, ctx->stream);
+        // the caller's rows go up first: the kernel writes the row of a solved tree only, every other row comes back as it was passed in
+        if (e == hipSuccess) e = hipMemcpyAsync(dev + o_sol, out_sol + (size_t)lo * cols, in_t * n, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_warm_mip_batch, dim3(n), dim3(WB_THREADS), lds, ctx->stream, n, (const double *)(dev + o_tg), (const double *)(dev + o_leq), S,
+        hipLaunchKernelGGL(k_warm_mip_batch, dim3(grid_cap > 0 && grid_cap < n ? grid_cap : n), dim3(WB_THREADS), lds, ctx->stream, n, (const double *)(dev + o_tg), (const double *)(dev + o_leq), S,
                            is_max ? 1 : 0, (double *)(dev + o_ws), (int32_t *)(dev + o_st), (double *)(dev + o_v), (double *)(dev + o_sol),
                            (unsigned *)(dev + o_stats));
         e = hipGetLastError();

@@ -665,6 +665,16 @@ int xpg_mip_warm_batch_f64(xpg_ctx * ctx, int nb, int is_max, const double * tgt
     XPG_BIND(ctx);
     return warm_mip_batch(ctx, nb, is_max, tgtf, leq, leq_rows, cols, is_bin, out_status, out_v, out_sol, out_stats);
 }
+// host-only test view: what xpg_mip_warm_batch_f64 would launch nb trees of that shape with (wb_plan, the launch's own rule)
+int xpg_test_warm_batch_geometry(int rows, int cols, int is_bin, int nb, long long * out, int n)
+{
+    if (!out || n < 0 || rows <= 0 || cols < 2 || nb <= 0) return XPG_ERR_SHAPE;
+    const WbPlan P = wb_plan(rows, cols, is_bin, nb);
+    const long long f[9] = { (long long)P.lds, P.refused, P.S.depth_cap, P.S.mcap, P.S.wcap, (long long)P.S.snap_stride, (long long)P.S.tree_stride,
+                             P.chunk, P.launches };
+    for (int k = 0; k < n && k < 9; k++) out[k] = f[k];
+    return 0;
+}
 
 } // extern "C"
 #endif // part 0
