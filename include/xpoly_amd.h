@@ -484,6 +484,40 @@ int xpg_mip_batch_vc_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const do
  * starts and summed over its walks: out[0] trees walked on the device, out[1] trees walked by the host controller,
  * out[2] free variables split per tree on the device route (0 on the host route).  Fills min(n, 3) entries. */
 int xpg_mip_last_route(long long * out, int n);
+/* xpg_mip_batch_vc_* for node LPs of ANY size: the same arguments, the same results (status, optimum, solution and node
+ * count bit for bit), one more route.
+ *   - a sign-pattern vc and node LPs within 64 KB of LDS: the launch xpg_mip_batch_vc_* makes;
+ *   - a sign-pattern vc past that: still one launch and no host controller -- a workgroup of 256 threads walks one tree
+ *     after the other as above, the tableau [R][ld] of every node LP in a slot in device memory that belongs to the
+ *     workgroup (as xpg_six_batch_hbm_*: ld = the widest width V + R + 2 rounded up to an even number of cells, everything
+ *     else of the solver in LDS; slots start on 256-byte lines).  Taken when eq_rows + cols + 1 <= 256, the solver's side
+ *     arrays for the largest node LP fit 160 KB of LDS beside the kernel's own (about R + V <= 960) and one slot fits
+ *     256 MB; grid x (slot + workspace) <= 256 MB, the grid is cut to stay under it; the handle keeps the slots, xpg_trim
+ *     returns them;
+ *   - anything else (a general vc, a shape beyond those limits): the host controller, as xpg_mip_batch_vc_*.
+ * xpg_mip_last_route counts the trees of the first two routes as walked on the device. */
+int xpg_mip_batch_vc_hbm_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg_rat32 * tgtf,
+                               const xpg_rat32 * vc, const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows,
+                               int cols, const uint8_t * rational_indicator, int32_t * out_status, xpg_rat32 * out_v,
+                               xpg_rat32 * out_sol, long long * out_nodes);
+int xpg_mip_batch_vc_hbm_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf,
+                             const double * vc, const double * eq, int eq_rows, const double * leq, int leq_rows,
+                             int cols, const uint8_t * rational_indicator, int32_t * out_status, double * out_v,
+                             double * out_sol, long long * out_nodes);
+/* Evidence, no reference counterpart: the route of the calling thread's last xpg_mip_batch_vc_hbm_* call.  out[0] trees
+ * on the LDS-resident walk, out[1] trees on the device-memory walk, out[2] trees on the host controller, out[3] free
+ * variables split per tree on the device, out[4] the grid of the launch (0 without one).  Fills min(n, 5) entries. */
+int xpg_mip_hbm_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the route rule of xpg_mip_batch_vc_hbm_* for nb trees of a shape of kind
+ * (0 fp64, 1 rational) on a device of num_cus compute units -- the function the launch itself asks.  pattern: whether vc
+ * is a sign pattern, extra: its free variables (ignored without a pattern).  Fills min(n, 11) entries: out[0] route (0
+ * LDS-resident walk, 1 device-memory walk, 2 host controller); [1] free variables; [2], [3] rows and variables the
+ * largest node LP is solved with (R, V: under minm the dual's); [4] LDS bytes per workgroup (route 0: the whole node LP,
+ * else the solver's side arrays); [5] bytes of one tableau slot (0 on route 0); [6] ld; [7] 8-byte words of one
+ * workgroup's workspace; [8] threads per workgroup; [9] grid (0 on route 2); [10] scratch bytes of the launch, grid x
+ * (slot + workspace).  XPG_ERR_SHAPE unless 0 <= extra <= cols - 1, nb > 0, num_cus > 0. */
+int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int cols, int is_bin, int is_max, int extra,
+                          int nb, int num_cus, long long * out, int n);
 /* Host-only views for tests (no device needed).  vc_pattern: 1 when vc [vc_rows][cols] of kind (0 fp64, 1 rational) is a
  * sign pattern, with out_free[j] = 1 for every free variable j < cols - 1; 0 when it is general; XPG_ERR_SHAPE unless
  * vc_rows == cols - 1.  mip_fits: 1 / 0, whether the device tree walk takes a problem of that shape with `extra` free
@@ -616,7 +650,8 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
                                         int32_t * out_ok);
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
  * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
- * scratch slots of xpg_six_batch_vc_*, xpg_six_batch_hbm_* and xpg_six_batch_vc_hbm_*. */
+ * scratch slots of xpg_six_batch_vc_*, xpg_six_batch_hbm_*, xpg_six_batch_vc_hbm_* and xpg_mip_batch_vc_hbm_* (which
+ * shares xpg_six_batch_hbm_*'s). */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the

@@ -1,6 +1,6 @@
-// Host controller of xpoly's branch-and-bound MIP<Mat,T> (src/com/lpsol.h:2087-2702),
-// of Lineq::has_solution (src/com/linsys.cpp:830-906) and of the DepPoly::is_empty front
-// end (src/eng/poly.cpp:530-573).
+// Host controller of xpoly's branch-and-bound MIP<Mat,T> (src/com/lpsol.h:2087-2702);
+// Lineq::has_solution (src/com/linsys.cpp:830-906) and the DepPoly::is_empty front end
+// (src/eng/poly.cpp:530-573) on top of it are in mip_front.hip.h.
 //
 // The tree walk is the reference's depth-first recursion -- its results depend on DFS order
 // through the shared fork_count row and the incumbent (lpsol.h:2474-2497) -- written as an
@@ -344,6 +344,11 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
                      int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes,
                      const uint8_t * allow_rational, const S * eqs, int eq_rows, const int * free_var = (const int *)0, int extra = 0);
 
+template <class S>
+int mip_batch_vc_host(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
+                      const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
+                      long long * out_nodes);
+
 // MIP::maxm / minm (lpsol.h:2636-2657, :2681-2702).
 template <class S>
 int mip_solve(xpg_ctx * ctx, int kind, bool is_max, bool is_bin, const S * tgtf, const S * vc, int vc_rows,
@@ -403,12 +408,12 @@ template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_b
 }
 // Launch shape of k_mip_tree for nb trees whose node LPs have at most rmax rows and n variables.
 struct MipGeom { size_t lds; int threads, grid; };
-template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax, int n, bool is_max)
+template <class S> inline MipGeom mip_geom_cus(int cus, int nb, int rmax, int n, bool is_max)
 {
     MipGeom g;
     const int R = is_max ? rmax : n, V = is_max ? n : rmax;
     g.lds = small_lds_bytes<S>(R, V);
-    const int cells = R * (V + R + 2), cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cells = R * (V + R + 2);
     g.threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);
     // more trees than the chip holds at that width: one wave per tree, more trees in flight (8192 knapsacks of 24
     // variables: 64 / 128 / 256 threads 623 k / 425 k / 318 k MIPs/s; at 1024, where the deepest tree decides, 163 / 171 / 170 k)
@@ -418,6 +423,8 @@ template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax
     if (g.grid > nb) g.grid = nb;
     return g;
 }
+template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax, int n, bool is_max)
+{ return mip_geom_cus<S>(ctx->num_cus > 0 ? ctx->num_cus : 256, nb, rmax, n, is_max); }
 // The same batch with the tree walks on the device (mip_kernels.hip.h): one workgroup per problem. Returns
 // XPG_ERR_UNSUPPORTED where a node LP of the deepest path would not fit the LDS budget -- the caller then takes the
 // host controller below. free_var [extra] (host; may be NULL / 0): the batch's free variables, ascending.
@@ -587,6 +594,16 @@ int mip_batch_vc(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, cons
             if (rc != XPG_ERR_UNSUPPORTED) return rc;
         }
     }
+    return mip_batch_vc_host<S>(ctx, kind, nb, is_max, is_bin, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, allow_rational, out_status, out_v,
+                                out_sol, out_nodes);
+}
+// The host controller's half of mip_batch_vc: every tree a MipTask under the caller's vc, advanced in lock step (arguments
+// checked by the caller, nb > 0).
+template <class S>
+int mip_batch_vc_host(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
+                      const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
+                      long long * out_nodes)
+{
     std::vector<MipTask<S> > tasks(nb);
     for (int b = 0; b < nb; b++)
         tasks[b].start(make_problem<S>(tgtf + (size_t)b * cols, vc, cols - 1, eq_rows > 0 ? eqs + (size_t)b * eq_rows * cols : (const S *)0, eq_rows,
@@ -602,178 +619,6 @@ int mip_batch_vc(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, cons
         nodes += T.nodes;
         if (T.final_status == XPG_IP_SUCC && out_sol && (int)T.sol.size() == cols)
             for (int j = 0; j < cols; j++) out_sol[(size_t)b * cols + j] = T.sol[j];
-    }
-    if (out_nodes) *out_nodes = nodes;
-    return 0;
-}
-
-// SIX::reviseTargetFunc on the all-ones objective (lpsol.h:2053-2074, linsys.cpp:851-862).
-inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, int cols, int rhs)
-{
-    std::vector<R32> tgtf(cols, R32(0, 1));
-    for (int j = 0; j < rhs; j++) {
-        bool nz = false;
-        for (int i = 0; i < leq_rows && !nz; i++) nz = !eq(leq[(size_t)i * cols + j], R32(0, 1));
-        for (int i = 0; i < eq_rows && !nz; i++) nz = !eq(eqs[(size_t)i * cols + j], R32(0, 1));
-        tgtf[j] = nz ? R32(1, 1) : R32(0, 1);
-    }
-    return tgtf;
-}
-
-// Lineq::has_solution (linsys.cpp:830-906): maxm then minm; success, or an unbounded answer
-// when a unique solution is not demanded, means "has a solution".
-inline int has_solution(xpg_ctx * ctx, const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, const R32 * vc,
-                        int vc_rows, int cols, int rhs, bool is_int, bool is_unique)
-{
-    if (!ctx || !vc || cols < 2 || rhs != cols - 1 || vc_rows != rhs) return XPG_ERR_SHAPE;
-    if (leq_rows == 0 && eq_rows == 0) return 0;
-    if (leq_rows == 0) return XPG_ERR_REF_UNDEFINED;      // the reference sizes tgtf from leq (linsys.cpp:851)
-    const std::vector<R32> tgtf = feasibility_objective(leq, leq_rows, eqs, eq_rows, cols, rhs);
-    R32 v; std::vector<R32> sol(cols);
-    for (int pass = 0; pass < 2; pass++) {
-        int st = is_int
-            ? mip_solve<R32>(ctx, 1, pass == 0, false, tgtf.data(), vc, vc_rows, eqs, eq_rows, leq, leq_rows, cols,
-                             (const uint8_t *)0, &v, sol.data(), (long *)0)
-            : six_solve<R32>(ctx, 1, pass == 0, tgtf.data(), vc, vc_rows, eqs, eq_rows, leq, leq_rows, cols,
-                             0xFFFFFFFFu, &v, sol.data());
-        if (st < 0) return st;
-        if (st == 0) return 1;
-        if (!is_unique && st == 1) return 1;
-    }
-    return 0;
-}
-
-
-// DepPoly::is_empty(keepit, vc) (src/eng/poly.cpp:530-573) for nb dependence polyhedra of one shape: the constant
-// is column rhs_idx, columns after it are constant symbols. move2var (when there are symbols) -> Lineq::reduce at
-// the last column -> inconsistent: empty; no row left: not empty; else Lineq::has_solution(int, unique) with the
-// caller's variable constraints vc [rhs_idx][rhs_idx + 1] (NULL: -x_i <= 0, poly.cpp:563-567).
-// With symbols that last step is undefined in the reference: has_solution is handed rhs_idx = the number of
-// variables while the matrix has grown by the symbols, which SIX::verify (lpsol.h:1526-1552, "No yet support const
-// term with multi-columns") only ASSERTs in debug builds -- those systems get XPG_ERR_REF_UNDEFINED, the ones
-// reduce decides get their answer.
-// symbols_as_vars (opt-in, NOT parity: XPG_DEP_SYMBOLS_AS_VARS): the evident intent of poly.cpp:530-573 for a parametrised
-// polyhedron -- after move2var the constant symbols ARE variables (free ones: nothing is known of their sign), so has_solution
-// is asked about the widened system, rhs_idx = the last column, vc widened by all-zero rows / columns for the symbols.
-inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs_idx, const R32 * vc_in,
-                              int32_t * out_empty, long * out_nodes, int symbols_as_vars = 0)
-{
-    if (!ctx || nb < 0 || !mats || rows <= 0 || cols < 2 || !out_empty || rhs_idx < 1 || rhs_idx > cols - 1) return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
-    const int last = cols - 1, nsym = last - rhs_idx;
-    // Variables that are x >= 0 or free (no vc, or a vc that is a sign pattern) and either no constant symbols or -- opt-in --
-    // the symbols as free variables: the whole test stays on the device -- reduce, the feasibility objectives, the integer
-    // maxm walk, the minm walk of what that left open -- and only the verdicts come back. With symbols, move2var runs on the
-    // host in front of the upload; the walks' free list is the caller's free variables, then every symbol.
-    static const bool on_dev = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    const bool widen_dev = nsym > 0 && symbols_as_vars != 0;
-    std::vector<int> fv;
-    const bool pattern = !vc_in || vc_sign_pattern(vc_in, rhs_idx, rhs_idx + 1, fv);
-    if (widen_dev) for (int j = rhs_idx; j < last; j++) fv.push_back(j);
-    const int extra = (int)fv.size();
-    if (on_dev && (nsym == 0 || widen_dev) && pattern && mip_device_fits<R32>(rows, cols, false, 0, extra) &&
-        lineq_lds_bytes(rows, cols) <= 160 * 1024 && rows <= 32767) {
-        const int n = cols - 1, rmax = rows + n, depth = n + 2;
-        const size_t bm = (size_t)nb * rows * cols * 8, bt = (size_t)nb * cols * 8;
-        DevBuf dm, dt, dk, dok, dact, demp, dst, dv, dn, dws, dfv;
-        std::vector<R32> moved;
-        if (nsym > 0) {
-            moved.resize((size_t)nb * rows * cols);
-            for (int b = 0; b < nb; b++)
-                move2var_one(mats + (size_t)b * rows * cols, moved.data() + (size_t)b * rows * cols, rows, cols, rhs_idx, rhs_idx + 1, last);
-            mats = moved.data();
-        }
-        if (extra > 0) {
-            XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
-            XPG_TRY(hipMemcpyAsync(dfv.p, fv.data(), (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        XPG_TRY(dm.alloc(ctx, bm)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
-        XPG_TRY(dok.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dact.alloc(ctx, (size_t)nb * 4)); XPG_TRY(demp.alloc(ctx, (size_t)nb * 4));
-        XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(dn.alloc(ctx, (size_t)nb * 4));
-        XPG_TRY(hipMemcpyAsync(dm.p, mats, bm, hipMemcpyHostToDevice, ctx->stream));
-        // Lineq::reduce on the device arrays (the C ABI entry: its kernels live in the row-elimination translation unit)
-        int rc = xpg_lineq_reduce_batch_rat32_dev(ctx, nb, (xpg_rat32 *)dm.p, rows, cols, last, 1, (int32_t *)dk.p, (int32_t *)dok.p);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_dep_prepare, dim3((nb + 3) / 4), dim3(64, 4), 0, ctx->stream, nb, (const R32 *)dm.p, rows, cols,
-                           (const int *)dk.p, (const int *)dok.p, (R32 *)dt.p, (int *)dact.p, (int32_t *)demp.p);
-        XPG_TRY(hipMemsetAsync(dn.p, 0, (size_t)nb * 4, ctx->stream));
-        std::vector<int32_t> nodes_a((size_t)nb, 0), nodes_b((size_t)nb, 0);
-        for (int pass = 0; pass < 2; pass++) {
-            const bool is_max = pass == 0;
-            const MipGeom g = mip_geom<R32>(ctx, nb, rmax, n + extra, is_max);
-            const size_t lds = g.lds;
-            const int threads = g.threads, grid = g.grid;
-            const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
-            const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-            if (pass == 0) XPG_TRY(dws.alloc(ctx, (size_t)(cus * 32 < nb ? cus * 32 : nb) * ws_words * 8));   // the largest grid of either pass
-            XPG_TRY(hipMemsetAsync(dn.p, 0, (size_t)nb * 4, ctx->stream));
-            XPG_TRY(lds_limit((const void *)k_mip_tree<R32>, ctx->device, lds));
-            hipLaunchKernelGGL((k_mip_tree<R32>), dim3(grid), dim3(threads), lds, ctx->stream, nb, (const R32 *)dt.p, (const R32 *)dm.p,
-                               rows, cols, is_max ? 1 : 0, 0, rmax, depth, (unsigned long long *)dws.p, ws_words,
-                               (int32_t *)dst.p, (R32 *)dv.p, (R32 *)0, (int *)dn.p, (const int *)dk.p, (const int *)dact.p, (const uint8_t *)0,
-                               (const R32 *)0, 0, grid, (int *)0, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
-            XPG_TRY(hipGetLastError());
-            XPG_TRY(hipMemcpyAsync(pass == 0 ? nodes_a.data() : nodes_b.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-            hipLaunchKernelGGL(k_dep_update, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, (const int32_t *)dst.p,
-                               (int *)dact.p, (int32_t *)demp.p);
-        }
-        XPG_TRY(hipMemcpyAsync(out_empty, demp.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        if (out_nodes) { long t = 0; for (int b = 0; b < nb; b++) t += nodes_a[(size_t)b] + nodes_b[(size_t)b]; *out_nodes = t; }
-        MipRoute & rt = mip_route();                     // a tree that was walked counted at least its root
-        for (int b = 0; b < nb; b++) rt.device_trees += (nodes_a[(size_t)b] > 0) + (nodes_b[(size_t)b] > 0);
-        if (extra > rt.free_vars) rt.free_vars = extra;
-        return 0;
-    }
-    std::vector<R32> work((size_t)nb * rows * cols);
-    if (nsym > 0) {
-        for (int b = 0; b < nb; b++)
-            move2var_one(mats + (size_t)b * rows * cols, work.data() + (size_t)b * rows * cols, rows, cols, rhs_idx, rhs_idx + 1, last);
-    } else {
-        work.assign(mats, mats + (size_t)nb * rows * cols);
-    }
-    std::vector<int32_t> kept(nb), ok(nb);
-    int rc = xpg_lineq_reduce_batch_rat32(ctx, nb, (xpg_rat32 *)work.data(), rows, cols, last, 1, kept.data(), ok.data());
-    if (rc) return rc;
-    const bool widen = nsym > 0 && symbols_as_vars != 0;
-    const int nv = widen ? last : rhs_idx;
-    std::vector<R32> vc((size_t)nv * (nv + 1), R32(0, 1));
-    if (vc_in && !widen) vc.assign(vc_in, vc_in + (size_t)nv * (nv + 1));
-    else if (vc_in) {                                // the caller's [rhs_idx][rhs_idx + 1] block; the symbols' rows and columns stay zero (free)
-        for (int i = 0; i < rhs_idx; i++) {
-            for (int j = 0; j < rhs_idx; j++) vc[(size_t)i * (nv + 1) + j] = vc_in[(size_t)i * (rhs_idx + 1) + j];
-            vc[(size_t)i * (nv + 1) + nv] = vc_in[(size_t)i * (rhs_idx + 1) + rhs_idx];
-        }
-    }
-    else for (int i = 0; i < rhs_idx; i++) vc[(size_t)i * (nv + 1) + i] = R32(-1, 1);
-    std::vector<int> open;                       // systems still undecided
-    for (int b = 0; b < nb; b++) {
-        if (!ok[b]) out_empty[b] = 1;            // inconsistent bounds: empty (poly.cpp:550-552)
-        else if (kept[b] == 0) out_empty[b] = 0; // only redundant constraints: conservatively non-empty (:553-557)
-        else if (nsym > 0 && !widen) out_empty[b] = XPG_ERR_REF_UNDEFINED;
-        else { out_empty[b] = 1; open.push_back(b); }
-    }
-    long nodes = 0;
-    for (int pass = 0; pass < 2 && !open.empty(); pass++) {          // maxm, then minm (linsys.cpp:864-876)
-        std::vector<MipTask<R32> > tasks(open.size());
-        for (size_t t = 0; t < open.size(); t++) {
-            const int b = open[t];
-            const R32 * leq = work.data() + (size_t)b * rows * cols;
-            const std::vector<R32> tgtf = feasibility_objective(leq, kept[b], (const R32 *)0, 0, cols, last);
-            tasks[t].start(make_problem<R32>(tgtf.data(), vc.data(), nv, (const R32 *)0, 0, leq, kept[b], cols),
-                           pass == 0, false, (const uint8_t *)0);
-        }
-        rc = run_mip_tasks<R32>(ctx, 1, tasks);
-        if (rc) return rc;
-        std::vector<int> still;
-        for (size_t t = 0; t < open.size(); t++) {
-            nodes += tasks[t].nodes;
-            const int st = tasks[t].final_status;
-            if (st < 0) out_empty[open[t]] = st;             // reference undefined on this system
-            else if (st == XPG_IP_SUCC) out_empty[open[t]] = 0;
-            else still.push_back(open[t]);
-        }
-        open.swap(still);
     }
     if (out_nodes) *out_nodes = nodes;
     return 0;

@@ -439,38 +439,4 @@ void k_mip_tree(int nb, const S * tgtf_all, const S * leq_all, int leq_rows, int
     }
 }
 
-// ---- DepPoly::is_empty (src/eng/poly.cpp:530-573) after the reduce, on the device ------------------------------
-// Per polyhedron b with reduce's outputs kept[b] / ok[b]: the verdict reduce alone gives, else the feasibility
-// objective of Lineq::has_solution (SIX::reviseTargetFunc on all ones, lpsol.h:2053-2074 / linsys.cpp:851-862: 1 for
-// every variable that occurs in some inequality) and the "still open" mark for the MIP walks that follow.
-__global__ void k_dep_prepare(int nb, const R32 * mats, int rows, int cols, const int * kept, const int * ok, R32 * tgtf,
-                              int * active, int32_t * empty)
-{
-    const int b = blockIdx.x * blockDim.y + threadIdx.y;
-    if (b >= nb) return;
-    const int last = cols - 1, k = kept[b];
-    const bool open = ok[b] != 0 && k > 0;
-    if (threadIdx.x == 0) {
-        active[b] = open ? 1 : 0;
-        empty[b] = !ok[b] ? 1 : (k == 0 ? 0 : 1);       // inconsistent bounds: empty; only redundant constraints: not
-    }
-    const R32 * m = mats + (size_t)b * rows * cols;
-    for (int j = threadIdx.x; j < cols; j += blockDim.x) {
-        bool nz = false;
-        if (open && j < last)
-            for (int i = 0; i < k && !nz; i++) nz = ne(m[(size_t)i * cols + j], R32(0, 1));
-        tgtf[(size_t)b * cols + j] = nz ? R32(1, 1) : R32(0, 1);
-    }
-}
-// After a walk (maxm, then minm; linsys.cpp:864-876): success = a solution exists = not empty, decided; a negative
-// status = the reference is undefined on this system, decided; anything else stays open for the next walk.
-__global__ void k_dep_update(int nb, const int32_t * status, int * active, int32_t * empty)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb || active[b] != 1) return;
-    const int st = status[b];
-    if (st < 0) { empty[b] = st; active[b] = 0; }
-    else if (st == XPG_IP_SUCC) { empty[b] = 0; active[b] = 0; }
-}
-
 } // namespace xpg

@@ -12,7 +12,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/xpoly_amd.h"
-// The library is ONE shared object built from this file compiled six times in parallel (-DXPG_PART=0..5, build.py):
+// The library is ONE shared object built from this file compiled seven times in parallel (-DXPG_PART=0..6, build.py):
 // the device code of all kernels together takes four minutes in one translation unit, and every part only includes
 // the kernel headers its entry points launch. XPG_PART undefined = everything in one translation unit.
 //   part 0  handle, K1 pivot, the device-resident LP (every loop of lp_*.hip.h), warm-started MIP, test and debug hooks
@@ -21,6 +21,7 @@
 //   part 3  rational / integer row elimination (Lineq, rank / det / inv / null, hnf, gcd)
 //   part 4  LP batches beyond one CU's LDS (k_batch_hbm)
 //   part 5  the same with equalities and free variables (k_six_batch_vc_hbm)
+//   part 6  MIP tree walks whose node LPs are beyond 64 KB of LDS (k_mip_tree_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -35,7 +36,7 @@
 #include "warm_mip.hip.h"
 #include "warm_mip_batch.hip.h"
 #endif
-#if XPG_IN(1) || XPG_IN(2)
+#if XPG_IN(1) || XPG_IN(2) || XPG_IN(6)
 #include "six_host.hip.h"
 #include "batch_kernels.hip.h"
 #endif
@@ -52,14 +53,17 @@
 #include "lineq_host.hip.h"
 #endif
 #if XPG_IN(2)
-#include "mip_host.hip.h"
+#include "mip_front.hip.h"
+#endif
+#if XPG_IN(6)
+#include "mip_tree_hbm.hip.h"
 #endif
 
 using namespace xpg;
 
 // batch_dev<S> launches k_batch<S>: part 1 compiles it, part 2 (the MIP controller's node batches, has_solution's
-// LPs) and part 4 (LPs that do fit LDS) call part 1's instance
-#if XPG_PART == 2 || XPG_PART == 4
+// LPs), part 4 (LPs that do fit LDS) and part 6 (which includes the controller's header) call part 1's instance
+#if XPG_PART == 2 || XPG_PART == 4 || XPG_PART == 6
 namespace xpg {
 extern template int batch_dev<F64>(xpg_ctx *, int, int, const F64 *, const F64 *, int, int, unsigned, int32_t *, F64 *, F64 *, uint32_t *, int);
 extern template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *, int, int, unsigned, int32_t *, R32 *, R32 *, uint32_t *, int);
@@ -69,6 +73,19 @@ namespace xpg {
 template int batch_dev<F64>(xpg_ctx *, int, int, const F64 *, const F64 *, int, int, unsigned, int32_t *, F64 *, F64 *, uint32_t *, int);
 template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *, int, int, unsigned, int32_t *, R32 *, R32 *, uint32_t *, int);
 }
+#endif
+
+// mip_batch_device<S> (k_mip_tree) and mip_batch_vc_host<S> (the host controller): part 2 compiles them, part 6 (trees that do
+// fit 64 KB, a general vc) calls part 2's instances
+#define XPG_MIP_SHARED(X_, S_) \
+    X_ template int mip_batch_device<S_>(xpg_ctx *, int, bool, bool, const S_ *, const S_ *, int, int, int32_t *, S_ *, S_ *, long long *, \
+                                         const uint8_t *, const S_ *, int, const int *, int); \
+    X_ template int mip_batch_vc_host<S_>(xpg_ctx *, int, int, bool, bool, const S_ *, const S_ *, const S_ *, int, const S_ *, int, int, \
+                                          const uint8_t *, int32_t *, S_ *, S_ *, long long *);
+#if XPG_PART == 6
+namespace xpg { XPG_MIP_SHARED(extern, F64) XPG_MIP_SHARED(extern, R32) }
+#elif XPG_PART == 2
+namespace xpg { XPG_MIP_SHARED(, F64) XPG_MIP_SHARED(, R32) }
 #endif
 
 // six_batch_vc_host<S> / six_batch_vc_dev<S> (k_six_batch_vc, six_solve): part 1 compiles them, part 5 (shapes that do fit
@@ -1520,6 +1537,54 @@ int xpg_test_six_batch_vc_hbm_plan(int kind, const void * vc, int vc_rows, int l
     }
     const long long f[10] = { g.route, g.nfree, g.Rmax, g.Vmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
     for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
+    return 0;
+}
+} // extern "C"
+#endif
+#if XPG_IN(6)
+extern "C" {
+// ---- MIP trees whose node LPs are beyond 64 KB of LDS: the whole walk by a workgroup per tree, node tableaux in device
+// ---- memory (mip_tree_hbm.hip.h) ----
+int xpg_mip_batch_vc_hbm_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg_rat32 * tgtf, const xpg_rat32 * vc,
+                               const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, const uint8_t * ind,
+                               int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol, long long * out_nodes)
+{
+    XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
+    return mip_batch_vc_hbm<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows,
+                                 (const R32 *)leq, leq_rows, cols, ind, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
+}
+int xpg_mip_batch_vc_hbm_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf, const double * vc,
+                             const double * eq, int eq_rows, const double * leq, int leq_rows, int cols, const uint8_t * ind,
+                             int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
+{
+    XPG_BIND(ctx);
+    mip_route() = MipRoute{0, 0, 0};
+    return mip_batch_vc_hbm<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows,
+                                 (const F64 *)leq, leq_rows, cols, ind, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
+}
+// which route the trees of the calling thread's last xpg_mip_batch_vc_hbm_* call took (mip_tree_hbm.hip.h MipHbmRoute)
+int xpg_mip_hbm_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const MipHbmRoute & r = mip_hbm_route();
+    const long long f[5] = { r.lds, r.hbm, r.host, r.free_vars, r.grid };
+    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test view: the route rule of xpg_mip_batch_vc_hbm_* and the sizes it decides by
+int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int cols, int is_bin, int is_max, int extra, int nb, int num_cus,
+                          long long * out, int n)
+{
+    if (!out || n < 0 || cols < 2 || leq_rows < 0 || eq_rows < 0 || (leq_rows == 0 && eq_rows == 0) || extra < 0 || extra > cols - 1 ||
+        nb <= 0 || num_cus <= 0 || (kind != 0 && kind != 1))
+        return XPG_ERR_SHAPE;
+    const int ex = pattern ? extra : 0;
+    const MipHbmPlan g = kind == 0 ? mip_hbm_plan<F64>(pattern != 0, leq_rows, eq_rows, cols, is_bin != 0, is_max != 0, ex, nb, num_cus)
+                                   : mip_hbm_plan<R32>(pattern != 0, leq_rows, eq_rows, cols, is_bin != 0, is_max != 0, ex, nb, num_cus);
+    const long long f[11] = { g.route, g.extra, g.R, g.V, (long long)g.lds, (long long)g.slot, g.ld, (long long)g.ws_words, g.threads, g.grid,
+                              (long long)g.scratch };
+    for (int k = 0; k < n && k < 11; k++) out[k] = f[k];
     return 0;
 }
 } // extern "C"

@@ -470,6 +470,61 @@ def mip_last_route():
     return dict(device_trees=int(out[0]), host_trees=int(out[1]), free_vars=int(out[2]))
 
 
+def mip_batch_vc_hbm(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, ind=None, kind=RAT):
+    """xpg_mip_batch_vc_hbm_*: mip_batch_vc for node LPs of any size. A sign-pattern vc and node LPs within 64 KB of LDS: the
+    launch mip_batch_vc makes; a sign-pattern vc past that: still one launch, a workgroup per tree with the node tableaux in
+    device memory; anything else by the host controller. Arrays as mip_batch_vc takes them (ind: the rational_indicator).
+    Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
+    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
+    leq = None if leq is None else as_kind(leq, kind, 3)
+    eq = None if eq is None else as_kind(eq, kind, 3)
+    nb, cols = tgtf.shape[0], tgtf.shape[1]
+    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
+        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
+    for a in (leq, eq):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq is None else leq.shape[1]
+    eq_rows = 0 if eq is None else eq.shape[1]
+    ind = None if ind is None else np.ascontiguousarray(ind, dtype=np.uint8)
+    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    nodes = C.c_longlong()
+    fn = lib().xpg_mip_batch_vc_hbm_rat32 if kind == RAT else lib().xpg_mip_batch_vc_hbm_f64
+    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(vc), vp(eq), C.c_int(eq_rows),
+                 vp(leq), C.c_int(rows), C.c_int(cols), vp(ind), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch_vc_hbm")
+    return st, v, sol, nodes.value
+
+
+def mip_hbm_last_route():
+    """{'lds', 'hbm', 'host', 'free', 'grid'}: trees of this thread's last mip_batch_vc_hbm call on the LDS-resident walk / on
+    the device-memory walk / on the host controller, the free variables split per tree, and the grid of its launch."""
+    out = (C.c_longlong * 5)()
+    rc = lib().xpg_mip_hbm_last_route(out, C.c_int(5))
+    if rc != 0:
+        raise XpgError("xpg_mip_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
+    return {"lds": out[0], "hbm": out[1], "host": out[2], "free": out[3], "grid": out[4]}
+
+
+MIP_HBM_FIELDS = ("route", "free", "R", "V", "lds", "slot", "ld", "ws_words", "threads", "grid", "scratch")
+
+
+def mip_hbm_plan(kind, vc, leq_rows, eq_rows, cols, is_bin, is_max, nb, num_cus=256):
+    """xpg_test_mip_hbm_plan (host only, no device): what mip_batch_vc_hbm does with nb trees of a shape under vc
+    [cols - 1, cols(,2)] -- route (0 LDS-resident walk, 1 device-memory walk, 2 host controller), free variables, the rows and
+    variables the largest node LP is solved with, LDS bytes, slot bytes, ld, workspace words, threads, grid, scratch bytes."""
+    vc_a = as_kind(vc, kind, 2)
+    free = np.zeros(cols - 1, dtype=np.uint8)
+    pat = lib().xpg_test_vc_pattern(C.c_int(kind), vp(vc_a), C.c_int(vc_a.shape[0]), C.c_int(cols), vp(free))
+    if pat < 0:
+        raise XpgError("xpg_test_vc_pattern: %s" % _capi.ERRORS.get(pat, pat))
+    out = (C.c_longlong * 11)()
+    rc = lib().xpg_test_mip_hbm_plan(C.c_int(kind), C.c_int(pat), C.c_int(leq_rows), C.c_int(eq_rows), C.c_int(cols), C.c_int(int(is_bin)),
+                                     C.c_int(int(is_max)), C.c_int(int(free.sum())), C.c_int(nb), C.c_int(num_cus), out, C.c_int(11))
+    if rc != 0:
+        raise XpgError("xpg_test_mip_hbm_plan: %s" % _capi.ERRORS.get(rc, rc))
+    return dict(zip(MIP_HBM_FIELDS, (int(x) for x in out)))
+
+
 def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF):
     """SIX::maxm / minm for nb problems of one shape WITH equalities and free variables in one call (xpg_six_batch_vc_*):
     tgtf [nb, cols(,2)], vc [cols - 1, cols(,2)] shared by the batch, leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)]
