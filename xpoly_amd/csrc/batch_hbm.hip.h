@@ -72,6 +72,47 @@ template <class S> __device__ __forceinline__ void hbm_carve(Small<S> & P, unsig
     P.ld = ld;
 }
 
+// Address spaces of the pointers that cross a __noinline__ call boundary (six_batch_vc_hbm.hip.h, mip_tree_hbm.hip.h): behind
+// it the side arrays stay ds_* and the tableau global_* accesses (through generic pointers both became flat_*).
+#define XPG_AS_LDS __attribute__((address_space(3)))
+#define XPG_AS_GLOBAL __attribute__((address_space(1)))
+
+// The rules every route on a tableau in device memory shares (k_batch_hbm, k_six_batch_vc_hbm, k_mip_tree_hbm).
+// ld: the widest live width (V + R + 2) rounded up to an even number of cells; a tableau slot starts on a 256-byte line.
+inline size_t hbm_ld(int R, int V) { return ((size_t)V + (size_t)R + 2 + 1) & ~(size_t)1; }
+inline size_t hbm_slot_bytes(int R, size_t ld) { return ((size_t)R * ld * 8 + 255) & ~(size_t)255; }
+// The grid: workgroups per CU by the wavefronts resident there, cut by what 160 KB of LDS hold (lds: dynamic plus static
+// bytes of one workgroup), at least one; times the CUs, cut by the workgroups whose scratch (each bytes) fits
+// scratch_max and by nb, at least one.
+inline long long hbm_grid(int num_cus, int threads, int waves_per_cu, size_t lds, size_t each, size_t scratch_max, int nb)
+{
+    long long per_cu = waves_per_cu * 64 / threads;
+    const long long by_lds = (long long)(((size_t)160 * 1024) / lds);
+    if (per_cu > by_lds) per_cu = by_lds;
+    if (per_cu < 1) per_cu = 1;
+    long long grid = (long long)num_cus * per_cu;
+    const long long by_scratch = (long long)(scratch_max / each);
+    if (grid > by_scratch) grid = by_scratch;
+    if (grid > nb) grid = nb;
+    if (grid < 1) grid = 1;
+    return grid;
+}
+// What the code object of `kernel` really holds in static LDS against the figure its plan counted: a __shared__ array
+// added anywhere below the kernel is a clean error before the launch, not a plan that over-admits at the 160 KB edge.
+inline int hbm_static_lds_check(xpg_ctx * ctx, const void * kernel, size_t counted, const char * what)
+{
+    static std::mutex mu;
+    static std::map<const void *, size_t> held;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = held.find(kernel);
+    if (it == held.end()) {
+        hipFuncAttributes fa;
+        it = held.emplace(kernel, hipFuncGetAttributes(&fa, kernel) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)0).first;
+    }
+    if (it->second > counted) { ctx->err = what; return XPG_ERR_UNSUPPORTED; }
+    return 0;
+}
+
 // THE rule (the launch and xpg_test_batch_hbm_geometry both ask it): an LP that fits one CU's LDS takes k_batch exactly as
 // xpg_six_batch_* launches it; otherwise k_batch_hbm, as long as the side arrays fit 160 KB beside the kernel's static LDS
 // and one slot fits the scratch cap; anything else is refused before any launch.
@@ -90,9 +131,9 @@ template <class S> inline HbmGeom batch_hbm_geometry(int R, int V, int nb, int n
         g.route = HBM_ROUTE_LDS; g.lds = b.lds; g.slot = 0; g.ld = V + R + 2; g.threads = b.threads; g.grid = b.grid; g.scratch = 0;
         return g;
     }
-    const size_t ld = ((size_t)V + (size_t)R + 2 + 1) & ~(size_t)1;
+    const size_t ld = hbm_ld(R, V);
     g.lds = hbm_side_bytes<S>(R, V);
-    g.slot = ((size_t)R * ld * 8 + 255) & ~(size_t)255;
+    g.slot = hbm_slot_bytes(R, ld);
     g.ld = (int)ld;
     g.threads = threads > 0 ? threads : BATCH_HBM_THREADS;
     if (g.lds + SMALL_LDS_STATIC > (size_t)160 * 1024 || g.slot > BATCH_HBM_SCRATCH_MAX) {
@@ -100,17 +141,9 @@ template <class S> inline HbmGeom batch_hbm_geometry(int R, int V, int nb, int n
         return g;
     }
     g.route = HBM_ROUTE_HBM;
-    long long per_cu = (waves_per_cu > 0 ? waves_per_cu : BATCH_HBM_WAVES_PER_CU) * 64 / g.threads;
-    const long long by_lds = (long long)(((size_t)160 * 1024) / (g.lds + SMALL_LDS_STATIC));
-    if (per_cu > by_lds) per_cu = by_lds;
-    if (per_cu < 1) per_cu = 1;
-    long long grid = (long long)num_cus * per_cu;
-    const long long by_scratch = (long long)(BATCH_HBM_SCRATCH_MAX / g.slot);
-    if (grid > by_scratch) grid = by_scratch;
-    if (grid > nb) grid = nb;
-    if (grid < 1) grid = 1;
-    g.grid = (int)grid;
-    g.scratch = (size_t)grid * g.slot;
+    g.grid = (int)hbm_grid(num_cus, g.threads, waves_per_cu > 0 ? waves_per_cu : BATCH_HBM_WAVES_PER_CU, g.lds + SMALL_LDS_STATIC, g.slot,
+                           BATCH_HBM_SCRATCH_MAX, nb);
+    g.scratch = (size_t)g.grid * g.slot;
     return g;
 }
 
@@ -227,14 +260,12 @@ int batch_hbm_dev(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * l
         return rc;
     }
     if (grid_cap > 0 && g.grid > grid_cap) { g.grid = grid_cap; g.scratch = (size_t)g.grid * g.slot; }
-    if (g.scratch > ctx->batch_hbm_cap) {
-        if (ctx->batch_hbm_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->batch_hbm_buf); ctx->batch_hbm_buf = nullptr; ctx->batch_hbm_cap = 0; }
-        if (hipMalloc(&ctx->batch_hbm_buf, g.scratch) != hipSuccess) { ctx->batch_hbm_buf = nullptr; (void)hipGetLastError(); ctx->err = "hipMalloc(six_batch_hbm scratch)"; return XPG_ERR_ALLOC; }
-        ctx->batch_hbm_cap = g.scratch;
-    }
+    Scratch & slots = ctx->scratch[SCRATCH_BATCH_HBM];
+    if (const int rc = scratch_reserve(ctx, slots, g.scratch, g.scratch, "hipMalloc(six_batch_hbm scratch)")) return rc;
+    if (const int rc = hbm_static_lds_check(ctx, (const void *)k_batch_hbm<S>, SMALL_LDS_STATIC, "k_batch_hbm: static LDS above SMALL_LDS_STATIC")) return rc;
     XPG_HIP(ctx, lds_limit((const void *)k_batch_hbm<S>, ctx->device, g.lds));
     hipLaunchKernelGGL((k_batch_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, tgtf, leq, m, cols,
-                       is_max ? 1 : 0, max_iter, (unsigned long long *)ctx->batch_hbm_buf, (unsigned long long)(g.slot / 8), g.ld,
+                       is_max ? 1 : 0, max_iter, (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), g.ld,
                        out_status, out_v, out_sol, out_pivots);
     XPG_HIP(ctx, hipGetLastError());
     rt = BatchHbmRoute{0, nb, g.grid};
@@ -260,24 +291,12 @@ int batch_hbm_host(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * 
         if (rc == 0) rt = BatchHbmRoute{nb, 0, g.grid};
         return rc;
     }
-    const size_t bl = (size_t)nb * m * cols * 8, bt = (size_t)nb * cols * 8;
-    DevBuf dl, dt, dst, dv, ds;
-    XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8));
-    XPG_TRY(ds.alloc(ctx, bt));
-    XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = batch_hbm_dev<S>(ctx, is_max, nb, (const S *)dt.p, (const S *)dl.p, m, cols, max_iter, (int32_t *)dst.p, (S *)dv.p, (S *)ds.p, nullptr);
+    BatchIo io;
+    if (const int rc = io.up(ctx, nb, tgtf, nullptr, nullptr, 0, leq, m, cols)) return rc;
+    const int rc = batch_hbm_dev<S>(ctx, is_max, nb, (const S *)io.dt.p, (const S *)io.dl.p, m, cols, max_iter, (int32_t *)io.dst.p, (S *)io.dv.p,
+                                    (S *)io.ds.p, nullptr);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    std::vector<int32_t> st((size_t)nb);
-    std::vector<S> v((size_t)nb), sol((size_t)nb * cols);
-    XPG_TRY(hipMemcpyAsync(st.data(), dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(v.data(), dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(sol.data(), ds.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(out_status, st.data(), (size_t)nb * 4); memcpy(out_v, v.data(), (size_t)nb * 8);
-    for (int b = 0; b < nb; b++)                                 // (out_sol is written on success only, include/xpoly_amd.h)
-        if (st[(size_t)b] == 0) memcpy(out_sol + (size_t)b * cols, sol.data() + (size_t)b * cols, (size_t)cols * 8);
-    return 0;
+    return io.down(ctx, nb, cols, out_status, out_v, out_sol);
 }
 
 } // namespace xpg

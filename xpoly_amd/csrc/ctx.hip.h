@@ -14,7 +14,19 @@
 #include <string.h>
 #include "../../include/xpoly_amd.h"
 
-namespace xpg { struct LoopState; }
+namespace xpg {
+struct LoopState;
+// A grow-only scratch area in device memory that a handle keeps between calls (scratch_reserve below; xpg_trim and
+// xpg_destroy return every one of them).
+struct Scratch {
+    void * buf = 0; size_t cap = 0;
+    void release() { if (buf) { (void)hipFree(buf); buf = 0; cap = 0; } }
+};
+enum { SCRATCH_SIX_VC,       // k_six_batch_vc's scratch slots, one per workgroup
+       SCRATCH_BATCH_HBM,    // k_batch_hbm's and k_mip_tree_hbm's tableau slots, one per workgroup
+       SCRATCH_SIX_VC_HBM,   // k_six_batch_vc_hbm's slots, one per workgroup
+       SCRATCH_COUNT };
+}
 
 struct xpg_ctx {
     int device;
@@ -30,9 +42,7 @@ struct xpg_ctx {
     std::vector<std::pair<void *, size_t> > dev_cache;   // device blocks between host-array row-elimination calls (DevBuf)
     size_t dev_cache_bytes = 0;
     void * slice_buf = 0; size_t slice_cap = 0;   // k_batch's time slices: checkpoints, queue and counters (grow-only)
-    void * six_vc_buf = 0; size_t six_vc_cap = 0; // k_six_batch_vc's scratch slots, one per workgroup (grow-only; xpg_trim returns them)
-    void * batch_hbm_buf = 0; size_t batch_hbm_cap = 0;   // k_batch_hbm's tableau slots, one per workgroup (grow-only; xpg_trim returns them)
-    void * six_vc_hbm_buf = 0; size_t six_vc_hbm_cap = 0; // k_six_batch_vc_hbm's slots, one per workgroup (grow-only; xpg_trim returns them)
+    xpg::Scratch scratch[xpg::SCRATCH_COUNT];     // the per-workgroup slots of the batch kernels (SCRATCH_*)
     int loop_mode;          // XPG_LOOP: 0 the pipelined loop (2 launches per pivot), 3 the blocked loop (xpg_lp_loop_info's codes)
     int block_len;          // blocked loop: pivots staged per sweep, 1..BLK_MAX
     int loop_auto;          // XPG_LOOP unset: blocked loop where the sweep is what costs (large fp64 tableaux)
@@ -173,5 +183,51 @@ inline LineqGeom lineq_geom(int nb, int width, size_t sys_lds)
 }
 
 #define XPG_TRY(e_) do { hipError_t err_ = (e_); if (err_ != hipSuccess) { ctx->err = std::string(#e_) + ": " + hipGetErrorString(err_); return XPG_ERR_HIP; } } while (0)
+
+// s holds at least `need` bytes afterwards. An area that has to grow waits for the stream first (a launch may still use
+// it) and is allocated `alloc` >= need bytes; failure: XPG_ERR_ALLOC with `what` as the handle's error, the area empty.
+inline int scratch_reserve(xpg_ctx * ctx, Scratch & s, size_t need, size_t alloc, const char * what)
+{
+    if (need <= s.cap) return 0;
+    if (s.buf) { (void)hipStreamSynchronize(ctx->stream); s.release(); }
+    if (hipMalloc(&s.buf, alloc) != hipSuccess) { s.buf = 0; (void)hipGetLastError(); ctx->err = what; return XPG_ERR_ALLOC; }
+    s.cap = alloc;
+    return 0;
+}
+
+// The device side of a host-array batch call of 8-byte cells: tgtf [nb x cols], leq [nb x leq_rows x cols], with vc
+// [(cols - 1) x cols] and eqs [nb x eq_rows x cols] where the call has them (vc = NULL: neither), and status, v and sol.
+struct BatchIo {
+    DevBuf dt, dvc, de, dl, dst, dv, ds;
+    int up(xpg_ctx * ctx, int nb, const void * tgtf, const void * vc, const void * eqs, int eq_rows, const void * leq, int leq_rows, int cols)
+    {
+        const size_t bt = (size_t)nb * cols * 8, bv = (size_t)(cols - 1) * cols * 8, be = (size_t)nb * eq_rows * cols * 8,
+                     bl = (size_t)nb * leq_rows * cols * 8;
+        XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dl.alloc(ctx, bl));
+        if (vc) { XPG_TRY(dvc.alloc(ctx, bv)); XPG_TRY(de.alloc(ctx, be)); }
+        XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(ds.alloc(ctx, bt));
+        XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
+        if (vc) XPG_TRY(hipMemcpyAsync(dvc.p, vc, bv, hipMemcpyHostToDevice, ctx->stream));
+        if (eq_rows > 0) XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
+        if (leq_rows > 0) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    }
+    // Synchronises. Everything is staged on the host first, so a HIP call that fails leaves the caller's arrays untouched;
+    // out_sol is written on success only (include/xpoly_amd.h).
+    int down(xpg_ctx * ctx, int nb, int cols, int32_t * out_status, void * out_v, void * out_sol)
+    {
+        const size_t row = (size_t)cols * 8;
+        std::vector<int32_t> st((size_t)nb);
+        std::vector<unsigned char> v((size_t)nb * 8), sol((size_t)nb * row);
+        XPG_TRY(hipMemcpyAsync(st.data(), dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(v.data(), dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(sol.data(), ds.p, (size_t)nb * row, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        memcpy(out_status, st.data(), (size_t)nb * 4); memcpy(out_v, v.data(), (size_t)nb * 8);
+        for (int b = 0; b < nb; b++)
+            if (st[(size_t)b] == 0) memcpy((unsigned char *)out_sol + (size_t)b * row, sol.data() + (size_t)b * row, row);
+        return 0;
+    }
+};
 
 } // namespace xpg

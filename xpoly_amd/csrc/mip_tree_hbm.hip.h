@@ -7,8 +7,8 @@
 //            loop without its helper workgroups, ragged rows, active marks and time slices.
 //   solve    sm_solve_lp<S, true> on the node mip_build_node left in the workspace (raw solution into w.y), nf_unsplit after
 //            it with free variables: the tableau tab[R][ld] lies in the WORKGROUP's slot in global memory (maximising R =
-//            rmax, V = cols - 1 + extra, minimising the two swap; ld and the 256-byte slot alignment by batch_hbm_geometry's
-//            rule), the side arrays in LDS under hbm_carve, carved for the largest node of the deepest path.
+//            rmax, V = cols - 1 + extra, minimising the two swap; ld and the 256-byte slot alignment by hbm_ld and
+//            hbm_slot_bytes), the side arrays in LDS under hbm_carve, carved for the largest node of the deepest path.
 // A workgroup reads and writes its own slot and its own workspace alone: __syncthreads() is the only ordering. A slot is
 // rewritten by every node (sm_build writes every live cell before anything reads it) and the workspace fields
 // MipTask::start sets by every tree, so a workgroup takes tree after tree. Status, optimum, solution and node count are bit
@@ -26,8 +26,8 @@ inline MipHbmRoute & mip_hbm_route() { static thread_local MipHbmRoute r = {0, 0
 enum { MIP_HBM_ROUTE_LDS = 0, MIP_HBM_ROUTE_HBM = 1, MIP_HBM_ROUTE_HOST = 2 };
 // What k_mip_tree_hbm holds in LDS besides hbm_carve's arrays (the code object's group_segment_fixed_size): the reduction
 // scratch of the solver's inlined helpers (256 bytes), mip_build_node's sh_left[MIP_EQ_MAX] and sh_nf[4] (528), the walk's
-// sh_ctl[2] and the node's objective scratch (8 + 8). The launch holds the figure against the code object's (mip_hbm_launch): a
-// __shared__ array added anywhere below the kernel is a clean error there, not a plan that over-admits at the 160 KB edge.
+// sh_ctl[2] and the node's objective scratch (8 + 8). The launch holds the figure against the code object's
+// (hbm_static_lds_check).
 enum { MIP_HBM_LDS_STATIC = 256 + 2 * MIP_EQ_MAX + 16 + 16 };
 enum { MIP_HBM_THREADS = BATCH_HBM_THREADS, MIP_HBM_WAVES_PER_CU = BATCH_HBM_WAVES_PER_CU };
 
@@ -60,10 +60,10 @@ inline MipHbmPlan mip_hbm_plan(bool pattern, int leq_rows, int eq_rows, int cols
         g.scratch = (size_t)q.grid * g.ws_words * 8;
         return g;
     }
-    const size_t ld = ((size_t)g.V + (size_t)g.R + 2 + 1) & ~(size_t)1;
+    const size_t ld = hbm_ld(g.R, g.V);
     g.lds = rmax > 0 ? hbm_side_bytes<S>(g.R, g.V) : 0;
     g.ld = (int)ld;
-    g.slot = ((size_t)(g.R > 0 ? g.R : 0) * ld * 8 + 255) & ~(size_t)255;
+    g.slot = hbm_slot_bytes(g.R > 0 ? g.R : 0, ld);
     g.threads = MIP_HBM_THREADS;
     if (!pattern || rmax <= 0 || extra < 0 || extra > n0 || eq_rows + n0 + 2 > MIP_EQ_MAX ||
         g.lds + MIP_HBM_LDS_STATIC > (size_t)160 * 1024 || g.slot > BATCH_HBM_SCRATCH_MAX) {
@@ -71,18 +71,9 @@ inline MipHbmPlan mip_hbm_plan(bool pattern, int leq_rows, int eq_rows, int cols
         return g;
     }
     g.route = MIP_HBM_ROUTE_HBM;
-    long long per_cu = MIP_HBM_WAVES_PER_CU * 64 / g.threads;
-    const long long by_lds = (long long)(((size_t)160 * 1024) / (g.lds + MIP_HBM_LDS_STATIC));
-    if (per_cu > by_lds) per_cu = by_lds;
-    if (per_cu < 1) per_cu = 1;
-    long long grid = (long long)num_cus * per_cu;
     const size_t each = g.slot + g.ws_words * 8;
-    const long long by_scratch = (long long)(BATCH_HBM_SCRATCH_MAX / each);
-    if (grid > by_scratch) grid = by_scratch;
-    if (grid > nb) grid = nb;
-    if (grid < 1) grid = 1;
-    g.grid = (int)grid;
-    g.scratch = (size_t)grid * each;
+    g.grid = (int)hbm_grid(num_cus, g.threads, MIP_HBM_WAVES_PER_CU, g.lds + MIP_HBM_LDS_STATIC, each, BATCH_HBM_SCRATCH_MAX, nb);
+    g.scratch = (size_t)g.grid * each;
     return g;
 }
 
@@ -91,10 +82,6 @@ inline MipHbmPlan mip_hbm_plan(bool pattern, int leq_rows, int eq_rows, int cols
 // address-space-3 pointers, the slot and the workspace's arrays as address-space-1 ones, so behind the call boundary the side
 // arrays stay ds_* and the tableau global_* accesses; scalars by value, the status by value. (R, V): the largest node's, which
 // the LDS block was sized for -- every node carves the same arrays, as k_mip_tree's one sm_carve does.
-#ifndef XPG_AS_LDS
-#define XPG_AS_LDS __attribute__((address_space(3)))
-#define XPG_AS_GLOBAL __attribute__((address_space(1)))
-#endif
 template <class S> __device__ __noinline__ int mip_hbm_solve_node(XPG_AS_LDS unsigned char * lds, XPG_AS_GLOBAL S * tab, int R, int V, int ld,
                                                                   XPG_AS_GLOBAL const S * node, XPG_AS_GLOBAL const S * obj, int rows, int ncols,
                                                                   int is_max, XPG_AS_GLOBAL S * y, XPG_AS_LDS S * v_scratch)
@@ -176,11 +163,8 @@ int mip_hbm_launch(xpg_ctx * ctx, const MipHbmPlan & g, int nb, bool is_max, boo
 {
     const int n0 = cols - 1, rmax = mip_rmax(leq_rows, eq_rows, n0, is_bin), depth = n0 + 2;
     const size_t slots_bytes = (size_t)g.grid * g.slot;
-    if (slots_bytes > ctx->batch_hbm_cap) {
-        if (ctx->batch_hbm_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->batch_hbm_buf); ctx->batch_hbm_buf = nullptr; ctx->batch_hbm_cap = 0; }
-        if (hipMalloc(&ctx->batch_hbm_buf, slots_bytes) != hipSuccess) { ctx->batch_hbm_buf = nullptr; (void)hipGetLastError(); ctx->err = "hipMalloc(mip_batch_vc_hbm scratch)"; return XPG_ERR_ALLOC; }
-        ctx->batch_hbm_cap = slots_bytes;
-    }
+    Scratch & slots = ctx->scratch[SCRATCH_BATCH_HBM];
+    if (const int rc = scratch_reserve(ctx, slots, slots_bytes, slots_bytes, "hipMalloc(mip_batch_vc_hbm scratch)")) return rc;
     const size_t bl = (size_t)nb * leq_rows * cols * 8, bt = (size_t)nb * cols * 8, be = (size_t)nb * eq_rows * cols * 8;
     DevBuf dfv, dl, dt, dws, dst, dv, dsol, dn, dal, de;
     if (extra > 0) {
@@ -201,15 +185,12 @@ int mip_hbm_launch(xpg_ctx * ctx, const MipHbmPlan & g, int nb, bool is_max, boo
     if (bl) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
     XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
     if (out_sol) XPG_TRY(hipMemcpyAsync(dsol.p, out_sol, bt, hipMemcpyHostToDevice, ctx->stream));
-    static const size_t static_lds = [] {                        // what the code object really holds: the plan counted MIP_HBM_LDS_STATIC
-        hipFuncAttributes fa;
-        return hipFuncGetAttributes(&fa, (const void *)k_mip_tree_hbm<S>) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)0;
-    }();
-    if (static_lds > (size_t)MIP_HBM_LDS_STATIC) { ctx->err = "k_mip_tree_hbm: static LDS above MIP_HBM_LDS_STATIC"; return XPG_ERR_UNSUPPORTED; }
+    if (const int rc = hbm_static_lds_check(ctx, (const void *)k_mip_tree_hbm<S>, MIP_HBM_LDS_STATIC, "k_mip_tree_hbm: static LDS above MIP_HBM_LDS_STATIC"))
+        return rc;
     XPG_TRY(lds_limit((const void *)k_mip_tree_hbm<S>, ctx->device, g.lds));
     hipLaunchKernelGGL((k_mip_tree_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, (const S *)dt.p,
                        (const S *)dl.p, leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)dws.p, g.ws_words,
-                       (unsigned long long *)ctx->batch_hbm_buf, (unsigned long long)(g.slot / 8), g.ld, (int32_t *)dst.p, (S *)dv.p,
+                       (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), g.ld, (int32_t *)dst.p, (S *)dv.p,
                        out_sol ? (S *)dsol.p : (S *)0, (int *)dn.p, allow_rational ? (const uint8_t *)dal.p : (const uint8_t *)0,
                        eq_rows > 0 ? (const S *)de.p : (const S *)0, eq_rows, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
     XPG_TRY(hipGetLastError());

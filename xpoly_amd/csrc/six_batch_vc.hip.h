@@ -66,24 +66,21 @@ __host__ __device__ inline SixVcSlot six_vc_slot(int leq_rows, int eq_rows, int 
     return s;
 }
 
-// One workgroup per LP, grid-stride over the batch. vc is read on the device (the _dev entry points hold it there): every
-// workgroup derives the free list once; a vc that is no sign pattern, or a normal form beyond the launch's LDS, ends
-// every LP XPG_ERR_UNSUPPORTED (the host-array entry point has sent such a batch to six_solve instead and never launches).
-template <class S> __global__ __launch_bounds__(256, 4)
-void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ vc, const S * __restrict__ eqs, int eq_rows,
-                    const S * __restrict__ leq, int leq_rows, int cols, int is_max, unsigned max_iter, unsigned lds_bytes,
-                    unsigned long long * __restrict__ slots, unsigned long long slot_cells,
-                    int32_t * __restrict__ out_status, S * __restrict__ out_v, S * __restrict__ out_sol)
+// What every xpg_six_batch_vc_* and xpg_six_batch_vc_hbm_* entry point asks of its arguments.
+inline bool six_vc_args_ok(const xpg_ctx * ctx, int nb, const void * tgtf, const void * vc, const void * eqs, int eq_rows,
+                           const void * leq, int leq_rows, int cols, const void * out_status, const void * out_v, const void * out_sol)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
-    const int n0 = cols - 1;
-    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
-    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
-    const S m1 = minus_one<S>();
+    return ctx && nb >= 0 && tgtf && vc && cols >= 2 && eq_rows >= 0 && leq_rows >= 0 && !(eq_rows == 0 && leq_rows == 0) &&
+           !(eq_rows > 0 && !eqs) && !(leq_rows > 0 && !leq) && out_status && out_v && out_sol;
+}
 
-    // ---- vc: sign pattern? which variables are free (lpsol.h:1321-1339: a column of vc without a nonzero) ----
+// vc on the device (k_six_batch_vc, k_six_batch_vc_hbm), by all threads: is it a sign pattern, and which variables are free
+// (lpsol.h:1321-1339: a column of vc without a nonzero). Returns whether vc is general, i.e. no sign pattern; behind its
+// barrier fv holds the free variables, ascending, and hdr[0] their number.
+template <class S> __device__ __forceinline__ bool vc_scan(const S * __restrict__ vc, int n0, int cols, int * fv, int * hdr)
+{
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
+    const S m1 = minus_one<S>();
     bool bad = false;
     for (int t = tid; t < n0 * cols; t += nt) {
         const int i = t / cols, j = t - i * cols;
@@ -102,7 +99,41 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
         }
         if (tid == 0) hdr[0] = cnt;
     }
-    const bool general = __syncthreads_or(bad ? 1 : 0) != 0;     // (a barrier: hdr[0] and fv are the workgroup's now)
+    return __syncthreads_or(bad ? 1 : 0) != 0;                   // (a barrier: hdr[0] and fv are the workgroup's now)
+}
+
+// calcFinalSolution behind a solve that ended 0, by all threads: the split undone in y, the products with the ORIGINAL tgtf
+// into prod, the reduced solution into out_sol; their sum in column order, v and status 0 by thread 0.
+template <class S> __device__ __forceinline__ void vc_finish(S * y, const S * tg, int cols, const int * fv, int nfree, S * prod, S * out_sol,
+                                                             S * out_v, int32_t * out_status)
+{
+    nf_unsplit<S>(y, cols, fv, nfree);
+    nf_products<S>(y, tg, cols, prod, out_sol);
+    if (threadIdx.x == 0) {
+        S v = zero<S>();
+        for (int j = 0; j < cols; j++) v = add(v, prod[j]);
+        reduce(v);
+        *out_v = v;
+        *out_status = 0;
+    }
+}
+
+// One workgroup per LP, grid-stride over the batch. vc is read on the device (the _dev entry points hold it there): every
+// workgroup derives the free list once; a vc that is no sign pattern, or a normal form beyond the launch's LDS, ends
+// every LP XPG_ERR_UNSUPPORTED (the host-array entry point has sent such a batch to six_solve instead and never launches).
+template <class S> __global__ __launch_bounds__(256, 4)
+void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ vc, const S * __restrict__ eqs, int eq_rows,
+                    const S * __restrict__ leq, int leq_rows, int cols, int is_max, unsigned max_iter, unsigned lds_bytes,
+                    unsigned long long * __restrict__ slots, unsigned long long slot_cells,
+                    int32_t * __restrict__ out_status, S * __restrict__ out_v, S * __restrict__ out_sol)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    const int n0 = cols - 1;
+    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
+    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
+    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
     const int nfree = hdr[0], n = n0 + nfree;
     const SixVcPlan plan = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, is_max != 0);
     const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree);
@@ -145,17 +176,8 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
             if (tid == 0) { out_status[lp] = status; out_v[lp] = zero<S>(); }
             continue;
         }
-        // ---- finish (calcFinalSolution): the products into obj, which has done its work; their sum in column order
-        nf_unsplit<S>(y, cols, fv, nfree);
-        S * const prod = obj;
-        nf_products<S>(y, tg, cols, prod, out_sol + (size_t)lp * cols);
-        if (tid == 0) {
-            S v = zero<S>();
-            for (int j = 0; j < cols; j++) v = add(v, prod[j]);
-            reduce(v);
-            out_v[lp] = v;
-            out_status[lp] = 0;
-        }
+        // ---- finish (calcFinalSolution): the products into obj, which has done its work
+        vc_finish<S>(y, tg, cols, fv, nfree, obj, out_sol + (size_t)lp * cols, out_v + lp, out_status + lp);
     }
 }
 
@@ -188,9 +210,7 @@ template <class S>
 int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S * vc, const S * eqs, int eq_rows, const S * leq,
                      int leq_rows, int cols, unsigned max_iter, int nfree, int32_t * out_status, S * out_v, S * out_sol)
 {
-    if (!ctx || nb < 0 || !tgtf || !vc || cols < 2 || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) ||
-        (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq) || !out_status || !out_v || !out_sol)
-        return XPG_ERR_SHAPE;
+    if (!six_vc_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     const SixVcPlan least = six_vc_plan<S>(true, nfree >= 0 ? nfree : 0, leq_rows, eq_rows, cols, is_max);
     if (!least.device) return XPG_ERR_UNSUPPORTED;               // (no vc makes this shape fit)
@@ -201,15 +221,12 @@ int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S
     static const int grid_cap = [] { const char * e = xpg_hook("XPG_SIX_VC_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
     if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
     const size_t need = (size_t)grid * q.slot_cells * 8;
-    if (need > ctx->six_vc_cap) {
-        if (ctx->six_vc_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = nullptr; ctx->six_vc_cap = 0; }
-        const size_t cap = need + need / 2 < SIX_VC_SCRATCH_MAX ? need + need / 2 : need;
-        if (hipMalloc(&ctx->six_vc_buf, cap) != hipSuccess) { ctx->six_vc_buf = nullptr; (void)hipGetLastError(); ctx->err = "hipMalloc(six_batch_vc scratch)"; return XPG_ERR_ALLOC; }
-        ctx->six_vc_cap = cap;
-    }
+    Scratch & slots = ctx->scratch[SCRATCH_SIX_VC];              // grown with head room, so a batch a little larger does not grow it again
+    if (const int rc = scratch_reserve(ctx, slots, need, need + need / 2 < SIX_VC_SCRATCH_MAX ? need + need / 2 : need, "hipMalloc(six_batch_vc scratch)"))
+        return rc;
     XPG_HIP(ctx, lds_limit((const void *)k_six_batch_vc<S>, ctx->device, lds));
     hipLaunchKernelGGL((k_six_batch_vc<S>), dim3((unsigned)grid), dim3(threads), lds, ctx->stream, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows,
-                       cols, is_max ? 1 : 0, max_iter, (unsigned)lds, (unsigned long long *)ctx->six_vc_buf, (unsigned long long)q.slot_cells,
+                       cols, is_max ? 1 : 0, max_iter, (unsigned)lds, (unsigned long long *)slots.buf, (unsigned long long)q.slot_cells,
                        out_status, out_v, out_sol);
     XPG_HIP(ctx, hipGetLastError());
     return 0;
@@ -221,9 +238,7 @@ template <class S>
 int six_batch_vc_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S * tgtf, const S * vc, const S * eqs, int eq_rows, const S * leq,
                       int leq_rows, int cols, unsigned max_iter, int32_t * out_status, S * out_v, S * out_sol)
 {
-    if (!ctx || nb < 0 || !tgtf || !vc || cols < 2 || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) ||
-        (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq) || !out_status || !out_v || !out_sol)
-        return XPG_ERR_SHAPE;
+    if (!six_vc_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
     SixVcRoute & rt = six_vc_route();
     rt = SixVcRoute{0, 0, 0};
     if (nb == 0) return 0;
@@ -243,25 +258,14 @@ int six_batch_vc_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S * tg
         }
         return 0;
     }
-    const size_t bt = (size_t)nb * cols * 8, bv = (size_t)(cols - 1) * cols * 8, be = (size_t)nb * eq_rows * cols * 8,
-                 bl = (size_t)nb * leq_rows * cols * 8;
-    DevBuf dt, dvc, de, dl, dst, dv, ds;
-    XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dvc.alloc(ctx, bv)); XPG_TRY(de.alloc(ctx, be)); XPG_TRY(dl.alloc(ctx, bl));
-    XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(ds.alloc(ctx, bt));
-    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(dvc.p, vc, bv, hipMemcpyHostToDevice, ctx->stream));
-    if (eq_rows > 0) XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
-    if (leq_rows > 0) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = six_batch_vc_dev<S>(ctx, is_max, nb, (const S *)dt.p, (const S *)dvc.p, (const S *)de.p, eq_rows, (const S *)dl.p, leq_rows, cols,
-                                       max_iter, plan.nfree, (int32_t *)dst.p, (S *)dv.p, (S *)ds.p);
+    BatchIo io;
+    int rc = io.up(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols);
+    if (rc) return rc;
+    rc = six_batch_vc_dev<S>(ctx, is_max, nb, (const S *)io.dt.p, (const S *)io.dvc.p, (const S *)io.de.p, eq_rows, (const S *)io.dl.p, leq_rows, cols,
+                             max_iter, plan.nfree, (int32_t *)io.dst.p, (S *)io.dv.p, (S *)io.ds.p);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    std::vector<S> sol((size_t)nb * cols);
-    XPG_TRY(hipMemcpyAsync(out_status, dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(out_v, dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(sol.data(), ds.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < nb; b++)                                 // (out_sol is written on success only, include/xpoly_amd.h)
-        if (out_status[b] == 0) memcpy(out_sol + (size_t)b * cols, sol.data() + (size_t)b * cols, (size_t)cols * 8);
+    rc = io.down(ctx, nb, cols, out_status, out_v, out_sol);
+    if (rc) return rc;
     rt.device = nb; rt.free_vars = plan.nfree;
     return 0;
 }

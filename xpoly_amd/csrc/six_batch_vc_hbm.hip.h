@@ -83,7 +83,7 @@ inline SixVcHbmPlan six_vc_hbm_plan(bool pattern, int nfree, int leq_rows, int e
         g.threads = q.threads; g.grid = (int)q.grid; g.scratch = (size_t)q.grid * g.slot;
         return g;
     }
-    const size_t ld = ((size_t)g.Vmax + (size_t)g.Rmax + 2 + 1) & ~(size_t)1;
+    const size_t ld = hbm_ld(g.Rmax, g.Vmax);
     g.lds = hbm_side_bytes<S>(g.Rmax, g.Vmax);
     g.ld = (int)ld;
     g.slot = six_vc_hbm_slot(leq_rows, eq_rows, cols, cap, g.Rmax, g.ld).cells * 8;
@@ -93,17 +93,8 @@ inline SixVcHbmPlan six_vc_hbm_plan(bool pattern, int nfree, int leq_rows, int e
         return g;
     }
     g.route = SIX_VC_HBM_ROUTE_HBM;
-    long long per_cu = SIX_VC_HBM_WAVES_PER_CU * 64 / g.threads;
-    const long long by_lds = (long long)(((size_t)160 * 1024) / (g.lds + SIX_VC_HBM_LDS_STATIC));
-    if (per_cu > by_lds) per_cu = by_lds;
-    if (per_cu < 1) per_cu = 1;
-    long long grid = (long long)num_cus * per_cu;
-    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / g.slot);
-    if (grid > by_scratch) grid = by_scratch;
-    if (grid > nb) grid = nb;
-    if (grid < 1) grid = 1;
-    g.grid = (int)grid;
-    g.scratch = (size_t)grid * g.slot;
+    g.grid = (int)hbm_grid(num_cus, g.threads, SIX_VC_HBM_WAVES_PER_CU, g.lds + SIX_VC_HBM_LDS_STATIC, g.slot, SIX_VC_SCRATCH_MAX, nb);
+    g.scratch = (size_t)g.grid * g.slot;
     return g;
 }
 
@@ -114,8 +105,6 @@ inline SixVcHbmPlan six_vc_hbm_plan(bool pattern, int nfree, int leq_rows, int e
 // behind the call boundary the side arrays stay ds_* and the tableau global_* accesses (through generic pointers both became flat_*);
 // scalars by value, results by value.
 struct SixVcHbmSolved { int status; unsigned pivots; };
-#define XPG_AS_LDS __attribute__((address_space(3)))
-#define XPG_AS_GLOBAL __attribute__((address_space(1)))
 template <class S> __device__ __noinline__ SixVcHbmSolved six_vc_hbm_solve(XPG_AS_LDS unsigned char * lds, XPG_AS_GLOBAL S * tab, int ld, XPG_AS_GLOBAL const S * N,
                                                                           XPG_AS_GLOBAL const S * obj, int rows, int n, int is_max, unsigned max_iter,
                                                                           XPG_AS_GLOBAL S * y, XPG_AS_GLOBAL S * vout)
@@ -143,32 +132,11 @@ void k_six_batch_vc_hbm(int nb, const S * __restrict__ tgtf, const S * __restric
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
     const int n0 = cols - 1;
     S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
     int * const fv = (int *)slot;                                // (SixVcHbmSlot::fv == 0 whatever the shape is)
-    const S m1 = minus_one<S>();
-
-    // ---- vc: sign pattern? which variables are free (lpsol.h:1321-1339: a column of vc without a nonzero) ----
-    bool bad = false;
-    for (int t = tid; t < n0 * cols; t += nt) {
-        const int i = t / cols, j = t - i * cols;
-        const S c = vc[t];
-        if (j == i) bad |= !eq(c, zero<S>()) && !eq(c, m1);
-        else bad |= !eq(c, zero<S>());
-    }
-    if (tid < 64) {
-        int cnt = 0;
-        for (int base = 0; base < n0; base += 64) {
-            const int j = base + lane;
-            const bool fr = j < n0 && eq(vc[(size_t)j * cols + j], zero<S>());
-            const unsigned long long mask = __ballot(fr);
-            if (fr) fv[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = j;
-            cnt += __popcll(mask);
-        }
-        if (tid == 0) hdr[0] = cnt;
-    }
-    const bool general = __syncthreads_or(bad ? 1 : 0) != 0;     // (a barrier: hdr[0] and fv are the workgroup's now)
+    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
     const int nfree = hdr[0], n = n0 + nfree;
     const int rows_max = leq_rows + 2 * eq_rows;
     const int Rlp = is_max ? rows_max : n, Vlp = is_max ? n : rows_max;      // the largest normal form under the vc found
@@ -216,25 +184,9 @@ void k_six_batch_vc_hbm(int nb, const S * __restrict__ tgtf, const S * __restric
             if (tid == 0) { out_status[lp] = status; out_v[lp] = zero<S>(); }
             continue;
         }
-        // ---- finish (calcFinalSolution): the products into obj, which has done its work; their sum in column order
-        nf_unsplit<S>(y, cols, fv, nfree);
-        S * const prod = obj;
-        nf_products<S>(y, tg, cols, prod, out_sol + (size_t)lp * cols);
-        if (tid == 0) {
-            S v = zero<S>();
-            for (int j = 0; j < cols; j++) v = add(v, prod[j]);
-            reduce(v);
-            out_v[lp] = v;
-            out_status[lp] = 0;
-        }
+        // ---- finish (calcFinalSolution): the products into obj, which has done its work
+        vc_finish<S>(y, tg, cols, fv, nfree, obj, out_sol + (size_t)lp * cols, out_v + lp, out_status + lp);
     }
-}
-
-inline bool six_vc_hbm_args_ok(const xpg_ctx * ctx, int nb, const void * tgtf, const void * vc, const void * eqs, int eq_rows,
-                               const void * leq, int leq_rows, int cols, const void * out_status, const void * out_v, const void * out_sol)
-{
-    return ctx && nb >= 0 && tgtf && vc && cols >= 2 && eq_rows >= 0 && leq_rows >= 0 && !(eq_rows == 0 && leq_rows == 0) &&
-           !(eq_rows > 0 && !eqs) && !(leq_rows > 0 && !leq) && out_status && out_v && out_sol;
 }
 
 // The launch of k_six_batch_vc_hbm for a plan on the HBM route; every pointer is a device pointer.
@@ -243,15 +195,15 @@ int six_vc_hbm_launch(xpg_ctx * ctx, const SixVcHbmPlan & g, int nfree_cap, bool
                       int eq_rows, const S * leq, int leq_rows, int cols, unsigned max_iter, int32_t * out_status, S * out_v, S * out_sol,
                       uint32_t * out_pivots)
 {
-    if (g.scratch > ctx->six_vc_hbm_cap) {
-        if (ctx->six_vc_hbm_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->six_vc_hbm_buf); ctx->six_vc_hbm_buf = nullptr; ctx->six_vc_hbm_cap = 0; }
-        if (hipMalloc(&ctx->six_vc_hbm_buf, g.scratch) != hipSuccess) { ctx->six_vc_hbm_buf = nullptr; (void)hipGetLastError(); ctx->err = "hipMalloc(six_batch_vc_hbm scratch)"; return XPG_ERR_ALLOC; }
-        ctx->six_vc_hbm_cap = g.scratch;
-    }
+    Scratch & slots = ctx->scratch[SCRATCH_SIX_VC_HBM];
+    if (const int rc = scratch_reserve(ctx, slots, g.scratch, g.scratch, "hipMalloc(six_batch_vc_hbm scratch)")) return rc;
+    if (const int rc = hbm_static_lds_check(ctx, (const void *)k_six_batch_vc_hbm<S>, SIX_VC_HBM_LDS_STATIC,
+                                            "k_six_batch_vc_hbm: static LDS above SIX_VC_HBM_LDS_STATIC"))
+        return rc;
     XPG_HIP(ctx, lds_limit((const void *)k_six_batch_vc_hbm<S>, ctx->device, g.lds));
     hipLaunchKernelGGL((k_six_batch_vc_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, tgtf, vc, eqs, eq_rows,
                        leq, leq_rows, cols, is_max ? 1 : 0, max_iter, nfree_cap, g.Rmax, g.ld, (unsigned)g.lds,
-                       (unsigned long long *)ctx->six_vc_hbm_buf, (unsigned long long)(g.slot / 8), out_status, out_v, out_sol, out_pivots);
+                       (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), out_status, out_v, out_sol, out_pivots);
     XPG_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -265,7 +217,7 @@ int six_batch_vc_hbm_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, con
 {
     SixVcHbmRoute & rt = six_vc_hbm_route();
     rt = SixVcHbmRoute{0, 0, 0, -1, 0};
-    if (!six_vc_hbm_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
+    if (!six_vc_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     const SixVcHbmPlan g = six_vc_hbm_plan<S>(true, -1, leq_rows, eq_rows, cols, is_max, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
     if (g.route == SIX_VC_HBM_ROUTE_OTHER) return XPG_ERR_UNSUPPORTED;
@@ -291,7 +243,7 @@ int six_batch_vc_hbm_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S 
 {
     SixVcHbmRoute & rt = six_vc_hbm_route();
     rt = SixVcHbmRoute{0, 0, 0, 0, 0};
-    if (!six_vc_hbm_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
+    if (!six_vc_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     std::vector<int> fvar;
     const bool pattern = vc_sign_pattern(vc, cols - 1, cols, fvar);
@@ -303,27 +255,14 @@ int six_batch_vc_hbm_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S 
         rt.lds = r.device; rt.fallback = r.fallback; rt.free_vars = r.free_vars; rt.grid = rc == 0 && r.device ? g.grid : 0;
         return rc;
     }
-    const size_t bt = (size_t)nb * cols * 8, bv = (size_t)(cols - 1) * cols * 8, be = (size_t)nb * eq_rows * cols * 8,
-                 bl = (size_t)nb * leq_rows * cols * 8;
-    DevBuf dt, dvc, de, dl, dst, dv, ds;
-    XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dvc.alloc(ctx, bv)); XPG_TRY(de.alloc(ctx, be)); XPG_TRY(dl.alloc(ctx, bl));
-    XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(ds.alloc(ctx, bt));
-    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(dvc.p, vc, bv, hipMemcpyHostToDevice, ctx->stream));
-    if (eq_rows > 0) XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
-    if (leq_rows > 0) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = six_vc_hbm_launch<S>(ctx, g, nfree, is_max, nb, (const S *)dt.p, (const S *)dvc.p, (const S *)de.p, eq_rows, (const S *)dl.p,
-                                        leq_rows, cols, max_iter, (int32_t *)dst.p, (S *)dv.p, (S *)ds.p, nullptr);
+    BatchIo io;
+    int rc = io.up(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols);
+    if (rc) return rc;
+    rc = six_vc_hbm_launch<S>(ctx, g, nfree, is_max, nb, (const S *)io.dt.p, (const S *)io.dvc.p, (const S *)io.de.p, eq_rows, (const S *)io.dl.p,
+                              leq_rows, cols, max_iter, (int32_t *)io.dst.p, (S *)io.dv.p, (S *)io.ds.p, nullptr);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    std::vector<int32_t> st((size_t)nb);
-    std::vector<S> v((size_t)nb), sol((size_t)nb * cols);
-    XPG_TRY(hipMemcpyAsync(st.data(), dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(v.data(), dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(sol.data(), ds.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(out_status, st.data(), (size_t)nb * 4); memcpy(out_v, v.data(), (size_t)nb * 8);
-    for (int b = 0; b < nb; b++)                                 // (out_sol is written on success only, include/xpoly_amd.h)
-        if (st[(size_t)b] == 0) memcpy(out_sol + (size_t)b * cols, sol.data() + (size_t)b * cols, (size_t)cols * 8);
+    rc = io.down(ctx, nb, cols, out_status, out_v, out_sol);
+    if (rc) return rc;
     rt.hbm = nb; rt.free_vars = nfree; rt.grid = g.grid;
     return 0;
 }

@@ -178,9 +178,7 @@ void xpg_destroy(xpg_ctx * ctx)
     if (ctx->hpack) (void)hipHostFree(ctx->hpack);
     if (ctx->hred) (void)hipHostFree(ctx->hred);
     if (ctx->slice_buf) (void)hipFree(ctx->slice_buf);
-    if (ctx->six_vc_buf) (void)hipFree(ctx->six_vc_buf);
-    if (ctx->batch_hbm_buf) (void)hipFree(ctx->batch_hbm_buf);
-    if (ctx->six_vc_hbm_buf) (void)hipFree(ctx->six_vc_hbm_buf);
+    for (Scratch & s : ctx->scratch) s.release();
     for (xpg_ctx * l : ctx->lanes) xpg_destroy(l);
     ctx->lanes.clear();
     for (auto & b : ctx->dev_cache) (void)hipFree(b.first);
@@ -653,9 +651,7 @@ int xpg_trim(xpg_ctx * ctx)
     ctx->dev_cache.clear(); ctx->dev_cache_bytes = 0;
     if (ctx->hpack) { (void)hipHostFree(ctx->hpack); ctx->hpack = 0; ctx->hpack_cap = 0; }
     if (ctx->hred) { (void)hipHostFree(ctx->hred); ctx->hred = 0; ctx->hred_cap = 0; }
-    if (ctx->six_vc_buf) { (void)hipFree(ctx->six_vc_buf); ctx->six_vc_buf = 0; ctx->six_vc_cap = 0; }
-    if (ctx->batch_hbm_buf) { (void)hipFree(ctx->batch_hbm_buf); ctx->batch_hbm_buf = 0; ctx->batch_hbm_cap = 0; }
-    if (ctx->six_vc_hbm_buf) { (void)hipFree(ctx->six_vc_hbm_buf); ctx->six_vc_hbm_buf = 0; ctx->six_vc_hbm_cap = 0; }
+    for (Scratch & s : ctx->scratch) s.release();
     return 0;
 }
 

@@ -437,11 +437,9 @@ def mip_batch_eq(ctx, is_max, is_bin, tgtf, leq, eq, kind=RAT):
     return st, v, sol, nodes.value
 
 
-def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator=None, kind=RAT):
-    """nb independent MIPs under the variable constraints vc [cols - 1, cols(,2)] shared by the batch: tgtf [nb, cols(,2)],
-    leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)] or None (not both None), rational_indicator cols bytes or None.
-    A vc that is a sign pattern (diagonal -1 = x >= 0, 0 = free, nothing else) is walked on the device, free variables split
-    v = v' - v'' in front of every node LP; any other vc by the host controller. Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
+def _vc_batch_args(kind, tgtf, vc, leq, eq):
+    """The arrays of a batch under one vc as the ABI wants them, checked against each other:
+    (tgtf, vc, leq, eq, nb, cols, leq rows, eq rows)."""
     tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
     leq = None if leq is None else as_kind(leq, kind, 3)
     eq = None if eq is None else as_kind(eq, kind, 3)
@@ -453,6 +451,24 @@ def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator
             raise ValueError("leq / eq must be [nb, rows, cols]")
     rows = 0 if leq is None else leq.shape[1]
     eq_rows = 0 if eq is None else eq.shape[1]
+    return tgtf, vc, leq, eq, nb, cols, rows, eq_rows
+
+
+def _view(name, fields, *args):
+    """A host-only view of the library that fills an array of long long: its values under `fields`."""
+    out = (C.c_longlong * len(fields))()
+    rc = getattr(lib(), name)(*args, out, C.c_int(len(fields)))
+    if rc != 0:
+        raise XpgError("%s: %s" % (name, _capi.ERRORS.get(rc, rc)))
+    return dict(zip(fields, (int(x) for x in out)))
+
+
+def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator=None, kind=RAT):
+    """nb independent MIPs under the variable constraints vc [cols - 1, cols(,2)] shared by the batch: tgtf [nb, cols(,2)],
+    leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)] or None (not both None), rational_indicator cols bytes or None.
+    A vc that is a sign pattern (diagonal -1 = x >= 0, 0 = free, nothing else) is walked on the device, free variables split
+    v = v' - v'' in front of every node LP; any other vc by the host controller. Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
     ind = None if rational_indicator is None else np.ascontiguousarray(rational_indicator, dtype=np.uint8)
     st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
     nodes = C.c_longlong()
@@ -475,17 +491,7 @@ def mip_batch_vc_hbm(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, ind=None, kind
     launch mip_batch_vc makes; a sign-pattern vc past that: still one launch, a workgroup per tree with the node tableaux in
     device memory; anything else by the host controller. Arrays as mip_batch_vc takes them (ind: the rational_indicator).
     Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
-    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
-    leq = None if leq is None else as_kind(leq, kind, 3)
-    eq = None if eq is None else as_kind(eq, kind, 3)
-    nb, cols = tgtf.shape[0], tgtf.shape[1]
-    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
-        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
-    for a in (leq, eq):
-        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
-            raise ValueError("leq / eq must be [nb, rows, cols]")
-    rows = 0 if leq is None else leq.shape[1]
-    eq_rows = 0 if eq is None else eq.shape[1]
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
     ind = None if ind is None else np.ascontiguousarray(ind, dtype=np.uint8)
     st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
     nodes = C.c_longlong()
@@ -498,11 +504,7 @@ def mip_batch_vc_hbm(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, ind=None, kind
 def mip_hbm_last_route():
     """{'lds', 'hbm', 'host', 'free', 'grid'}: trees of this thread's last mip_batch_vc_hbm call on the LDS-resident walk / on
     the device-memory walk / on the host controller, the free variables split per tree, and the grid of its launch."""
-    out = (C.c_longlong * 5)()
-    rc = lib().xpg_mip_hbm_last_route(out, C.c_int(5))
-    if rc != 0:
-        raise XpgError("xpg_mip_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
-    return {"lds": out[0], "hbm": out[1], "host": out[2], "free": out[3], "grid": out[4]}
+    return _view("xpg_mip_hbm_last_route", ("lds", "hbm", "host", "free", "grid"))
 
 
 MIP_HBM_FIELDS = ("route", "free", "R", "V", "lds", "slot", "ld", "ws_words", "threads", "grid", "scratch")
@@ -517,12 +519,8 @@ def mip_hbm_plan(kind, vc, leq_rows, eq_rows, cols, is_bin, is_max, nb, num_cus=
     pat = lib().xpg_test_vc_pattern(C.c_int(kind), vp(vc_a), C.c_int(vc_a.shape[0]), C.c_int(cols), vp(free))
     if pat < 0:
         raise XpgError("xpg_test_vc_pattern: %s" % _capi.ERRORS.get(pat, pat))
-    out = (C.c_longlong * 11)()
-    rc = lib().xpg_test_mip_hbm_plan(C.c_int(kind), C.c_int(pat), C.c_int(leq_rows), C.c_int(eq_rows), C.c_int(cols), C.c_int(int(is_bin)),
-                                     C.c_int(int(is_max)), C.c_int(int(free.sum())), C.c_int(nb), C.c_int(num_cus), out, C.c_int(11))
-    if rc != 0:
-        raise XpgError("xpg_test_mip_hbm_plan: %s" % _capi.ERRORS.get(rc, rc))
-    return dict(zip(MIP_HBM_FIELDS, (int(x) for x in out)))
+    return _view("xpg_test_mip_hbm_plan", MIP_HBM_FIELDS, C.c_int(kind), C.c_int(pat), C.c_int(leq_rows), C.c_int(eq_rows), C.c_int(cols),
+                 C.c_int(int(is_bin)), C.c_int(int(is_max)), C.c_int(int(free.sum())), C.c_int(nb), C.c_int(num_cus))
 
 
 def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF):
@@ -532,17 +530,7 @@ def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF)
     64 KB of LDS: SIX::normalize, the solve and calcFinalSolution run on the device for the whole batch; anything else is
     solved per problem as SIX.maxm / minm would. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); status -7 marks the
     problems the reference is undefined on; sol rows are written on status 0 only."""
-    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
-    leq = None if leq is None else as_kind(leq, kind, 3)
-    eq = None if eq is None else as_kind(eq, kind, 3)
-    nb, cols = tgtf.shape[0], tgtf.shape[1]
-    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
-        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
-    for a in (leq, eq):
-        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
-            raise ValueError("leq / eq must be [nb, rows, cols]")
-    rows = 0 if leq is None else leq.shape[1]
-    eq_rows = 0 if eq is None else eq.shape[1]
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
     st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
     fn = lib().xpg_six_batch_vc_f64 if kind == F64 else lib().xpg_six_batch_vc_rat32
     ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
@@ -570,11 +558,7 @@ def six_batch_hbm(ctx, kind, is_max, tgtf, leq, max_iter=0xFFFFFFFF, out=None):
 def six_batch_hbm_last_route():
     """{'lds', 'hbm', 'grid'}: LPs of this thread's last six_batch_hbm call solved LDS-resident / on tableaux in device
     memory, and the grid of its launch."""
-    out = (C.c_longlong * 3)()
-    rc = lib().xpg_six_batch_hbm_last_route(out, C.c_int(3))
-    if rc != 0:
-        raise XpgError("xpg_six_batch_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
-    return {"lds": out[0], "hbm": out[1], "grid": out[2]}
+    return _view("xpg_six_batch_hbm_last_route", ("lds", "hbm", "grid"))
 
 
 BATCH_HBM_FIELDS = ("route", "lds", "slot", "ld", "threads", "grid", "scratch")
@@ -584,11 +568,7 @@ def six_batch_hbm_geometry(kind, R, V, nb, num_cus=256):
     """xpg_test_batch_hbm_geometry (host only, no device): what six_batch_hbm does with nb LPs solved as R rows x V
     variables -- route (0 LDS-resident, 1 tableau in device memory, 2 refused), LDS bytes, slot bytes, ld, threads, grid,
     scratch bytes of the launch."""
-    out = (C.c_longlong * 7)()
-    rc = lib().xpg_test_batch_hbm_geometry(C.c_int(kind), C.c_int(R), C.c_int(V), C.c_int(nb), C.c_int(num_cus), out, C.c_int(7))
-    if rc != 0:
-        raise XpgError("xpg_test_batch_hbm_geometry: %s" % _capi.ERRORS.get(rc, rc))
-    return dict(zip(BATCH_HBM_FIELDS, (int(x) for x in out)))
+    return _view("xpg_test_batch_hbm_geometry", BATCH_HBM_FIELDS, C.c_int(kind), C.c_int(R), C.c_int(V), C.c_int(nb), C.c_int(num_cus))
 
 
 def six_batch_vc_hbm(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF, out=None):
@@ -597,17 +577,7 @@ def six_batch_vc_hbm(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFF
     finishes on a slot in device memory; anything else per problem as SIX.maxm / minm would. Arrays as six_batch_vc takes
     them. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); `out`: such a triple to write into (rows of sol whose status is
     not 0 are left alone)."""
-    tgtf = as_kind(tgtf, kind, 2); vc = as_kind(vc, kind, 2)
-    leq = None if leq is None else as_kind(leq, kind, 3)
-    eq = None if eq is None else as_kind(eq, kind, 3)
-    nb, cols = tgtf.shape[0], tgtf.shape[1]
-    if vc.shape[0] != cols - 1 or vc.shape[1] != cols:
-        raise ValueError("vc must be [cols - 1, cols] = %s, got %s" % ((cols - 1, cols), vc.shape[:2]))
-    for a in (leq, eq):
-        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
-            raise ValueError("leq / eq must be [nb, rows, cols]")
-    rows = 0 if leq is None else leq.shape[1]
-    eq_rows = 0 if eq is None else eq.shape[1]
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
     if out is None:
         out = (np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind))
     st, v, sol = out
@@ -622,11 +592,7 @@ def six_batch_vc_hbm_last_route():
     """{'lds', 'hbm', 'fallback', 'free', 'grid'}: LPs of this thread's last six_batch_vc_hbm / six_batch_vc_hbm_dev call on the
     LDS-resident kernel / on slots in device memory / solved one by one, the free variables split per LP (-1 after a _dev
     call), and the grid of its launch."""
-    out = (C.c_longlong * 5)()
-    rc = lib().xpg_six_batch_vc_hbm_last_route(out, C.c_int(5))
-    if rc != 0:
-        raise XpgError("xpg_six_batch_vc_hbm_last_route: %s" % _capi.ERRORS.get(rc, rc))
-    return {"lds": out[0], "hbm": out[1], "fallback": out[2], "free": out[3], "grid": out[4]}
+    return _view("xpg_six_batch_vc_hbm_last_route", ("lds", "hbm", "fallback", "free", "grid"))
 
 
 SIX_BATCH_VC_HBM_FIELDS = ("route", "nfree", "Rmax", "Vmax", "lds", "slot", "ld", "threads", "grid", "scratch")
@@ -638,13 +604,8 @@ def six_batch_vc_hbm_plan(kind, vc, leq_rows, eq_rows, cols, is_max, nb, num_cus
     variables the largest normal form is solved with, LDS bytes, slot bytes, ld, threads, grid, scratch bytes. vc=None: the
     view of six_batch_vc_hbm_dev, which sizes for every variable free."""
     vc_a = None if vc is None else as_kind(vc, kind, 2)
-    out = (C.c_longlong * 10)()
-    rc = lib().xpg_test_six_batch_vc_hbm_plan(C.c_int(kind), vp(vc_a), C.c_int(0 if vc_a is None else vc_a.shape[0]), C.c_int(leq_rows),
-                                              C.c_int(eq_rows), C.c_int(cols), C.c_int(int(is_max)), C.c_int(nb), C.c_int(num_cus),
-                                              out, C.c_int(10))
-    if rc != 0:
-        raise XpgError("xpg_test_six_batch_vc_hbm_plan: %s" % _capi.ERRORS.get(rc, rc))
-    return dict(zip(SIX_BATCH_VC_HBM_FIELDS, (int(x) for x in out)))
+    return _view("xpg_test_six_batch_vc_hbm_plan", SIX_BATCH_VC_HBM_FIELDS, C.c_int(kind), vp(vc_a), C.c_int(0 if vc_a is None else vc_a.shape[0]),
+                 C.c_int(leq_rows), C.c_int(eq_rows), C.c_int(cols), C.c_int(int(is_max)), C.c_int(nb), C.c_int(num_cus))
 
 
 def six_batch_last_route():
