@@ -443,6 +443,48 @@ int xpg_test_warm_batch_geometry(int leq_rows, int cols, int is_bin, int nb, lon
 int xpg_has_solution_rat32(xpg_ctx * ctx, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq,
                            int eq_rows, const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx,
                            int is_int_sol, int is_unique_sol);
+/* Lineq::has_solution for nb systems of one shape in one call: leq [nb][leq_rows][cols], eq [nb][eq_rows][cols], vc
+ * [cols-1][cols] shared by the batch.  XPG_ERR_SHAPE as xpg_has_solution_rat32 (rhs_idx == cols - 1, vc_rows == rhs_idx);
+ * nb = 0 returns 0; without any row every verdict is 0, without an inequality XPG_ERR_REF_UNDEFINED (the reference sizes its
+ * objective from leq).  out_has[b]: 1 / 0, or the negative status a solve of system b returned (-7 where lpsol.h:1232 reads
+ * past an equality's row); such a status ends that system at once.  out_status [nb][2] (may be NULL): the XPG_SIX_* /
+ * XPG_IP_* status of the maxm solve and of the minm solve, [1] = XPG_HS_NOT_RUN where maxm decided (and both on the
+ * per-system route, which reports verdicts only).  The rule is the reference's: status 0 -> 1, status 1 without
+ * is_unique_sol -> 1, else minm under the same rule, else 0.
+ * is_int_sol = 0: max_iter bounds each SIX solve (0xFFFFFFFF: the reference's default, what the single call uses).
+ *   - vc a sign pattern and the largest normal form within 64 KB of LDS in BOTH directions: one launch, a workgroup per
+ *     system -- the objective (SIX::reviseTargetFunc on all ones) from the cells as given, SIX::normalize ONCE, maxm, then
+ *     minm on the same normal form where maxm left the question open;
+ *   - a sign pattern past that with both directions within the limits of xpg_six_batch_vc_hbm_*: the same on a slot in
+ *     device memory (one launch, sized for the larger direction);
+ *   - anything else: xpg_has_solution_rat32 per system (max_iter is not used there).
+ *   The statuses are bit for bit those of xpg_six_maxm_rat32 / xpg_six_minm_rat32 on the objective has_solution builds.
+ * is_int_sol = 1 (host arrays only; max_iter ignored, MIP fixes 10000 per node): xpg_mip_batch_vc_hbm_rat32 with
+ *   is_max = 1 on all systems, then with is_max = 0 on the open ones; the answers of xpg_has_solution_rat32(..., 1, u).
+ * The _dev form: every pointer a device pointer, is_int_sol must be 0, enqueue only -- results after xpg_sync.  The host
+ * never sees vc: sized for every variable free; a vc that is no sign pattern ends every system XPG_ERR_UNSUPPORTED, a shape
+ * beyond both kernels returns XPG_ERR_UNSUPPORTED before any launch.  Slots live in the areas the handle keeps for
+ * xpg_six_batch_vc_* / xpg_six_batch_vc_hbm_*; xpg_trim returns them.
+ * Tests: tests/test_has_solution_batch_host.py, tests/test_gpu_has_solution_batch.py. */
+enum { XPG_HS_NOT_RUN = 0x7FFFFFFF };
+int xpg_has_solution_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                 const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol,
+                                 unsigned max_iter, int32_t * out_has, int32_t * out_status);
+int xpg_has_solution_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                     const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol,
+                                     unsigned max_iter, int32_t * out_has, int32_t * out_status);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_has_solution_batch_* call did.  out[0] systems on
+ * the LDS-resident kernel, [1] on the device-memory kernel, [2] solved per system, [3] systems whose second solve ran (-1
+ * after a _dev call: only the device knows), [4] the grid of the launch (0 without one).  Fills min(n, 5) entries. */
+int xpg_has_solution_batch_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the route rule of xpg_has_solution_batch_* (is_int_sol = 0) for nb rational
+ * systems of a shape under vc [vc_rows][cols] on a device of num_cus compute units -- the function the launch itself asks;
+ * vc = NULL: the _dev form's view.  Fills min(n, 9) entries: out[0] route (0 LDS-resident kernel, 1 device-memory kernel,
+ * 2 neither); [1] free variables (-1: the _dev view); [2] rows of the largest tableau of either direction; [3] LDS bytes
+ * per workgroup (route 0: the larger direction's whole LP, else the larger side arrays); [4] bytes of one slot; [5] ld;
+ * [6] threads; [7] grid (0 on route 2); [8] scratch bytes of the launch. */
+int xpg_test_has_solution_batch_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus,
+                                     long long * out, int n);
 
 /* Batches: nb independent problems of one shape, x >= 0, inequalities only
  * (tgtf[nb][cols], leq[nb][leq_rows][cols]).  Every tree is walked on the device by one

@@ -3,7 +3,7 @@
 -ffp-contract=off is part of the numerical contract, not a tuning flag: the
 reference rounds after the multiply and again after the add (lpsol.h:1485-1489).
 
-csrc/xpoly_amd.hip is compiled seven times in parallel (-DXPG_PART=0..6, each part
+csrc/xpoly_amd.hip is compiled eight times in parallel (-DXPG_PART=0..7, each part
 holding the entry points of one subsystem and including only the kernel headers
 they launch) and the objects are linked into one shared object: the device code
 of all kernels in one translation unit took 4.7 minutes, the parts take about
@@ -23,7 +23,7 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 HOOKS_OUT = os.path.join(HERE, "libxpoly_amd_hooks.so")
 HOOKS_OBJ = os.path.join(HERE, "csrc", "_obj", "hooks")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17"]
-PARTS = 7
+PARTS = 8
 # headers each part includes (directly or not): a part is recompiled when one of them, or xpoly_amd.hip, is newer than
 # its object
 COMMON = ["xpoly_amd.hip", "scalar.hip.h", "ctx.hip.h", "rat_ops.hip.h", "../../include/xpoly_amd.h"]
@@ -36,6 +36,8 @@ DEPS = {
     5: ["lp_kernels.hip.h", "six_host.hip.h", "batch_kernels.hip.h", "batch_hbm.hip.h", "six_batch_vc.hip.h", "six_batch_vc_hbm.hip.h", "normalize_dev.hip.h"],
     6: ["lp_kernels.hip.h", "six_host.hip.h", "batch_kernels.hip.h", "batch_hbm.hip.h", "lineq_shared.hip.h", "mip_host.hip.h", "mip_kernels.hip.h",
         "mip_tree_hbm.hip.h", "normalize_dev.hip.h"],
+    7: ["lp_kernels.hip.h", "six_host.hip.h", "batch_kernels.hip.h", "batch_hbm.hip.h", "six_batch_vc.hip.h", "six_batch_vc_hbm.hip.h", "normalize_dev.hip.h",
+        "has_solution_batch.hip.h"],
 }
 
 

@@ -1,0 +1,399 @@
+// Lineq::has_solution (src/com/linsys.cpp:830-906) for a batch of systems of one shape in ONE launch (xpg_has_solution_batch_*):
+// maxm on SIX::reviseTargetFunc's all-ones objective, then minm where that left the question open. One workgroup owns one
+// system from the caller's arrays to the verdict, grid-stride over the batch, and every step is code that exists already:
+//   stage      leq and eq as k_six_batch_vc / k_six_batch_vc_hbm stage them
+//   objective  hs_objective below: feasibility_objective (six_host.hip.h) on the cells as staged, BEFORE any fold, into tg in
+//              the workgroup's slot
+//   normalise  ONCE: nf_convert_eq, nf_objective, nf_form (normalize_dev.hip.h) into the slot's N and obj
+//   maxm       the carve of a single call for (rows, n), sm_solve_lp with is_max = 1, raw solution
+//   minm       if open: the carve for the dual's shape over the same LDS, sm_solve_lp with is_max = 0 on the SAME N and obj --
+//              sm_solve_lp reads its source and never writes it
+// There is no calcFinalSolution (vc_finish never changes a status), so the statuses are those of two single
+// xpg_six_{maxm,minm}_rat32 calls and the verdict is has_solution()'s (mip_front.hip.h). Two kernels: k_has_solution_batch, the
+// LDS-resident form of k_six_batch_vc, and k_has_solution_batch_hbm, the device-memory form of k_six_batch_vc_hbm; ONE route
+// rule (hs_plan) sends the whole batch to one of them, sized for the larger direction, or to the host.
+// Slots are those of the two kernels this one joins with tg [cols] behind them: six_vc_slot | tg, six_vc_hbm_slot | tg, in
+// the handle's SCRATCH_SIX_VC / SCRATCH_SIX_VC_HBM areas. is_int_sol = 1 is composed on the host from xpg_mip_batch_vc_hbm_rat32.
+#pragma once
+#include "six_batch_vc_hbm.hip.h"
+
+namespace xpg {
+
+// What the calling thread's last xpg_has_solution_batch_* call did (xpg_has_solution_batch_last_route): systems on route 0 / 1 /
+// 2, systems whose second solve ran (-1 after a _dev call: only the device knows), the grid of the launch.
+struct HsRoute { long long lds, hbm, host, second, grid; };
+inline HsRoute & hs_route() { static thread_local HsRoute r = {0, 0, 0, 0, 0}; return r; }
+
+enum { HS_ROUTE_LDS = 0, HS_ROUTE_HBM = 1, HS_ROUTE_OTHER = 2 };
+
+// THE route rule (the launch and xpg_test_has_solution_batch_plan both ask it), from the plans of the two directions
+// (six_vc_hbm_plan, which asks six_vc_plan): nfree as six_vc_hbm_plan takes it.
+//   LDS    both directions keep k_six_batch_vc's launch: k_has_solution_batch, LDS and threads of the larger direction
+//   HBM    a sign pattern past that with neither direction refused: k_has_solution_batch_hbm, side arrays, tableau rows and
+//          slot of the larger of each, under the limits six_vc_hbm_plan holds one direction to
+//   OTHER  the host-array form calls has_solution() per system, the _dev form returns XPG_ERR_UNSUPPORTED before any launch
+struct HsPlan {
+    int route, nfree, Rmax;
+    size_t lds;             // LDS route: the larger small_lds_bytes; else the larger hbm_side_bytes
+    size_t slot;            // bytes of one workgroup's slot, tg included
+    int ld, threads, grid;
+    size_t scratch;         // grid x slot
+    size_t tg_cell;         // where tg starts in the slot, in 8-byte cells
+};
+template <class S> inline HsPlan hs_plan(bool pattern, int nfree, int leq_rows, int eq_rows, int cols, int nb, int num_cus)
+{
+    const SixVcHbmPlan a = six_vc_hbm_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, true, nb, num_cus);
+    const SixVcHbmPlan b = six_vc_hbm_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, false, nb, num_cus);
+    const size_t tgc = ((size_t)cols + 31) & ~(size_t)31;        // slots keep starting on 256-byte lines
+    HsPlan g;
+    g.nfree = a.nfree; g.Rmax = a.Rmax > b.Rmax ? a.Rmax : b.Rmax;
+    if (a.route == SIX_VC_HBM_ROUTE_LDS && b.route == SIX_VC_HBM_ROUTE_LDS) {
+        g.route = HS_ROUTE_LDS; g.lds = a.lds > b.lds ? a.lds : b.lds; g.ld = a.ld;
+        g.threads = a.threads > b.threads ? a.threads : b.threads;
+        g.tg_cell = a.slot / 8; g.slot = a.slot + tgc * 8;
+        long long grid = a.grid < b.grid ? a.grid : b.grid;
+        const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / g.slot);
+        if (grid > by_scratch) grid = by_scratch > 0 ? by_scratch : 1;
+        g.grid = (int)grid; g.scratch = (size_t)grid * g.slot;
+        return g;
+    }
+    const int cap = nfree >= 0 ? nfree : cols - 1;
+    const size_t sa = hbm_side_bytes<S>(a.Rmax, a.Vmax), sb = hbm_side_bytes<S>(b.Rmax, b.Vmax);
+    g.lds = sa > sb ? sa : sb;
+    g.ld = (int)hbm_ld(a.Rmax, a.Vmax);                          // (R + V is the same in both directions)
+    g.tg_cell = six_vc_hbm_slot(leq_rows, eq_rows, cols, cap, g.Rmax, g.ld).cells;
+    g.slot = (g.tg_cell + tgc) * 8;
+    g.threads = SIX_VC_HBM_THREADS;
+    if (a.route == SIX_VC_HBM_ROUTE_OTHER || b.route == SIX_VC_HBM_ROUTE_OTHER || g.lds + SIX_VC_HBM_LDS_STATIC > (size_t)160 * 1024 ||
+        g.slot > SIX_VC_SCRATCH_MAX) {
+        g.route = HS_ROUTE_OTHER; g.grid = 0; g.scratch = 0;
+        return g;
+    }
+    g.route = HS_ROUTE_HBM;
+    g.grid = (int)hbm_grid(num_cus, g.threads, SIX_VC_HBM_WAVES_PER_CU, g.lds + SIX_VC_HBM_LDS_STATIC, g.slot, SIX_VC_SCRATCH_MAX, nb);
+    g.scratch = (size_t)g.grid * g.slot;
+    return g;
+}
+
+// feasibility_objective (six_host.hip.h) by all threads, a thread a column: tg[j] = 1 where some staged inequality or equality
+// has a nonzero in column j < cols - 1, else 0. Behind its barrier tg is the workgroup's.
+template <class S> __device__ __forceinline__ void hs_objective(const S * L, int leq_rows, const S * E, int eq_rows, int cols, S * tg)
+{
+    for (int j = (int)threadIdx.x; j < cols; j += (int)blockDim.x) {
+        bool nz = false;
+        if (j < cols - 1) {
+            for (int i = 0; i < leq_rows && !nz; i++) nz = ne(L[(size_t)i * cols + j], zero<S>());
+            for (int i = 0; i < eq_rows && !nz; i++) nz = ne(E[(size_t)i * cols + j], zero<S>());
+        }
+        tg[j] = nz ? one<S>() : zero<S>();
+    }
+    __syncthreads();
+}
+// has_solution()'s verdict on one solve's status (linsys.cpp:864-876): < 0 the reference is undefined here, 1 a solution
+// exists; 0: still open.
+__device__ __forceinline__ int hs_verdict(int status, int is_unique)
+{
+    if (status < 0) return status;
+    return status == 0 || (status == 1 && !is_unique) ? 1 : 0;
+}
+// Every system of the launch ends `has` without a solve (a general vc, a shape the launch was not sized for; leq_rows = 0).
+__device__ __forceinline__ void hs_end_all(int nb, int has, int s0, int32_t * out_has, int32_t * out_status)
+{
+    for (int b = (int)(blockIdx.x * blockDim.x + threadIdx.x); b < nb; b += (int)(gridDim.x * blockDim.x)) {
+        out_has[b] = has;
+        if (out_status) { out_status[2 * (size_t)b] = s0; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
+    }
+}
+__global__ void k_hs_fill(int nb, int has, int s0, int32_t * out_has, int32_t * out_status) { hs_end_all(nb, has, s0, out_has, out_status); }
+
+// The LDS-resident form: k_six_batch_vc with the objective built on the device and the solve asked twice.
+template <class S> __global__ __launch_bounds__(256, 4)
+void k_has_solution_batch(int nb, const S * __restrict__ vc, const S * __restrict__ eqs, int eq_rows, const S * __restrict__ leq, int leq_rows,
+                          int cols, int is_unique, unsigned max_iter, unsigned lds_bytes, unsigned long long * __restrict__ slots,
+                          unsigned long long slot_cells, unsigned long long tg_cell, int32_t * __restrict__ out_has,
+                          int32_t * __restrict__ out_status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    const int n0 = cols - 1;
+    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
+    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
+    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
+    const int nfree = hdr[0], n = n0 + nfree;
+    const SixVcPlan up = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, true);
+    const SixVcPlan down = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, false);
+    const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree);
+    if (!up.device || !down.device || up.lds > (size_t)lds_bytes || down.lds > (size_t)lds_bytes || sl.work_cells * 8 > (size_t)lds_bytes ||
+        sl.cells > (size_t)tg_cell || tg_cell + (size_t)cols > (size_t)slot_cells) {
+        hs_end_all(nb, XPG_ERR_UNSUPPORTED, XPG_ERR_UNSUPPORTED, out_has, out_status);
+        return;
+    }
+    S * const N = slot + sl.N; S * const obj = slot + sl.obj; S * const y = slot + sl.y; S * const vout = slot + sl.v;
+    S * const tg = slot + tg_cell;
+    S * const work = (S *)lds;
+    S * const L = work + sl.L; S * const E = work + sl.E; int * const rest = (int *)(work + sl.rest);
+    const int lcells = leq_rows * cols, ecells = eq_rows * cols;
+
+    for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
+        __syncthreads();                                         // the system before is through with the LDS block, the slot and hdr
+        {
+            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
+            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
+            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
+        }
+        __syncthreads();
+        hs_objective<S>(L, leq_rows, E, eq_rows, cols, tg);
+        const EqRows<S> eq_lds = {E, cols};
+        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_lds, eq_rows, rest, hdr);
+        int has = 0, st[2] = {XPG_HS_NOT_RUN, XPG_HS_NOT_RUN};
+        if (nrest < 0) {                                         // this system alone; it never meets the pivot loop
+            has = st[0] = XPG_ERR_REF_UNDEFINED;
+        } else {
+            const int rows = leq_rows + 2 * nrest;
+            nf_objective<S>(tg, cols, fv, nfree, obj);
+            nf_form<S>(L, leq_rows, cols, eq_lds, rest, nrest, fv, nfree, N);    // (its barrier: L / E are read, the LDS block is the solver's)
+            for (int pass = 0; pass < 2 && has == 0; pass++) {   // maxm, then minm of what that left open
+                const int is_max = pass == 0 ? 1 : 0;
+                __syncthreads();                                 // pass 1 is through with the LDS block
+                Small<S> P;
+                sm_carve(P, lds, is_max ? rows : n, is_max ? n : rows);
+                Source<S> src;
+                src.leq = N; src.tgtf = obj; src.m = rows; src.cols = n + 1; src.is_max = is_max;
+                st[pass] = sm_solve_lp<S>(P, src, max_iter, /*raw_sol=*/1, y, vout);
+                has = hs_verdict(st[pass], is_unique);
+            }
+        }
+        if (tid == 0) {
+            out_has[lp] = has;
+            if (out_status) { out_status[2 * (size_t)lp] = st[0]; out_status[2 * (size_t)lp + 1] = st[1]; }
+        }
+    }
+}
+
+// The device-memory form: k_six_batch_vc_hbm's slot, reshaping and solve (six_vc_hbm_solve, registers of its own), asked twice.
+template <class S> __global__ __launch_bounds__(1024)
+void k_has_solution_batch_hbm(int nb, const S * __restrict__ vc, const S * __restrict__ eqs, int eq_rows, const S * __restrict__ leq,
+                              int leq_rows, int cols, int is_unique, unsigned max_iter, int nfree_cap, int Rmax, int ld, unsigned lds_bytes,
+                              unsigned long long * slots, unsigned long long slot_cells, int32_t * __restrict__ out_has,
+                              int32_t * __restrict__ out_status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    const int n0 = cols - 1;
+    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
+    int * const fv = (int *)slot;                                // (SixVcHbmSlot::fv == 0 whatever the shape is)
+    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
+    const int nfree = hdr[0], n = n0 + nfree;
+    const int rows_max = leq_rows + 2 * eq_rows;
+    const SixVcHbmSlot sl = six_vc_hbm_slot(leq_rows, eq_rows, cols, nfree_cap, Rmax, ld);
+    if (general || nfree > nfree_cap || eq_rows > (int)SIX_VC_MAX_EQ || rows_max > Rmax || n > Rmax || n + rows_max + 2 > ld ||
+        hbm_side_bytes<S>(rows_max, n) > (size_t)lds_bytes || hbm_side_bytes<S>(n, rows_max) > (size_t)lds_bytes ||
+        sl.cells + (size_t)cols > (size_t)slot_cells) {
+        hs_end_all(nb, XPG_ERR_UNSUPPORTED, XPG_ERR_UNSUPPORTED, out_has, out_status);
+        return;
+    }
+    S * const L = slot + sl.L; S * const E = slot + sl.E; int * const rest = (int *)(slot + sl.rest);
+    S * const N = slot + sl.N; S * const obj = slot + sl.obj; S * const y = slot + sl.y; S * const vout = slot + sl.v;
+    S * const tab = slot + sl.tab; S * const tg = slot + sl.cells;
+    const int lcells = leq_rows * cols, ecells = eq_rows * cols;
+
+    for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
+        __syncthreads();                                         // the system before is through with the LDS block, the slot and hdr
+        {
+            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
+            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
+            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
+        }
+        __syncthreads();
+        hs_objective<S>(L, leq_rows, E, eq_rows, cols, tg);
+        const EqRows<S> eq_slot = {E, cols};
+        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_slot, eq_rows, rest, hdr);
+        int has = 0, st[2] = {XPG_HS_NOT_RUN, XPG_HS_NOT_RUN};
+        if (nrest < 0) {
+            has = st[0] = XPG_ERR_REF_UNDEFINED;
+        } else {
+            const int rows = leq_rows + 2 * nrest;
+            nf_objective<S>(tg, cols, fv, nfree, obj);
+            nf_form<S>(L, leq_rows, cols, eq_slot, rest, nrest, fv, nfree, N);
+            for (int pass = 0; pass < 2 && has == 0; pass++) {   // maxm, then minm of what that left open
+                __syncthreads();                                 // pass 1 is through with the LDS block and the tableau
+                st[pass] = six_vc_hbm_solve<S>((XPG_AS_LDS unsigned char *)lds, (XPG_AS_GLOBAL S *)tab, ld, (XPG_AS_GLOBAL const S *)N,
+                                               (XPG_AS_GLOBAL const S *)obj, rows, n, pass == 0 ? 1 : 0, max_iter, (XPG_AS_GLOBAL S *)y,
+                                               (XPG_AS_GLOBAL S *)vout).status;
+                has = hs_verdict(st[pass], is_unique);
+            }
+        }
+        if (tid == 0) {
+            out_has[lp] = has;
+            if (out_status) { out_status[2 * (size_t)lp] = st[0]; out_status[2 * (size_t)lp + 1] = st[1]; }
+        }
+    }
+}
+
+// What xpg_has_solution_batch_* ask of their arguments: has_solution()'s shape rule, and the arrays the rows need.
+inline bool hs_args_ok(const xpg_ctx * ctx, int nb, const void * leq, int leq_rows, const void * eqs, int eq_rows, const void * vc, int vc_rows,
+                       int cols, int rhs, const void * out_has)
+{
+    return ctx && nb >= 0 && vc && cols >= 2 && rhs == cols - 1 && vc_rows == rhs && leq_rows >= 0 && eq_rows >= 0 &&
+           !(leq_rows > 0 && !leq) && !(eq_rows > 0 && !eqs) && out_has;
+}
+
+// The launch for a plan on route 0 or 1; every pointer is a device pointer. nfree_cap: the free variables the plan was sized for.
+template <class S>
+int hs_launch(xpg_ctx * ctx, HsPlan g, int nfree_cap, int nb, const S * vc, const S * eqs, int eq_rows, const S * leq, int leq_rows, int cols,
+              bool is_unique, unsigned max_iter, int32_t * out_has, int32_t * out_status)
+{
+    static const int grid_cap = [] { const char * e = xpg_hook("XPG_HS_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
+    if (grid_cap > 0 && g.grid > grid_cap) { g.grid = grid_cap; g.scratch = (size_t)g.grid * g.slot; }
+    if (g.route == HS_ROUTE_LDS) {
+        Scratch & slots = ctx->scratch[SCRATCH_SIX_VC];
+        if (const int rc = scratch_reserve(ctx, slots, g.scratch, g.scratch, "hipMalloc(has_solution_batch scratch)")) return rc;
+        XPG_HIP(ctx, lds_limit((const void *)k_has_solution_batch<S>, ctx->device, g.lds));
+        hipLaunchKernelGGL((k_has_solution_batch<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, vc, eqs, eq_rows, leq,
+                           leq_rows, cols, is_unique ? 1 : 0, max_iter, (unsigned)g.lds, (unsigned long long *)slots.buf,
+                           (unsigned long long)(g.slot / 8), (unsigned long long)g.tg_cell, out_has, out_status);
+    } else {
+        Scratch & slots = ctx->scratch[SCRATCH_SIX_VC_HBM];
+        if (const int rc = scratch_reserve(ctx, slots, g.scratch, g.scratch, "hipMalloc(has_solution_batch_hbm scratch)")) return rc;
+        if (const int rc = hbm_static_lds_check(ctx, (const void *)k_has_solution_batch_hbm<S>, SIX_VC_HBM_LDS_STATIC,
+                                                "k_has_solution_batch_hbm: static LDS above SIX_VC_HBM_LDS_STATIC"))
+            return rc;
+        XPG_HIP(ctx, lds_limit((const void *)k_has_solution_batch_hbm<S>, ctx->device, g.lds));
+        hipLaunchKernelGGL((k_has_solution_batch_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, vc, eqs, eq_rows,
+                           leq, leq_rows, cols, is_unique ? 1 : 0, max_iter, nfree_cap, g.Rmax, g.ld, (unsigned)g.lds,
+                           (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), out_has, out_status);
+    }
+    XPG_HIP(ctx, hipGetLastError());
+    HsRoute & rt = hs_route();
+    (g.route == HS_ROUTE_LDS ? rt.lds : rt.hbm) = nb; rt.grid = g.grid;
+    return 0;
+}
+
+// Device arrays in and out, enqueue only (a scratch area that has to grow waits for the stream first). The host never sees
+// vc: everything is sized for every variable free; is_int_sol is the host-array form's alone.
+template <class S>
+int has_solution_batch_dev(xpg_ctx * ctx, int nb, const S * leq, int leq_rows, const S * eqs, int eq_rows, const S * vc, int vc_rows, int cols,
+                           int rhs, bool is_int, bool is_unique, unsigned max_iter, int32_t * out_has, int32_t * out_status)
+{
+    HsRoute & rt = hs_route();
+    rt = HsRoute{0, 0, 0, -1, 0};
+    if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has) || is_int) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    if (leq_rows == 0) {                                         // no system: 0; no inequality: the reference sizes tgtf from leq (linsys.cpp:851)
+        hipLaunchKernelGGL(k_hs_fill, dim3((unsigned)((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024)), dim3(256), 0, ctx->stream, nb,
+                           eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED, eq_rows == 0 ? (int)XPG_HS_NOT_RUN : (int)XPG_ERR_REF_UNDEFINED, out_has, out_status);
+        XPG_HIP(ctx, hipGetLastError());
+        return 0;
+    }
+    const HsPlan g = hs_plan<S>(true, -1, leq_rows, eq_rows, cols, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    if (g.route == HS_ROUTE_OTHER) return XPG_ERR_UNSUPPORTED;
+    return hs_launch<S>(ctx, g, cols - 1, nb, vc, eqs, eq_rows, leq, leq_rows, cols, is_unique, max_iter, out_has, out_status);
+}
+
+// Host arrays; synchronises once. single(b): has_solution() of system b (route 2, a function of another part of the library).
+template <class S, class Single>
+int has_solution_batch_host(xpg_ctx * ctx, int nb, const S * leq, int leq_rows, const S * eqs, int eq_rows, const S * vc, int vc_rows, int cols,
+                            int rhs, bool is_unique, unsigned max_iter, int32_t * out_has, int32_t * out_status, Single single)
+{
+    HsRoute & rt = hs_route();
+    rt = HsRoute{0, 0, 0, 0, 0};
+    if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has)) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    const auto end = [&](int b, int has, int s0, int s1) {
+        out_has[b] = has;
+        if (out_status) { out_status[2 * (size_t)b] = s0; out_status[2 * (size_t)b + 1] = s1; }
+    };
+    if (leq_rows == 0) {
+        const int has = eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED;
+        for (int b = 0; b < nb; b++) end(b, has, eq_rows == 0 ? (int)XPG_HS_NOT_RUN : has, XPG_HS_NOT_RUN);
+        return 0;
+    }
+    std::vector<int> fvar;
+    const bool pattern = vc_sign_pattern(vc, vc_rows, cols, fvar);
+    const int nfree = pattern ? (int)fvar.size() : 0;
+    const HsPlan g = hs_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    if (g.route == HS_ROUTE_OTHER) {                             // the statuses stay has_solution()'s own: XPG_HS_NOT_RUN here
+        for (int b = 0; b < nb; b++) {
+            const int has = single(b);
+            if (has < 0 && has != XPG_ERR_REF_UNDEFINED) return has;
+            end(b, has, XPG_HS_NOT_RUN, XPG_HS_NOT_RUN);
+            rt.host++;
+        }
+        return 0;
+    }
+    const size_t bl = (size_t)nb * leq_rows * cols * 8, be = (size_t)nb * eq_rows * cols * 8, bv = (size_t)vc_rows * cols * 8;
+    DevBuf dl, de, dvc, dhas, dst;
+    XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(de.alloc(ctx, be)); XPG_TRY(dvc.alloc(ctx, bv));
+    XPG_TRY(dhas.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dst.alloc(ctx, (size_t)nb * 8));
+    XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
+    if (eq_rows > 0) XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(dvc.p, vc, bv, hipMemcpyHostToDevice, ctx->stream));
+    int rc = hs_launch<S>(ctx, g, nfree, nb, (const S *)dvc.p, (const S *)de.p, eq_rows, (const S *)dl.p, leq_rows, cols, is_unique, max_iter,
+                          (int32_t *)dhas.p, (int32_t *)dst.p);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); rt = HsRoute{0, 0, 0, 0, 0}; return rc; }
+    std::vector<int32_t> has((size_t)nb), st((size_t)nb * 2);       // staged, so a HIP call that fails leaves the caller's arrays untouched
+    XPG_TRY(hipMemcpyAsync(has.data(), dhas.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(st.data(), dst.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < nb; b++) {
+        end(b, has[(size_t)b], st[2 * (size_t)b], st[2 * (size_t)b + 1]);
+        rt.second += st[2 * (size_t)b + 1] != XPG_HS_NOT_RUN;
+    }
+    return 0;
+}
+
+// is_int_sol = 1, host arrays: has_solution()'s two MIP walks for the whole batch -- walk(is_max, count, tgtf, eq, leq, status)
+// is xpg_mip_batch_vc_hbm_rat32 with is_bin = 0 and no indicator -- maxm on all systems, minm on the compacted open ones.
+template <class Walk>
+int has_solution_batch_int(xpg_ctx * ctx, int nb, const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, const R32 * vc, int vc_rows,
+                           int cols, int rhs, bool is_unique, int32_t * out_has, int32_t * out_status, Walk walk)
+{
+    HsRoute & rt = hs_route();
+    rt = HsRoute{0, 0, 0, 0, 0};
+    if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has)) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    if (leq_rows == 0) {
+        const int has = eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED;
+        for (int b = 0; b < nb; b++) {
+            out_has[b] = has;
+            if (out_status) { out_status[2 * (size_t)b] = eq_rows == 0 ? (int)XPG_HS_NOT_RUN : has; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
+        }
+        return 0;
+    }
+    const size_t lc = (size_t)leq_rows * cols, ec = (size_t)eq_rows * cols;
+    std::vector<R32> tg((size_t)nb * cols), cl, ce, ct;
+    for (int b = 0; b < nb; b++) {
+        const std::vector<R32> t = feasibility_objective(leq + b * lc, leq_rows, eq_rows ? eqs + b * ec : (const R32 *)0, eq_rows, cols, rhs);
+        std::copy(t.begin(), t.end(), tg.begin() + (size_t)b * cols);
+    }
+    std::vector<int32_t> st((size_t)nb);
+    std::vector<int> open;
+    if (const int rc = walk(1, nb, tg.data(), eqs, leq, st.data())) return rc;
+    for (int b = 0; b < nb; b++) {
+        const int s = st[(size_t)b];
+        out_has[b] = s < 0 ? s : (s == 0 || (s == 1 && !is_unique) ? 1 : 0);
+        if (out_status) { out_status[2 * (size_t)b] = s; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
+        if (out_has[b] == 0) open.push_back(b);
+    }
+    if (open.empty()) return 0;
+    const int no = (int)open.size();
+    cl.resize(no * lc); ce.resize(no * ec); ct.resize((size_t)no * cols);
+    for (int t = 0; t < no; t++) {
+        const size_t b = (size_t)open[(size_t)t];
+        std::copy(leq + b * lc, leq + (b + 1) * lc, cl.begin() + t * lc);
+        if (ec) std::copy(eqs + b * ec, eqs + (b + 1) * ec, ce.begin() + t * ec);
+        std::copy(tg.begin() + b * cols, tg.begin() + (b + 1) * cols, ct.begin() + (size_t)t * cols);
+    }
+    if (const int rc = walk(0, no, ct.data(), ec ? ce.data() : (const R32 *)0, cl.data(), st.data())) return rc;
+    for (int t = 0; t < no; t++) {
+        const int b = open[(size_t)t], s = st[(size_t)t];
+        out_has[b] = s < 0 ? s : (s == 0 || (s == 1 && !is_unique) ? 1 : 0);
+        if (out_status) out_status[2 * (size_t)b + 1] = s;
+    }
+    rt.second = no;
+    return 0;
+}
+
+} // namespace xpg

@@ -41,19 +41,6 @@ __global__ void k_dep_update(int nb, const int32_t * status, int * active, int32
     else if (st == XPG_IP_SUCC) { empty[b] = 0; active[b] = 0; }
 }
 
-// SIX::reviseTargetFunc on the all-ones objective (lpsol.h:2053-2074, linsys.cpp:851-862).
-inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, int cols, int rhs)
-{
-    std::vector<R32> tgtf(cols, R32(0, 1));
-    for (int j = 0; j < rhs; j++) {
-        bool nz = false;
-        for (int i = 0; i < leq_rows && !nz; i++) nz = !eq(leq[(size_t)i * cols + j], R32(0, 1));
-        for (int i = 0; i < eq_rows && !nz; i++) nz = !eq(eqs[(size_t)i * cols + j], R32(0, 1));
-        tgtf[j] = nz ? R32(1, 1) : R32(0, 1);
-    }
-    return tgtf;
-}
-
 // Lineq::has_solution (linsys.cpp:830-906): maxm then minm; success, or an unbounded answer
 // when a unique solution is not demanded, means "has a solution".
 inline int has_solution(xpg_ctx * ctx, const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, const R32 * vc,

@@ -177,6 +177,20 @@ template <class S> bool vc_sign_pattern(const S * vc, int vc_rows, int cols, std
     return true;
 }
 
+// SIX::reviseTargetFunc on the all-ones objective (lpsol.h:2053-2074, linsys.cpp:851-862): Lineq::has_solution's objective,
+// for its single-problem front end (mip_front.hip.h) and its batched one (has_solution_batch.hip.h).
+inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, int cols, int rhs)
+{
+    std::vector<R32> tgtf(cols, R32(0, 1));
+    for (int j = 0; j < rhs; j++) {
+        bool nz = false;
+        for (int i = 0; i < leq_rows && !nz; i++) nz = !eq(leq[(size_t)i * cols + j], R32(0, 1));
+        for (int i = 0; i < eq_rows && !nz; i++) nz = !eq(eqs[(size_t)i * cols + j], R32(0, 1));
+        tgtf[j] = nz ? R32(1, 1) : R32(0, 1);
+    }
+    return tgtf;
+}
+
 // The cells of the normal form on the host (the LDS route's small problems).
 template <class S>
 int normalize_cells_host(const S * eqs, const S * leq, NormalForm<S> & F)

@@ -12,7 +12,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/xpoly_amd.h"
-// The library is ONE shared object built from this file compiled seven times in parallel (-DXPG_PART=0..6, build.py):
+// The library is ONE shared object built from this file compiled eight times in parallel (-DXPG_PART=0..7, build.py):
 // the device code of all kernels together takes four minutes in one translation unit, and every part only includes
 // the kernel headers its entry points launch. XPG_PART undefined = everything in one translation unit.
 //   part 0  handle, K1 pivot, the device-resident LP (every loop of lp_*.hip.h), warm-started MIP, test and debug hooks
@@ -22,6 +22,7 @@
 //   part 4  LP batches beyond one CU's LDS (k_batch_hbm)
 //   part 5  the same with equalities and free variables (k_six_batch_vc_hbm)
 //   part 6  MIP tree walks whose node LPs are beyond 64 KB of LDS (k_mip_tree_hbm)
+//   part 7  batched has_solution (k_has_solution_batch, k_has_solution_batch_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -57,6 +58,9 @@
 #endif
 #if XPG_IN(6)
 #include "mip_tree_hbm.hip.h"
+#endif
+#if XPG_IN(7)
+#include "has_solution_batch.hip.h"
 #endif
 
 using namespace xpg;
@@ -1581,6 +1585,59 @@ int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int 
     const long long f[11] = { g.route, g.extra, g.R, g.V, (long long)g.lds, (long long)g.slot, g.ld, (long long)g.ws_words, g.threads, g.grid,
                               (long long)g.scratch };
     for (int k = 0; k < n && k < 11; k++) out[k] = f[k];
+    return 0;
+}
+} // extern "C"
+#endif
+#if XPG_IN(7)
+extern "C" {
+// ---- Lineq::has_solution for a batch: maxm, then minm where still open, one launch (has_solution_batch.hip.h) ----
+int xpg_has_solution_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                 const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol,
+                                 unsigned max_iter, int32_t * out_has, int32_t * out_status)
+{
+    XPG_BIND(ctx);
+    const size_t lc = (size_t)(leq_rows > 0 ? leq_rows : 0) * cols, ec = (size_t)(eq_rows > 0 ? eq_rows : 0) * cols;
+    if (is_int_sol)       // the two walks are another part's (mip_tree_hbm.hip.h): its C entry point
+        return has_solution_batch_int(ctx, nb, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols, rhs_idx,
+                                      is_unique_sol != 0, out_has, out_status,
+                                      [&](int is_max, int count, const R32 * tg, const R32 * e, const R32 * l, int32_t * st) {
+            std::vector<R32> v((size_t)count), sol((size_t)count * cols);
+            return xpg_mip_batch_vc_hbm_rat32(ctx, count, is_max, 0, (const xpg_rat32 *)tg, vc, (const xpg_rat32 *)e, eq_rows, (const xpg_rat32 *)l,
+                                              leq_rows, cols, (const uint8_t *)0, st, (xpg_rat32 *)v.data(), (xpg_rat32 *)sol.data(), (long long *)0);
+        });
+    return has_solution_batch_host<R32>(ctx, nb, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols, rhs_idx,
+                                        is_unique_sol != 0, max_iter, out_has, out_status, [&](int b) {   // has_solution() is another part's (mip_front.hip.h)
+        return xpg_has_solution_rat32(ctx, leq + (size_t)b * lc, leq_rows, eq_rows > 0 ? eq + (size_t)b * ec : (const xpg_rat32 *)0, eq_rows, vc,
+                                      vc_rows, cols, rhs_idx, 0, is_unique_sol);
+    });
+}
+int xpg_has_solution_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                     const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol,
+                                     unsigned max_iter, int32_t * out_has, int32_t * out_status)
+{
+    XPG_BIND(ctx);
+    return has_solution_batch_dev<R32>(ctx, nb, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols, rhs_idx,
+                                       is_int_sol != 0, is_unique_sol != 0, max_iter, out_has, out_status);
+}
+// what the calling thread's last xpg_has_solution_batch_* call did (has_solution_batch.hip.h HsRoute)
+int xpg_has_solution_batch_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const HsRoute & r = hs_route();
+    const long long f[5] = { r.lds, r.hbm, r.host, r.second, r.grid };
+    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
+    return 0;
+}
+// host-only test view: the route rule of xpg_has_solution_batch_* and the sizes it decides by; vc == NULL: the _dev form's view
+int xpg_test_has_solution_batch_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus, long long * out, int n)
+{
+    if (!out || n < 0 || cols < 2 || (vc && vc_rows != cols - 1) || leq_rows <= 0 || eq_rows < 0 || nb <= 0 || num_cus <= 0) return XPG_ERR_SHAPE;
+    std::vector<int> fv;
+    const bool pat = vc ? vc_sign_pattern((const R32 *)vc, vc_rows, cols, fv) : true;
+    const HsPlan g = hs_plan<R32>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, nb, num_cus);
+    const long long f[9] = { g.route, g.nfree, g.Rmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
+    for (int k = 0; k < n && k < 9; k++) out[k] = f[k];
     return 0;
 }
 } // extern "C"

@@ -187,9 +187,20 @@ class Context:
                       C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
                       C.c_void_p(sol_ptr), C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_vc_hbm_dev")
 
+    def has_solution_batch_dev(self, nb, leq_ptr, leq_rows, eq_ptr, eq_rows, vc_ptr, cols, is_unique_sol, has_ptr, status_ptr=None,
+                               max_iter=0xFFFFFFFF, is_int_sol=False):
+        """xpg_has_solution_batch_rat32_dev: has_solution_batch on device pointers (vc included), enqueue only -- results after
+        sync(). Sized for every variable free. A vc that is no sign pattern ends every system -4; a shape beyond both kernels, or
+        is_int_sol, raises XpgError and launches nothing."""
+        self.check(lib().xpg_has_solution_batch_rat32_dev(
+            self._h, C.c_int(nb), C.c_void_p(leq_ptr) if leq_ptr else None, C.c_int(leq_rows), C.c_void_p(eq_ptr) if eq_ptr else None,
+            C.c_int(eq_rows), C.c_void_p(vc_ptr), C.c_int(cols - 1), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_int_sol)),
+            C.c_int(int(is_unique_sol)), C.c_uint(max_iter), C.c_void_p(has_ptr), C.c_void_p(status_ptr) if status_ptr else None),
+            "xpg_has_solution_batch_rat32_dev")
+
     def trim(self):
-        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm / six_batch_vc_hbm go
-        back to the runtime."""
+        """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm / six_batch_vc_hbm /
+        has_solution_batch go back to the runtime."""
         self.check(lib().xpg_trim(self._h), "xpg_trim")
 
 
@@ -663,6 +674,58 @@ def has_solution(ctx, leq, eq, vc, rhs_idx, is_int_sol, is_unique_sol):
     if r < 0 and r != -7:
         ctx.check(r, "xpg_has_solution_rat32")
     return r
+
+
+HS_NOT_RUN = 0x7FFFFFFF                  # XPG_HS_NOT_RUN: the solve did not run
+
+
+def has_solution_batch(ctx, leq, eq, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
+    """Lineq::has_solution for nb rational systems of one shape in one call (xpg_has_solution_batch_rat32): leq [nb, rows,
+    cols(,2)], eq [nb, eq_rows, cols(,2)] or None, vc [cols - 1, cols(,2)] shared by the batch; the constant is the last column.
+    is_int_sol False: a sign-pattern vc within the batch kernels' limits is answered in ONE launch -- the feasibility objective,
+    SIX::normalize once, maxm, then minm where that left the question open -- anything else per system as has_solution does.
+    is_int_sol True: two batched MIP walks, the second on the systems the first left open. Returns has[nb] (1 / 0, or the
+    negative status a solve returned: -7 where the reference is undefined), and with want_status also status[nb, 2]: the SIX /
+    IP status of the maxm and of the minm solve, HS_NOT_RUN for a solve that did not run."""
+    vc = as_kind(vc, RAT, 2)
+    cols = vc.shape[1]
+    leq_a = None if leq is None else as_kind(leq, RAT, 3)
+    eq_a = None if eq is None else as_kind(eq, RAT, 3)
+    if leq_a is None and eq_a is None:
+        raise ValueError("leq and eq are both None: the batch size is unknown")
+    nb = (leq_a if leq_a is not None else eq_a).shape[0]
+    for a in (leq_a, eq_a):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq_a is None else leq_a.shape[1]
+    eq_rows = 0 if eq_a is None else eq_a.shape[1]
+    has = np.zeros(nb, dtype=np.int32)
+    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
+    ctx.check(lib().xpg_has_solution_batch_rat32(ctx._h, C.c_int(nb), vp(leq_a if rows else None), C.c_int(rows), vp(eq_a if eq_rows else None),
+                                                 C.c_int(eq_rows), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1),
+                                                 C.c_int(int(is_int_sol)), C.c_int(int(is_unique_sol)), C.c_uint(max_iter), vp(has), vp(st)),
+              "xpg_has_solution_batch_rat32")
+    return (has, st) if want_status else has
+
+
+def has_solution_batch_last_route():
+    """{'lds', 'hbm', 'host', 'second', 'grid'}: systems of this thread's last has_solution_batch / has_solution_batch_dev call on
+    the LDS-resident kernel / the device-memory kernel / answered per system, the systems whose second solve ran (-1 after a
+    _dev call), and the grid of its launch."""
+    return _view("xpg_has_solution_batch_last_route", ("lds", "hbm", "host", "second", "grid"))
+
+
+HAS_SOLUTION_BATCH_FIELDS = ("route", "nfree", "Rmax", "lds", "slot", "ld", "threads", "grid", "scratch")
+
+
+def has_solution_batch_plan(vc, leq_rows, eq_rows, cols, nb, num_cus=256):
+    """xpg_test_has_solution_batch_plan (host only, no device): what has_solution_batch (is_int_sol False) does with nb systems
+    of a shape under vc [cols - 1, cols(,2)] -- route (0 LDS-resident kernel, 1 device-memory kernel, 2 neither), free
+    variables, rows of the largest tableau of either direction, LDS bytes, slot bytes, ld, threads, grid, scratch bytes.
+    vc=None: the view of has_solution_batch_dev, which sizes for every variable free."""
+    vc_a = None if vc is None else as_kind(vc, RAT, 2)
+    return _view("xpg_test_has_solution_batch_plan", HAS_SOLUTION_BATCH_FIELDS, vp(vc_a), C.c_int(0 if vc_a is None else vc_a.shape[0]),
+                 C.c_int(leq_rows), C.c_int(eq_rows), C.c_int(cols), C.c_int(nb), C.c_int(num_cus))
 
 
 class SIX:
