@@ -199,6 +199,46 @@ def test_shape_rules_and_systems_without_rows(ctx):
     _compare(_batch(ctx, (vc_arr, eq, leq), True)[:2], want, True, "after trim")
 
 
+@pytest.mark.parametrize("eq_rows", [0, 2])
+def test_without_inequalities_every_form_ends_as_the_single_call(ctx, eq_rows):
+    """leq_rows = 0 never meets a solve: no rows at all is "no solution" with neither solve run, equalities only is
+    XPG_ERR_REF_UNDEFINED as verdict and as the first status (the reference sizes tgtf from leq). The host-array form, the _dev
+    form and the is_int_sol = 1 form give that for every system, and xpg_has_solution_rat32 the same verdict per system."""
+    from xpoly_amd._capi import lib, vp
+    from xpoly_amd.six import has_solution
+    import ctypes as C
+    nb, cols = 3, 4
+    vc_arr = gen.to_rat(gen.vc_nonneg(cols - 1, False))
+    eq = gen.to_rat(np.random.default_rng(31).integers(-3, 4, size=(nb, eq_rows, cols))) if eq_rows else None
+    want_has = 0 if eq_rows == 0 else XPG_ERR_REF_UNDEFINED
+    want_st = (hs.NOT_RUN, hs.NOT_RUN) if eq_rows == 0 else (XPG_ERR_REF_UNDEFINED, hs.NOT_RUN)
+    for unique in (False, True):
+        for is_int in (0, 1):
+            has = np.full(nb, 55, dtype=np.int32); st = np.full((nb, 2), 55, dtype=np.int32)
+            assert lib().xpg_has_solution_batch_rat32(
+                ctx._h, C.c_int(nb), None, C.c_int(0), vp(eq), C.c_int(eq_rows), vp(vc_arr), C.c_int(cols - 1), C.c_int(cols), C.c_int(cols - 1),
+                C.c_int(is_int), C.c_int(int(unique)), C.c_uint(hs.NO_LIMIT), vp(has), vp(st)) == 0
+            one = [has_solution(ctx, None, None if eq is None else eq[i], vc_arr, cols - 1, bool(is_int), unique) for i in range(nb)]
+            print("eq_rows=%d u=%d int=%d has %s status %s single %s" % (eq_rows, unique, is_int, has.tolist(), st.tolist(), one))
+            assert has.tolist() == [want_has] * nb and st.tolist() == [list(want_st)] * nb and one == [want_has] * nb
+        d_eq = ctx.malloc(eq.nbytes) if eq_rows else 0
+        d_vc, d_has, d_st = ctx.malloc(vc_arr.nbytes), ctx.malloc(nb * 4), ctx.malloc(nb * 8)
+        try:
+            if eq_rows:
+                ctx.upload(d_eq, eq)
+            ctx.upload(d_vc, vc_arr)
+            ctx.upload(d_has, np.full(nb, 55, dtype=np.int32)); ctx.upload(d_st, np.full((nb, 2), 55, dtype=np.int32))
+            ctx.has_solution_batch_dev(nb, 0, 0, d_eq, eq_rows, d_vc, cols, unique, d_has, d_st)
+            ctx.sync()
+            has = ctx.download(np.zeros(nb, dtype=np.int32), d_has)
+            st = ctx.download(np.zeros((nb, 2), dtype=np.int32), d_st)
+        finally:
+            for p in [d_vc, d_has, d_st] + ([d_eq] if eq_rows else []):
+                ctx.free(p)
+        print("eq_rows=%d u=%d _dev has %s status %s" % (eq_rows, unique, has.tolist(), st.tolist()))
+        assert has.tolist() == [want_has] * nb and st.tolist() == [list(want_st)] * nb
+
+
 def test_the_collector_groups_by_shape_and_scatters_back(ctx, tmp_path):
     """tests/cxx/has_solution_all.cpp in a child process: systems of (4, 1, 4, 0) and (9, 2, 4, 0) interleaved -- one vc, two
     shape groups -- come back in the order given with the checker's verdicts."""

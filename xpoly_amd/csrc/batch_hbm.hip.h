@@ -248,11 +248,10 @@ int batch_hbm_dev(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * l
     if (nb == 0) return 0;
     const int n = cols - 1;
     const int R = is_max ? m : n, V = is_max ? n : m;
-    static const int threads_hook = [] { const char * e = xpg_hook("XPG_BATCH_HBM_THREADS"); return e ? atoi(e) : 0; }();   // A/B runs (tools/lab)
-    static const int waves_hook = [] { const char * e = xpg_hook("XPG_BATCH_HBM_WAVES"); return e ? atoi(e) : 0; }();
-    static const int grid_cap = [] { const char * e = xpg_hook("XPG_BATCH_HBM_GRID"); return e ? atoi(e) : 0; }();
+    const int threads_hook = XPG_INT_HOOK("XPG_BATCH_HBM_THREADS"), waves_hook = XPG_INT_HOOK("XPG_BATCH_HBM_WAVES");   // A/B runs (tools/lab)
+    const int grid_cap = XPG_INT_HOOK("XPG_BATCH_HBM_GRID");
     const int threads = threads_hook >= 64 && threads_hook <= 1024 && threads_hook % 64 == 0 ? threads_hook : 0;
-    HbmGeom g = batch_hbm_geometry<S>(R, V, nb, ctx->num_cus > 0 ? ctx->num_cus : 256, threads, waves_hook);
+    HbmGeom g = batch_hbm_geometry<S>(R, V, nb, ctx_cus(ctx), threads, waves_hook);
     if (g.route == HBM_ROUTE_REFUSED) return XPG_ERR_UNSUPPORTED;
     if (g.route == HBM_ROUTE_LDS) {
         const int rc = batch_dev<S>(ctx, is_max, nb, tgtf, leq, m, cols, max_iter, out_status, out_v, out_sol, out_pivots, 0);
@@ -284,7 +283,7 @@ int batch_hbm_host(xpg_ctx * ctx, int is_max, int nb, const S * tgtf, const S * 
     if (nb == 0) return 0;
     const int n = cols - 1;
     const int R = is_max ? m : n, V = is_max ? n : m;
-    const HbmGeom g = batch_hbm_geometry<S>(R, V, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const HbmGeom g = batch_hbm_geometry<S>(R, V, nb, ctx_cus(ctx));
     if (g.route == HBM_ROUTE_REFUSED) return XPG_ERR_UNSUPPORTED;
     if (g.route == HBM_ROUTE_LDS) {
         const int rc = batch_host<S>(ctx, is_max, nb, tgtf, leq, m, cols, max_iter, out_status, out_v, out_sol);

@@ -84,7 +84,11 @@ struct DeviceGuard {
 #define XPG_BIND(ctx_) xpg::DeviceGuard xpg_bind_guard_((ctx_) ? (ctx_)->device : -1)
 
 inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
+// The compute units the launch geometries count on: the device's, or an MI355X's where the handle could not ask.
+inline int ctx_cus(const xpg_ctx * ctx) { return ctx->num_cus > 0 ? ctx->num_cus : 256; }
 
+// The views of the C ABI (xpg_*_last_route, xpg_test_*_plan, ...) hand out the first n of their fields.
+template <class T, class U, int K> inline int copy_fields(T * out, int n, const U (&f)[K]) { for (int k = 0; k < n && k < K; k++) out[k] = f[k]; return 0; }
 // hipFuncAttributeMaxDynamicSharedMemorySize is one value per (function, device): two host threads -- two handles,
 // or the _multi entry points given the same device twice -- setting "exactly what this launch needs" could lower
 // it between the other thread's set and its launch. So the limit is only ever RAISED, under a mutex.

@@ -1,17 +1,19 @@
 // Lineq::has_solution (src/com/linsys.cpp:830-906) for a batch of systems of one shape in ONE launch (xpg_has_solution_batch_*):
 // maxm on SIX::reviseTargetFunc's all-ones objective, then minm where that left the question open. One workgroup owns one
-// system from the caller's arrays to the verdict, grid-stride over the batch, and every step is code that exists already:
-//   stage      leq and eq as k_six_batch_vc / k_six_batch_vc_hbm stage them
-//   objective  hs_objective below: feasibility_objective (six_host.hip.h) on the cells as staged, BEFORE any fold, into tg in
-//              the workgroup's slot
-//   normalise  ONCE: nf_convert_eq, nf_objective, nf_form (normalize_dev.hip.h) into the slot's N and obj
+// system from the caller's arrays to the verdict, grid-stride over the batch, through the steps the four kernels of this family
+// share (six_batch_vc.hip.h: vc_prologue, vc_stage, vc_reshape) and has_solution's rules as six_host.hip.h states them once
+// (hs_verdict, hs_no_inequality, hs_store):
+//   stage      vc_stage: leq and eq between two barriers
+//   objective  hs_objective below: feasibility_objective (six_host.hip.h) on the cells as staged, BEFORE any fold, into tg
+//   normalise  ONCE, vc_reshape: nf_convert_eq, nf_objective, nf_form (normalize_dev.hip.h) into the slot's N and obj
 //   maxm       the carve of a single call for (rows, n), sm_solve_lp with is_max = 1, raw solution
-//   minm       if open: the carve for the dual's shape over the same LDS, sm_solve_lp with is_max = 0 on the SAME N and obj --
-//              sm_solve_lp reads its source and never writes it
+//   minm       if hs_verdict leaves it open: the carve for the dual's shape over the same LDS, sm_solve_lp with is_max = 0 on the
+//              SAME N and obj -- sm_solve_lp reads its source and never writes it
 // There is no calcFinalSolution (vc_finish never changes a status), so the statuses are those of two single
 // xpg_six_{maxm,minm}_rat32 calls and the verdict is has_solution()'s (mip_front.hip.h). Two kernels: k_has_solution_batch, the
-// LDS-resident form of k_six_batch_vc, and k_has_solution_batch_hbm, the device-memory form of k_six_batch_vc_hbm; ONE route
-// rule (hs_plan) sends the whole batch to one of them, sized for the larger direction, or to the host.
+// LDS-resident form of k_six_batch_vc, and k_has_solution_batch_hbm, the device-memory form of k_six_batch_vc_hbm; their two-pass
+// loops stay two (one body taking the solve as a callable moved the spills of both). ONE route rule (hs_plan) sends the whole
+// batch to one of them, sized for the larger direction, or to the host.
 // Slots are those of the two kernels this one joins with tg [cols] behind them: six_vc_slot | tg, six_vc_hbm_slot | tg, in
 // the handle's SCRATCH_SIX_VC / SCRATCH_SIX_VC_HBM areas. is_int_sol = 1 is composed on the host from xpg_mip_batch_vc_hbm_rat32.
 #pragma once
@@ -51,9 +53,7 @@ template <class S> inline HsPlan hs_plan(bool pattern, int nfree, int leq_rows, 
         g.route = HS_ROUTE_LDS; g.lds = a.lds > b.lds ? a.lds : b.lds; g.ld = a.ld;
         g.threads = a.threads > b.threads ? a.threads : b.threads;
         g.tg_cell = a.slot / 8; g.slot = a.slot + tgc * 8;
-        long long grid = a.grid < b.grid ? a.grid : b.grid;
-        const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / g.slot);
-        if (grid > by_scratch) grid = by_scratch > 0 ? by_scratch : 1;
+        const long long grid = six_vc_scratch_cut(a.grid < b.grid ? a.grid : b.grid, g.slot);
         g.grid = (int)grid; g.scratch = (size_t)grid * g.slot;
         return g;
     }
@@ -64,13 +64,8 @@ template <class S> inline HsPlan hs_plan(bool pattern, int nfree, int leq_rows, 
     g.tg_cell = six_vc_hbm_slot(leq_rows, eq_rows, cols, cap, g.Rmax, g.ld).cells;
     g.slot = (g.tg_cell + tgc) * 8;
     g.threads = SIX_VC_HBM_THREADS;
-    if (a.route == SIX_VC_HBM_ROUTE_OTHER || b.route == SIX_VC_HBM_ROUTE_OTHER || g.lds + SIX_VC_HBM_LDS_STATIC > (size_t)160 * 1024 ||
-        g.slot > SIX_VC_SCRATCH_MAX) {
-        g.route = HS_ROUTE_OTHER; g.grid = 0; g.scratch = 0;
-        return g;
-    }
-    g.route = HS_ROUTE_HBM;
-    g.grid = (int)hbm_grid(num_cus, g.threads, SIX_VC_HBM_WAVES_PER_CU, g.lds + SIX_VC_HBM_LDS_STATIC, g.slot, SIX_VC_SCRATCH_MAX, nb);
+    g.grid = six_vc_hbm_grid(a.route != SIX_VC_HBM_ROUTE_OTHER && b.route != SIX_VC_HBM_ROUTE_OTHER, g.lds, g.slot, nb, num_cus);
+    g.route = g.grid > 0 ? HS_ROUTE_HBM : HS_ROUTE_OTHER;
     g.scratch = (size_t)g.grid * g.slot;
     return g;
 }
@@ -89,20 +84,11 @@ template <class S> __device__ __forceinline__ void hs_objective(const S * L, int
     }
     __syncthreads();
 }
-// has_solution()'s verdict on one solve's status (linsys.cpp:864-876): < 0 the reference is undefined here, 1 a solution
-// exists; 0: still open.
-__device__ __forceinline__ int hs_verdict(int status, int is_unique)
-{
-    if (status < 0) return status;
-    return status == 0 || (status == 1 && !is_unique) ? 1 : 0;
-}
 // Every system of the launch ends `has` without a solve (a general vc, a shape the launch was not sized for; leq_rows = 0).
 __device__ __forceinline__ void hs_end_all(int nb, int has, int s0, int32_t * out_has, int32_t * out_status)
 {
-    for (int b = (int)(blockIdx.x * blockDim.x + threadIdx.x); b < nb; b += (int)(gridDim.x * blockDim.x)) {
-        out_has[b] = has;
-        if (out_status) { out_status[2 * (size_t)b] = s0; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
-    }
+    for (int b = (int)(blockIdx.x * blockDim.x + threadIdx.x); b < nb; b += (int)(gridDim.x * blockDim.x))
+        hs_store(b, has, s0, XPG_HS_NOT_RUN, out_has, out_status);
 }
 __global__ void k_hs_fill(int nb, int has, int s0, int32_t * out_has, int32_t * out_status) { hs_end_all(nb, has, s0, out_has, out_status); }
 
@@ -116,9 +102,9 @@ void k_has_solution_batch(int nb, const S * __restrict__ vc, const S * __restric
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int n0 = cols - 1;
+    const int n0 = cols - 1;                                     // (vc_prologue's lines: through it this kernel's spills move)
     S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
-    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
+    int * const fv = (int *)slot;
     const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
     const int nfree = hdr[0], n = n0 + nfree;
     const SixVcPlan up = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, true);
@@ -136,23 +122,14 @@ void k_has_solution_batch(int nb, const S * __restrict__ vc, const S * __restric
     const int lcells = leq_rows * cols, ecells = eq_rows * cols;
 
     for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
-        __syncthreads();                                         // the system before is through with the LDS block, the slot and hdr
-        {
-            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
-            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
-            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
-        }
-        __syncthreads();
+        vc_stage<S>(tid, nt, leq, lcells, eqs, ecells, lp, L, E);
         hs_objective<S>(L, leq_rows, E, eq_rows, cols, tg);
-        const EqRows<S> eq_lds = {E, cols};
-        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_lds, eq_rows, rest, hdr);
+        const int nrest = vc_reshape<S>(L, leq_rows, cols, E, eq_rows, rest, hdr, tg, fv, nfree, obj, N);
         int has = 0, st[2] = {XPG_HS_NOT_RUN, XPG_HS_NOT_RUN};
         if (nrest < 0) {                                         // this system alone; it never meets the pivot loop
             has = st[0] = XPG_ERR_REF_UNDEFINED;
         } else {
             const int rows = leq_rows + 2 * nrest;
-            nf_objective<S>(tg, cols, fv, nfree, obj);
-            nf_form<S>(L, leq_rows, cols, eq_lds, rest, nrest, fv, nfree, N);    // (its barrier: L / E are read, the LDS block is the solver's)
             for (int pass = 0; pass < 2 && has == 0; pass++) {   // maxm, then minm of what that left open
                 const int is_max = pass == 0 ? 1 : 0;
                 __syncthreads();                                 // pass 1 is through with the LDS block
@@ -161,13 +138,10 @@ void k_has_solution_batch(int nb, const S * __restrict__ vc, const S * __restric
                 Source<S> src;
                 src.leq = N; src.tgtf = obj; src.m = rows; src.cols = n + 1; src.is_max = is_max;
                 st[pass] = sm_solve_lp<S>(P, src, max_iter, /*raw_sol=*/1, y, vout);
-                has = hs_verdict(st[pass], is_unique);
+                has = hs_verdict(st[pass], is_unique != 0);
             }
         }
-        if (tid == 0) {
-            out_has[lp] = has;
-            if (out_status) { out_status[2 * (size_t)lp] = st[0]; out_status[2 * (size_t)lp + 1] = st[1]; }
-        }
+        if (tid == 0) hs_store(lp, has, st[0], st[1], out_has, out_status);
     }
 }
 
@@ -181,14 +155,12 @@ void k_has_solution_batch_hbm(int nb, const S * __restrict__ vc, const S * __res
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int n0 = cols - 1;
-    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
-    int * const fv = (int *)slot;                                // (SixVcHbmSlot::fv == 0 whatever the shape is)
-    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
-    const int nfree = hdr[0], n = n0 + nfree;
+    const VcProlog<S> pr = vc_prologue<S>(vc, cols, slots, slot_cells, hdr);
+    S * const slot = pr.slot; const int * const fv = pr.fv;
+    const int nfree = pr.nfree, n = pr.n;
     const int rows_max = leq_rows + 2 * eq_rows;
     const SixVcHbmSlot sl = six_vc_hbm_slot(leq_rows, eq_rows, cols, nfree_cap, Rmax, ld);
-    if (general || nfree > nfree_cap || eq_rows > (int)SIX_VC_MAX_EQ || rows_max > Rmax || n > Rmax || n + rows_max + 2 > ld ||
+    if (pr.general || nfree > nfree_cap || eq_rows > (int)SIX_VC_MAX_EQ || rows_max > Rmax || n > Rmax || n + rows_max + 2 > ld ||
         hbm_side_bytes<S>(rows_max, n) > (size_t)lds_bytes || hbm_side_bytes<S>(n, rows_max) > (size_t)lds_bytes ||
         sl.cells + (size_t)cols > (size_t)slot_cells) {
         hs_end_all(nb, XPG_ERR_UNSUPPORTED, XPG_ERR_UNSUPPORTED, out_has, out_status);
@@ -200,35 +172,23 @@ void k_has_solution_batch_hbm(int nb, const S * __restrict__ vc, const S * __res
     const int lcells = leq_rows * cols, ecells = eq_rows * cols;
 
     for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
-        __syncthreads();                                         // the system before is through with the LDS block, the slot and hdr
-        {
-            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
-            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
-            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
-        }
-        __syncthreads();
+        vc_stage<S>(tid, nt, leq, lcells, eqs, ecells, lp, L, E);
         hs_objective<S>(L, leq_rows, E, eq_rows, cols, tg);
-        const EqRows<S> eq_slot = {E, cols};
-        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_slot, eq_rows, rest, hdr);
+        const int nrest = vc_reshape<S>(L, leq_rows, cols, E, eq_rows, rest, hdr, tg, fv, nfree, obj, N);
         int has = 0, st[2] = {XPG_HS_NOT_RUN, XPG_HS_NOT_RUN};
         if (nrest < 0) {
             has = st[0] = XPG_ERR_REF_UNDEFINED;
         } else {
             const int rows = leq_rows + 2 * nrest;
-            nf_objective<S>(tg, cols, fv, nfree, obj);
-            nf_form<S>(L, leq_rows, cols, eq_slot, rest, nrest, fv, nfree, N);
             for (int pass = 0; pass < 2 && has == 0; pass++) {   // maxm, then minm of what that left open
                 __syncthreads();                                 // pass 1 is through with the LDS block and the tableau
                 st[pass] = six_vc_hbm_solve<S>((XPG_AS_LDS unsigned char *)lds, (XPG_AS_GLOBAL S *)tab, ld, (XPG_AS_GLOBAL const S *)N,
                                                (XPG_AS_GLOBAL const S *)obj, rows, n, pass == 0 ? 1 : 0, max_iter, (XPG_AS_GLOBAL S *)y,
                                                (XPG_AS_GLOBAL S *)vout).status;
-                has = hs_verdict(st[pass], is_unique);
+                has = hs_verdict(st[pass], is_unique != 0);
             }
         }
-        if (tid == 0) {
-            out_has[lp] = has;
-            if (out_status) { out_status[2 * (size_t)lp] = st[0]; out_status[2 * (size_t)lp + 1] = st[1]; }
-        }
+        if (tid == 0) hs_store(lp, has, st[0], st[1], out_has, out_status);
     }
 }
 
@@ -245,7 +205,7 @@ template <class S>
 int hs_launch(xpg_ctx * ctx, HsPlan g, int nfree_cap, int nb, const S * vc, const S * eqs, int eq_rows, const S * leq, int leq_rows, int cols,
               bool is_unique, unsigned max_iter, int32_t * out_has, int32_t * out_status)
 {
-    static const int grid_cap = [] { const char * e = xpg_hook("XPG_HS_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
+    const int grid_cap = XPG_INT_HOOK("XPG_HS_GRID");            // tests: the grid-stride path at small nb
     if (grid_cap > 0 && g.grid > grid_cap) { g.grid = grid_cap; g.scratch = (size_t)g.grid * g.slot; }
     if (g.route == HS_ROUTE_LDS) {
         Scratch & slots = ctx->scratch[SCRATCH_SIX_VC];
@@ -281,13 +241,14 @@ int has_solution_batch_dev(xpg_ctx * ctx, int nb, const S * leq, int leq_rows, c
     rt = HsRoute{0, 0, 0, -1, 0};
     if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has) || is_int) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    if (leq_rows == 0) {                                         // no system: 0; no inequality: the reference sizes tgtf from leq (linsys.cpp:851)
-        hipLaunchKernelGGL(k_hs_fill, dim3((unsigned)((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024)), dim3(256), 0, ctx->stream, nb,
-                           eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED, eq_rows == 0 ? (int)XPG_HS_NOT_RUN : (int)XPG_ERR_REF_UNDEFINED, out_has, out_status);
+    if (leq_rows == 0) {
+        const HsNoLeq e = hs_no_inequality(eq_rows);
+        hipLaunchKernelGGL(k_hs_fill, dim3((unsigned)((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024)), dim3(256), 0, ctx->stream, nb, e.has, e.status0,
+                           out_has, out_status);
         XPG_HIP(ctx, hipGetLastError());
         return 0;
     }
-    const HsPlan g = hs_plan<S>(true, -1, leq_rows, eq_rows, cols, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const HsPlan g = hs_plan<S>(true, -1, leq_rows, eq_rows, cols, nb, ctx_cus(ctx));
     if (g.route == HS_ROUTE_OTHER) return XPG_ERR_UNSUPPORTED;
     return hs_launch<S>(ctx, g, cols - 1, nb, vc, eqs, eq_rows, leq, leq_rows, cols, is_unique, max_iter, out_has, out_status);
 }
@@ -301,24 +262,20 @@ int has_solution_batch_host(xpg_ctx * ctx, int nb, const S * leq, int leq_rows, 
     rt = HsRoute{0, 0, 0, 0, 0};
     if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    const auto end = [&](int b, int has, int s0, int s1) {
-        out_has[b] = has;
-        if (out_status) { out_status[2 * (size_t)b] = s0; out_status[2 * (size_t)b + 1] = s1; }
-    };
     if (leq_rows == 0) {
-        const int has = eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED;
-        for (int b = 0; b < nb; b++) end(b, has, eq_rows == 0 ? (int)XPG_HS_NOT_RUN : has, XPG_HS_NOT_RUN);
+        const HsNoLeq e = hs_no_inequality(eq_rows);
+        for (int b = 0; b < nb; b++) hs_store(b, e.has, e.status0, XPG_HS_NOT_RUN, out_has, out_status);
         return 0;
     }
     std::vector<int> fvar;
     const bool pattern = vc_sign_pattern(vc, vc_rows, cols, fvar);
     const int nfree = pattern ? (int)fvar.size() : 0;
-    const HsPlan g = hs_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const HsPlan g = hs_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, nb, ctx_cus(ctx));
     if (g.route == HS_ROUTE_OTHER) {                             // the statuses stay has_solution()'s own: XPG_HS_NOT_RUN here
         for (int b = 0; b < nb; b++) {
             const int has = single(b);
             if (has < 0 && has != XPG_ERR_REF_UNDEFINED) return has;
-            end(b, has, XPG_HS_NOT_RUN, XPG_HS_NOT_RUN);
+            hs_store(b, has, XPG_HS_NOT_RUN, XPG_HS_NOT_RUN, out_has, out_status);
             rt.host++;
         }
         return 0;
@@ -338,7 +295,7 @@ int has_solution_batch_host(xpg_ctx * ctx, int nb, const S * leq, int leq_rows, 
     XPG_TRY(hipMemcpyAsync(st.data(), dst.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < nb; b++) {
-        end(b, has[(size_t)b], st[2 * (size_t)b], st[2 * (size_t)b + 1]);
+        hs_store(b, has[(size_t)b], st[2 * (size_t)b], st[2 * (size_t)b + 1], out_has, out_status);
         rt.second += st[2 * (size_t)b + 1] != XPG_HS_NOT_RUN;
     }
     return 0;
@@ -355,11 +312,8 @@ int has_solution_batch_int(xpg_ctx * ctx, int nb, const R32 * leq, int leq_rows,
     if (!hs_args_ok(ctx, nb, leq, leq_rows, eqs, eq_rows, vc, vc_rows, cols, rhs, out_has)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
     if (leq_rows == 0) {
-        const int has = eq_rows == 0 ? 0 : (int)XPG_ERR_REF_UNDEFINED;
-        for (int b = 0; b < nb; b++) {
-            out_has[b] = has;
-            if (out_status) { out_status[2 * (size_t)b] = eq_rows == 0 ? (int)XPG_HS_NOT_RUN : has; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
-        }
+        const HsNoLeq e = hs_no_inequality(eq_rows);
+        for (int b = 0; b < nb; b++) hs_store(b, e.has, e.status0, XPG_HS_NOT_RUN, out_has, out_status);
         return 0;
     }
     const size_t lc = (size_t)leq_rows * cols, ec = (size_t)eq_rows * cols;
@@ -368,29 +322,26 @@ int has_solution_batch_int(xpg_ctx * ctx, int nb, const R32 * leq, int leq_rows,
         const std::vector<R32> t = feasibility_objective(leq + b * lc, leq_rows, eq_rows ? eqs + b * ec : (const R32 *)0, eq_rows, cols, rhs);
         std::copy(t.begin(), t.end(), tg.begin() + (size_t)b * cols);
     }
-    std::vector<int32_t> st((size_t)nb);
+    std::vector<int32_t> st((size_t)nb), st2;
     std::vector<int> open;
     if (const int rc = walk(1, nb, tg.data(), eqs, leq, st.data())) return rc;
     for (int b = 0; b < nb; b++) {
-        const int s = st[(size_t)b];
-        out_has[b] = s < 0 ? s : (s == 0 || (s == 1 && !is_unique) ? 1 : 0);
-        if (out_status) { out_status[2 * (size_t)b] = s; out_status[2 * (size_t)b + 1] = XPG_HS_NOT_RUN; }
+        hs_store(b, hs_verdict(st[(size_t)b], is_unique), st[(size_t)b], XPG_HS_NOT_RUN, out_has, out_status);
         if (out_has[b] == 0) open.push_back(b);
     }
     if (open.empty()) return 0;
     const int no = (int)open.size();
-    cl.resize(no * lc); ce.resize(no * ec); ct.resize((size_t)no * cols);
+    cl.resize(no * lc); ce.resize(no * ec); ct.resize((size_t)no * cols); st2.resize((size_t)no);
     for (int t = 0; t < no; t++) {
         const size_t b = (size_t)open[(size_t)t];
         std::copy(leq + b * lc, leq + (b + 1) * lc, cl.begin() + t * lc);
         if (ec) std::copy(eqs + b * ec, eqs + (b + 1) * ec, ce.begin() + t * ec);
         std::copy(tg.begin() + b * cols, tg.begin() + (b + 1) * cols, ct.begin() + (size_t)t * cols);
     }
-    if (const int rc = walk(0, no, ct.data(), ec ? ce.data() : (const R32 *)0, cl.data(), st.data())) return rc;
+    if (const int rc = walk(0, no, ct.data(), ec ? ce.data() : (const R32 *)0, cl.data(), st2.data())) return rc;
     for (int t = 0; t < no; t++) {
-        const int b = open[(size_t)t], s = st[(size_t)t];
-        out_has[b] = s < 0 ? s : (s == 0 || (s == 1 && !is_unique) ? 1 : 0);
-        if (out_status) out_status[2 * (size_t)b + 1] = s;
+        const int b = open[(size_t)t];
+        hs_store(b, hs_verdict(st2[(size_t)t], is_unique), st[(size_t)b], st2[(size_t)t], out_has, out_status);
     }
     rt.second = no;
     return 0;

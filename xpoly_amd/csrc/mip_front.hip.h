@@ -47,19 +47,16 @@ inline int has_solution(xpg_ctx * ctx, const R32 * leq, int leq_rows, const R32 
                         int vc_rows, int cols, int rhs, bool is_int, bool is_unique)
 {
     if (!ctx || !vc || cols < 2 || rhs != cols - 1 || vc_rows != rhs) return XPG_ERR_SHAPE;
-    if (leq_rows == 0 && eq_rows == 0) return 0;
-    if (leq_rows == 0) return XPG_ERR_REF_UNDEFINED;      // the reference sizes tgtf from leq (linsys.cpp:851)
+    if (leq_rows == 0) return hs_no_inequality(eq_rows).has;
     const std::vector<R32> tgtf = feasibility_objective(leq, leq_rows, eqs, eq_rows, cols, rhs);
     R32 v; std::vector<R32> sol(cols);
     for (int pass = 0; pass < 2; pass++) {
-        int st = is_int
+        const int st = is_int
             ? mip_solve<R32>(ctx, 1, pass == 0, false, tgtf.data(), vc, vc_rows, eqs, eq_rows, leq, leq_rows, cols,
                              (const uint8_t *)0, &v, sol.data(), (long *)0)
             : six_solve<R32>(ctx, 1, pass == 0, tgtf.data(), vc, vc_rows, eqs, eq_rows, leq, leq_rows, cols,
                              0xFFFFFFFFu, &v, sol.data());
-        if (st < 0) return st;
-        if (st == 0) return 1;
-        if (!is_unique && st == 1) return 1;
+        if (const int has = hs_verdict(st, is_unique)) return has;
     }
     return 0;
 }
@@ -125,7 +122,7 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
             const size_t lds = g.lds;
             const int threads = g.threads, grid = g.grid;
             const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
-            const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+            const int cus = ctx_cus(ctx);
             if (pass == 0) XPG_TRY(dws.alloc(ctx, (size_t)(cus * 32 < nb ? cus * 32 : nb) * ws_words * 8));   // the largest grid of either pass
             XPG_TRY(hipMemsetAsync(dn.p, 0, (size_t)nb * 4, ctx->stream));
             XPG_TRY(lds_limit((const void *)k_mip_tree<R32>, ctx->device, lds));

@@ -424,7 +424,7 @@ template <class S> inline MipGeom mip_geom_cus(int cus, int nb, int rmax, int n,
     return g;
 }
 template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax, int n, bool is_max)
-{ return mip_geom_cus<S>(ctx->num_cus > 0 ? ctx->num_cus : 256, nb, rmax, n, is_max); }
+{ return mip_geom_cus<S>(ctx_cus(ctx), nb, rmax, n, is_max); }
 // The same batch with the tree walks on the device (mip_kernels.hip.h): one workgroup per problem. Returns
 // XPG_ERR_UNSUPPORTED where a node LP of the deepest path would not fit the LDS budget -- the caller then takes the
 // host controller below. free_var [extra] (host; may be NULL / 0): the batch's free variables, ascending.
@@ -459,7 +459,7 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
     // Speculative ceiling children (mip_kernels.hip.h, SP_*): for batches that leave the chip under-filled -- one tree per
     // walking workgroup, the batch lasts as long as its deepest tree -- helper workgroups behind the walkers solve the node
     // LPs the walks will need next, one helper per CU. Not with root equalities (the helper builds plain nodes only).
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = ctx_cus(ctx);
     const bool spec = eq_rows == 0 && grid == nb && nb <= 8 * cus;
     const int nhelp = spec ? cus : 0;        // (256 / 512 / 2048 helpers measured alike: 3.72 / 3.77 / 3.86 ms for 1024 knapsacks, 4.41 without)
     DevBuf dq;

@@ -221,7 +221,7 @@ int mip_batch_vc_hbm(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, 
     std::vector<int> fv;
     const bool pattern = vc_sign_pattern(vc, cols - 1, cols, fv);
     const int extra = pattern ? (int)fv.size() : 0;
-    const MipHbmPlan g = mip_hbm_plan<S>(pattern, leq_rows, eq_rows, cols, is_bin, is_max, extra, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const MipHbmPlan g = mip_hbm_plan<S>(pattern, leq_rows, eq_rows, cols, is_bin, is_max, extra, nb, ctx_cus(ctx));
     if (g.route == MIP_HBM_ROUTE_LDS) {
         const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes,
                                            allow_rational, eqs, eq_rows, fv.data(), extra);

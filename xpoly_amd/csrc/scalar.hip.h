@@ -33,6 +33,8 @@ inline const char * xpg_hook(const char * name)
     return nullptr;
 #endif
 }
+// An integer test hook, read once per process at each site that asks, 0 where unset (grid caps for the tests, A/B knobs of tools/lab).
+#define XPG_INT_HOOK(name_) ([] { static const int v_ = [] { const char * e_ = xpg_hook(name_); return e_ ? atoi(e_) : 0; }(); return v_; }())
 
 // diagnostic builds (-DXPG_TRACE): every committed pivot of workgroup 0 is printed (entering, leaving, row)
 #if defined(XPG_TRACE) && defined(__HIP_DEVICE_COMPILE__)

@@ -118,6 +118,55 @@ template <class S> __device__ __forceinline__ void vc_finish(S * y, const S * tg
     }
 }
 
+// The LP loop's steps that k_six_batch_vc, k_six_batch_vc_hbm and the two has_solution kernels (has_solution_batch.hip.h) share,
+// on plain pointers like the nf_* they drive: whether L, E and rest lie in the LDS block or in the slot is the caller's business.
+// Prologue: the workgroup's slot, fv at its cell 0 (whatever the shape is, in SixVcSlot and SixVcHbmSlot), vc_scan and what it
+// found. The device-memory kernels call it; k_six_batch_vc and k_has_solution_batch, with sm_solve_lp inlined, keep its five
+// lines: through the function their register allocation moved (profiles/vc_kernels_shared_isa.txt).
+template <class S> struct VcProlog { S * slot; int * fv; bool general; int nfree, n; };
+template <class S> __device__ __forceinline__ VcProlog<S> vc_prologue(const S * vc, int cols, unsigned long long * slots, unsigned long long slot_cells,
+                                                                      int * hdr)
+{
+    const int n0 = cols - 1;
+    VcProlog<S> p;
+    p.slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
+    p.fv = (int *)p.slot;
+    p.general = vc_scan<S>(vc, n0, cols, p.fv, hdr);
+    p.nfree = hdr[0]; p.n = n0 + p.nfree;
+    return p;
+}
+// Every LP of the launch ends XPG_ERR_UNSUPPORTED (a general vc, a shape the launch was not sized for). tid, nt: threadIdx.x and
+// blockDim.x as the kernel read them at its top, here and in vc_stage.
+template <class S> __device__ __forceinline__ void vc_end_all(int tid, int nt, int nb, int32_t * out_status, S * out_v, uint32_t * out_pivots)
+{
+    for (int lp = (int)blockIdx.x * nt + tid; lp < nb; lp += (int)gridDim.x * nt) {
+        out_status[lp] = XPG_ERR_UNSUPPORTED; out_v[lp] = zero<S>();
+        if (out_pivots) out_pivots[lp] = 0u;
+    }
+}
+// Stage: problem lp's cells as they lie, whole rows by consecutive lanes, between two barriers.
+template <class S> __device__ __forceinline__ void vc_stage(int tid, int nt, const S * leq, int lcells, const S * eqs, int ecells, int lp, S * L, S * E)
+{
+    __syncthreads();                                             // the LP before is through with the LDS block, the slot and hdr
+    const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
+    for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
+    for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
+    __syncthreads();
+}
+// Reshape (normalize_dev.hip.h): L folded in place, then the normalised objective and N. Returns nf_convert_eq's answer: the
+// equalities kept as pairs (the normal form has leq_rows + 2 of them rows), or < 0: that LP alone ends XPG_ERR_REF_UNDEFINED and
+// never meets the pivot loop. Behind nf_form's barrier L / E are read: where they lie in the LDS block, that is the solver's.
+template <class S> __device__ __forceinline__ int vc_reshape(S * L, int leq_rows, int cols, const S * E, int eq_rows, int * rest, int * hdr, const S * tg,
+                                                             const int * fv, int nfree, S * obj, S * N)
+{
+    const EqRows<S> eq = {E, cols};
+    const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq, eq_rows, rest, hdr);
+    if (nrest < 0) return nrest;
+    nf_objective<S>(tg, cols, fv, nfree, obj);
+    nf_form<S>(L, leq_rows, cols, eq, rest, nrest, fv, nfree, N);
+    return nrest;
+}
+
 // One workgroup per LP, grid-stride over the batch. vc is read on the device (the _dev entry points hold it there): every
 // workgroup derives the free list once; a vc that is no sign pattern, or a normal form beyond the launch's LDS, ends
 // every LP XPG_ERR_UNSUPPORTED (the host-array entry point has sent such a batch to six_solve instead and never launches).
@@ -130,15 +179,15 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int n0 = cols - 1;
+    const int n0 = cols - 1;                                     // (vc_prologue's lines: through it this kernel's spills move)
     S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
-    int * const fv = (int *)slot;                                // (SixVcSlot::fv == 0 whatever nfree is)
+    int * const fv = (int *)slot;
     const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
     const int nfree = hdr[0], n = n0 + nfree;
     const SixVcPlan plan = six_vc_plan<S>(!general, nfree, leq_rows, eq_rows, cols, is_max != 0);
     const SixVcSlot sl = six_vc_slot(leq_rows, eq_rows, cols, nfree);
     if (!plan.device || plan.lds > (size_t)lds_bytes || sl.work_cells * 8 > (size_t)lds_bytes) {
-        for (int lp = (int)blockIdx.x * nt + tid; lp < nb; lp += (int)gridDim.x * nt) { out_status[lp] = XPG_ERR_UNSUPPORTED; out_v[lp] = zero<S>(); }
+        vc_end_all<S>(tid, nt, nb, out_status, out_v, nullptr);
         return;
     }
     S * const N = slot + sl.N; S * const obj = slot + sl.obj; S * const y = slot + sl.y; S * const vout = slot + sl.v;
@@ -148,24 +197,13 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
 
     for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
         const S * tg = tgtf + (size_t)lp * cols;
-        __syncthreads();                                         // the LP before is through with the LDS block, the slot and hdr
-        // ---- stage: the caller's cells as they lie, whole rows by consecutive lanes
-        {
-            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
-            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
-            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
-        }
-        __syncthreads();
-        // ---- reshape (normalize_dev.hip.h): L folded in place, then N and the normalised objective
-        const EqRows<S> eq_lds = {E, cols};
-        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_lds, eq_rows, rest, hdr);
-        if (nrest < 0) {                                         // this LP alone; it never meets the pivot loop
+        vc_stage<S>(tid, nt, leq, lcells, eqs, ecells, lp, L, E);
+        const int nrest = vc_reshape<S>(L, leq_rows, cols, E, eq_rows, rest, hdr, tg, fv, nfree, obj, N);
+        if (nrest < 0) {
             if (tid == 0) { out_status[lp] = XPG_ERR_REF_UNDEFINED; out_v[lp] = zero<S>(); }
             continue;
         }
         const int rows = leq_rows + 2 * nrest;
-        nf_objective<S>(tg, cols, fv, nfree, obj);
-        nf_form<S>(L, leq_rows, cols, eq_lds, rest, nrest, fv, nfree, N);    // (its barrier: L / E are read, the LDS block is the solver's)
         // ---- solve: the arrays and the code of a single call's launch (k_batch with nb = 1 on this normal form)
         Small<S> P;
         sm_carve(P, lds, is_max ? rows : n, is_max ? n : rows);
@@ -181,6 +219,12 @@ void k_six_batch_vc(int nb, const S * __restrict__ tgtf, const S * __restrict__ 
     }
 }
 
+// The scratch cut of the LDS-resident launches: grid x slot stays under SIX_VC_SCRATCH_MAX, with one workgroup at the least.
+inline long long six_vc_scratch_cut(long long grid, size_t slot_bytes)
+{
+    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / slot_bytes);
+    return grid > by_scratch ? (by_scratch > 0 ? by_scratch : 1) : grid;
+}
 // The launch of k_six_batch_vc for a shape the device route takes (six_batch_vc_dev asks it, and the route rule of
 // xpg_six_batch_vc_hbm_* reports it): nfree as six_batch_vc_dev takes it.
 struct SixVcGeom { size_t lds; int threads; long long grid; size_t slot_cells; };
@@ -198,8 +242,7 @@ template <class S> inline SixVcGeom six_vc_geometry(int nfree, int nb, int leq_r
     const int per_cu = (int)((160 * 1024) / q.lds) > 0 ? (int)((160 * 1024) / q.lds) : 1;
     q.grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
     if (q.grid > nb) q.grid = nb;
-    const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / (q.slot_cells * 8));
-    if (q.grid > by_scratch) q.grid = by_scratch > 0 ? by_scratch : 1;
+    q.grid = six_vc_scratch_cut(q.grid, q.slot_cells * 8);
     return q;
 }
 
@@ -218,7 +261,7 @@ int six_batch_vc_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, const S
     const size_t lds = q.lds;
     const int threads = q.threads;
     long long grid = q.grid;
-    static const int grid_cap = [] { const char * e = xpg_hook("XPG_SIX_VC_GRID"); return e ? atoi(e) : 0; }();   // tests: the grid-stride path at small nb
+    const int grid_cap = XPG_INT_HOOK("XPG_SIX_VC_GRID");        // tests: the grid-stride path at small nb
     if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
     const size_t need = (size_t)grid * q.slot_cells * 8;
     Scratch & slots = ctx->scratch[SCRATCH_SIX_VC];              // grown with head room, so a batch a little larger does not grow it again

@@ -62,6 +62,13 @@ __host__ __device__ inline SixVcHbmSlot six_vc_hbm_slot(int leq_rows, int eq_row
 //   HBM    a sign pattern past 64 KB: k_six_batch_vc_hbm, if eq_rows <= SIX_VC_MAX_EQ, the side arrays of the largest normal
 //          form fit 160 KB beside the kernel's static LDS and one slot fits the scratch cap
 //   OTHER  the host-array form solves per problem (six_solve), the _dev form returns XPG_ERR_UNSUPPORTED before any launch
+// Its device-memory half, which hs_plan (has_solution_batch.hip.h) decides by too: the grid (hbm_grid under SIX_VC_SCRATCH_MAX;
+// the scratch is grid x slot), or 0, refused: not `allowed`, side arrays past 160 KB beside the static LDS, a slot past the cap.
+inline int six_vc_hbm_grid(bool allowed, size_t lds, size_t slot, int nb, int num_cus)
+{
+    if (!allowed || lds + SIX_VC_HBM_LDS_STATIC > (size_t)160 * 1024 || slot > SIX_VC_SCRATCH_MAX) return 0;
+    return (int)hbm_grid(num_cus, SIX_VC_HBM_THREADS, SIX_VC_HBM_WAVES_PER_CU, lds + SIX_VC_HBM_LDS_STATIC, slot, SIX_VC_SCRATCH_MAX, nb);
+}
 struct SixVcHbmPlan {
     int route, nfree, Rmax, Vmax;
     size_t lds;             // LDS route: the largest normal form's small_lds_bytes; else hbm_side_bytes(Rmax, Vmax)
@@ -88,12 +95,8 @@ inline SixVcHbmPlan six_vc_hbm_plan(bool pattern, int nfree, int leq_rows, int e
     g.ld = (int)ld;
     g.slot = six_vc_hbm_slot(leq_rows, eq_rows, cols, cap, g.Rmax, g.ld).cells * 8;
     g.threads = SIX_VC_HBM_THREADS;
-    if (!pattern || eq_rows > SIX_VC_MAX_EQ || g.lds + SIX_VC_HBM_LDS_STATIC > (size_t)160 * 1024 || g.slot > SIX_VC_SCRATCH_MAX) {
-        g.route = SIX_VC_HBM_ROUTE_OTHER; g.grid = 0; g.scratch = 0;
-        return g;
-    }
-    g.route = SIX_VC_HBM_ROUTE_HBM;
-    g.grid = (int)hbm_grid(num_cus, g.threads, SIX_VC_HBM_WAVES_PER_CU, g.lds + SIX_VC_HBM_LDS_STATIC, g.slot, SIX_VC_SCRATCH_MAX, nb);
+    g.grid = six_vc_hbm_grid(pattern && eq_rows <= SIX_VC_MAX_EQ, g.lds, g.slot, nb, num_cus);
+    g.route = g.grid > 0 ? SIX_VC_HBM_ROUTE_HBM : SIX_VC_HBM_ROUTE_OTHER;
     g.scratch = (size_t)g.grid * g.slot;
     return g;
 }
@@ -133,19 +136,14 @@ void k_six_batch_vc_hbm(int nb, const S * __restrict__ tgtf, const S * __restric
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int hdr[4];                                       // [0]: the free variables, until all have read them; then nf_convert_eq's
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int n0 = cols - 1;
-    S * const slot = (S *)(slots + (size_t)blockIdx.x * slot_cells);
-    int * const fv = (int *)slot;                                // (SixVcHbmSlot::fv == 0 whatever the shape is)
-    const bool general = vc_scan<S>(vc, n0, cols, fv, hdr);
-    const int nfree = hdr[0], n = n0 + nfree;
+    const VcProlog<S> pr = vc_prologue<S>(vc, cols, slots, slot_cells, hdr);
+    S * const slot = pr.slot; const int * const fv = pr.fv;
+    const int nfree = pr.nfree, n = pr.n;
     const int rows_max = leq_rows + 2 * eq_rows;
     const int Rlp = is_max ? rows_max : n, Vlp = is_max ? n : rows_max;      // the largest normal form under the vc found
-    if (general || nfree > nfree_cap || eq_rows > (int)SIX_VC_MAX_EQ || Rlp > Rmax || Vlp + Rlp + 2 > ld ||
+    if (pr.general || nfree > nfree_cap || eq_rows > (int)SIX_VC_MAX_EQ || Rlp > Rmax || Vlp + Rlp + 2 > ld ||
         hbm_side_bytes<S>(Rlp, Vlp) > (size_t)lds_bytes) {
-        for (int lp = (int)blockIdx.x * nt + tid; lp < nb; lp += (int)gridDim.x * nt) {
-            out_status[lp] = XPG_ERR_UNSUPPORTED; out_v[lp] = zero<S>();
-            if (out_pivots) out_pivots[lp] = 0u;
-        }
+        vc_end_all<S>(tid, nt, nb, out_status, out_v, out_pivots);
         return;
     }
     const SixVcHbmSlot sl = six_vc_hbm_slot(leq_rows, eq_rows, cols, nfree_cap, Rmax, ld);
@@ -156,24 +154,13 @@ void k_six_batch_vc_hbm(int nb, const S * __restrict__ tgtf, const S * __restric
 
     for (int lp = (int)blockIdx.x; lp < nb; lp += (int)gridDim.x) {
         const S * tg = tgtf + (size_t)lp * cols;
-        __syncthreads();                                         // the LP before is through with the LDS block, the slot and hdr
-        // ---- stage: the caller's cells as they lie, whole rows by consecutive lanes
-        {
-            const S * gl = leq + (size_t)lp * lcells; const S * ge = eqs + (size_t)lp * ecells;
-            for (int t = tid; t < lcells; t += nt) L[t] = gl[t];
-            for (int t = tid; t < ecells; t += nt) E[t] = ge[t];
-        }
-        __syncthreads();
-        // ---- reshape (normalize_dev.hip.h) on the slot: L folded in place, then N and the normalised objective
-        const EqRows<S> eq_slot = {E, cols};
-        const int nrest = nf_convert_eq<S>(L, leq_rows, cols, eq_slot, eq_rows, rest, hdr);
-        if (nrest < 0) {                                         // this LP alone; it never meets the pivot loop
+        vc_stage<S>(tid, nt, leq, lcells, eqs, ecells, lp, L, E);
+        const int nrest = vc_reshape<S>(L, leq_rows, cols, E, eq_rows, rest, hdr, tg, fv, nfree, obj, N);    // on the slot
+        if (nrest < 0) {
             if (tid == 0) { out_status[lp] = XPG_ERR_REF_UNDEFINED; out_v[lp] = zero<S>(); if (out_pivots) out_pivots[lp] = 0u; }
             continue;
         }
         const int rows = leq_rows + 2 * nrest;
-        nf_objective<S>(tg, cols, fv, nfree, obj);
-        nf_form<S>(L, leq_rows, cols, eq_slot, rest, nrest, fv, nfree, N);
         // ---- solve: k_batch_hbm's, on the rows this LP has
         const SixVcHbmSolved solved = six_vc_hbm_solve<S>((XPG_AS_LDS unsigned char *)lds, (XPG_AS_GLOBAL S *)tab, ld, (XPG_AS_GLOBAL const S *)N,
                                                           (XPG_AS_GLOBAL const S *)obj, rows, n, is_max, max_iter, (XPG_AS_GLOBAL S *)y,
@@ -219,7 +206,7 @@ int six_batch_vc_hbm_dev(xpg_ctx * ctx, bool is_max, int nb, const S * tgtf, con
     rt = SixVcHbmRoute{0, 0, 0, -1, 0};
     if (!six_vc_args_ok(ctx, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, out_status, out_v, out_sol)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    const SixVcHbmPlan g = six_vc_hbm_plan<S>(true, -1, leq_rows, eq_rows, cols, is_max, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const SixVcHbmPlan g = six_vc_hbm_plan<S>(true, -1, leq_rows, eq_rows, cols, is_max, nb, ctx_cus(ctx));
     if (g.route == SIX_VC_HBM_ROUTE_OTHER) return XPG_ERR_UNSUPPORTED;
     if (g.route == SIX_VC_HBM_ROUTE_LDS) {
         const int rc = six_batch_vc_dev<S>(ctx, is_max, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, max_iter, -1, out_status, out_v, out_sol);
@@ -248,7 +235,7 @@ int six_batch_vc_hbm_host(xpg_ctx * ctx, int kind, bool is_max, int nb, const S 
     std::vector<int> fvar;
     const bool pattern = vc_sign_pattern(vc, cols - 1, cols, fvar);
     const int nfree = pattern ? (int)fvar.size() : 0;
-    const SixVcHbmPlan g = six_vc_hbm_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, is_max, nb, ctx->num_cus > 0 ? ctx->num_cus : 256);
+    const SixVcHbmPlan g = six_vc_hbm_plan<S>(pattern, nfree, leq_rows, eq_rows, cols, is_max, nb, ctx_cus(ctx));
     if (g.route != SIX_VC_HBM_ROUTE_HBM) {
         const int rc = six_batch_vc_host<S>(ctx, kind, is_max, nb, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, max_iter, out_status, out_v, out_sol);
         const SixVcRoute & r = six_vc_route();

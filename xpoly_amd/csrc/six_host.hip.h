@@ -191,6 +191,27 @@ inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, con
     return tgtf;
 }
 
+// Lineq::has_solution's rules, once for its single-problem front end and every form of the batched one. The verdict on one
+// solve's status (linsys.cpp:864-876): < 0 the reference is undefined here (passed through); 1 a solution exists -- the solve
+// succeeded, or ended unbounded where uniqueness is not demanded; 0: still open.
+__host__ __device__ inline int hs_verdict(int status, bool is_unique)
+{
+    return status < 0 ? status : (status == 0 || (status == 1 && !is_unique) ? 1 : 0);
+}
+// Without inequalities no solve runs. No rows at all: no solution. Equalities only: the reference sizes tgtf from leq
+// (linsys.cpp:851), XPG_ERR_REF_UNDEFINED as verdict and as the status of the first solve.
+struct HsNoLeq { int has, status0; };
+inline HsNoLeq hs_no_inequality(int eq_rows)
+{
+    return eq_rows == 0 ? HsNoLeq{0, (int)XPG_HS_NOT_RUN} : HsNoLeq{(int)XPG_ERR_REF_UNDEFINED, (int)XPG_ERR_REF_UNDEFINED};
+}
+// The three outputs of system b: the verdict, and the statuses of maxm and minm where the caller asked for them.
+__host__ __device__ inline void hs_store(int b, int has, int s0, int s1, int32_t * out_has, int32_t * out_status)
+{
+    out_has[b] = has;
+    if (out_status) { out_status[2 * (size_t)b] = s0; out_status[2 * (size_t)b + 1] = s1; }
+}
+
 // The cells of the normal form on the host (the LDS route's small problems).
 template <class S>
 int normalize_cells_host(const S * eqs, const S * leq, NormalForm<S> & F)

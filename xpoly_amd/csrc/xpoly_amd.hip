@@ -109,6 +109,30 @@ XPG_SIX_VC_INSTANCES(template, R32)
 }
 #endif
 
+#if XPG_IN(1) || XPG_IN(5) || XPG_IN(7)
+namespace {
+// What the host-only test views (xpg_test_*_plan) know of a vc: whether it is a sign pattern; nfree as the plans take it (the
+// free variables of a pattern, 0 for a general vc, -1 for vc == NULL: the _dev forms' view); and the columns without a nonzero
+// (lpsol.h:1322), which a general vc has too.
+struct VcView { bool pattern; int nfree, zero_cols; };
+template <class S> VcView vc_view(const void * vc, int vc_rows, int cols)
+{
+    VcView v = {true, -1, 0};
+    if (!vc) return v;
+    const S * c = (const S *)vc;
+    std::vector<int> fv;
+    v.pattern = vc_sign_pattern(c, vc_rows, cols, fv);
+    v.nfree = v.pattern ? (int)fv.size() : 0;
+    for (int j = 0; j < cols - 1; j++) {
+        bool nz = false;
+        for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<S>());
+        v.zero_cols += nz ? 0 : 1;
+    }
+    return v;
+}
+}
+#endif
+
 static_assert(sizeof(F64) == 8 && sizeof(R32) == 8, "both scalars are 8 bytes");
 static_assert(sizeof(xpg_rat32) == sizeof(R32), "ABI layout of a rational");
 
@@ -554,8 +578,7 @@ int xpg_lp_loop_info(xpg_lp * lp, int32_t * out, int n)
     int32_t f[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (lp->impl->kind == 0) ((Lp<F64> *)lp->impl)->loop_info(f);
     else ((Lp<R32> *)lp->impl)->loop_info(f);
-    for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 
 #ifdef XPG_STAMPS
@@ -689,8 +712,7 @@ int xpg_test_warm_batch_geometry(int rows, int cols, int is_bin, int nb, long lo
     const WbPlan P = wb_plan(rows, cols, is_bin, nb);
     const long long f[9] = { (long long)P.lds, P.refused, P.S.depth_cap, P.S.mcap, P.S.wcap, (long long)P.S.snap_stride, (long long)P.S.tree_stride,
                              P.chunk, P.launches };
-    for (int k = 0; k < n && k < 9; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 
 } // extern "C"
@@ -736,8 +758,7 @@ int xpg_six_last_profile(double * out_ms, int n)
     if (!out_ms || n < 0) return XPG_ERR_SHAPE;
     const SixProfile & p = six_profile();
     const double f[9] = { p.total_ms, p.reshape_ms, p.create_ms, p.dual_ms, p.solve_ms, p.read_ms, p.destroy_ms, (double)p.route, (double)p.pivots };
-    for (int k = 0; k < n && k < 9; k++) out_ms[k] = f[k];
-    return 0;
+    return copy_fields(out_ms, n, f);
 }
 int xpg_test_normalize(xpg_ctx * ctx, int kind, const void * tgtf, const void * vc, int vc_rows, const void * eq, int eq_rows,
                        const void * leq, int leq_rows, int cols, void * out_dev_cells, void * out_host_cells, long long cap_cells,
@@ -862,8 +883,7 @@ int xpg_six_batch_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const SixVcRoute & r = six_vc_route();
     const long long f[3] = { r.device, r.fallback, r.free_vars };
-    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test view: the route rule of xpg_six_batch_vc_* and the sizes it decides by
 int xpg_test_six_batch_vc_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max, long long * out, int n)
@@ -871,23 +891,11 @@ int xpg_test_six_batch_vc_plan(int kind, const void * vc, int vc_rows, int leq_r
     if (!vc || !out || n < 0 || cols < 2 || vc_rows != cols - 1 || leq_rows < 0 || eq_rows < 0 || (leq_rows == 0 && eq_rows == 0) ||
         (kind != 0 && kind != 1))
         return XPG_ERR_SHAPE;
-    std::vector<int> fv;
-    SixVcPlan p;
-    int nfree = 0;
-    if (kind == 0) {
-        const F64 * c = (const F64 *)vc;
-        const bool pat = vc_sign_pattern(c, vc_rows, cols, fv);
-        for (int j = 0; j < cols - 1; j++) { bool nz = false; for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<F64>()); nfree += nz ? 0 : 1; }
-        p = six_vc_plan<F64>(pat, nfree, leq_rows, eq_rows, cols, is_max != 0);
-    } else {
-        const R32 * c = (const R32 *)vc;
-        const bool pat = vc_sign_pattern(c, vc_rows, cols, fv);
-        for (int j = 0; j < cols - 1; j++) { bool nz = false; for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<R32>()); nfree += nz ? 0 : 1; }
-        p = six_vc_plan<R32>(pat, nfree, leq_rows, eq_rows, cols, is_max != 0);
-    }
+    const VcView v = kind == 0 ? vc_view<F64>(vc, vc_rows, cols) : vc_view<R32>(vc, vc_rows, cols);
+    const SixVcPlan p = kind == 0 ? six_vc_plan<F64>(v.pattern, v.zero_cols, leq_rows, eq_rows, cols, is_max != 0)
+                                  : six_vc_plan<R32>(v.pattern, v.zero_cols, leq_rows, eq_rows, cols, is_max != 0);
     const long long f[5] = { p.device, p.nfree, p.rows_max, p.n, (long long)p.lds };
-    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 
 } // extern "C"
@@ -1394,8 +1402,7 @@ int xpg_mip_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const MipRoute & r = mip_route();
     const long long f[3] = { r.device_trees, r.host_trees, r.free_vars };
-    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test views: the vc classifier and the LDS fit test the MIP entry points route by
 int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free)
@@ -1420,8 +1427,7 @@ int xpg_test_batch_geometry(int kind, int R, int V, int nb, int num_cus, long lo
     if (!out || n < 0 || R <= 0 || V <= 0 || nb <= 0 || num_cus <= 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
     const BatchGeom g = kind == 0 ? batch_geometry<F64>(R, V, nb, num_cus) : batch_geometry<R32>(R, V, nb, num_cus);
     const long long f[10] = { (long long)g.lds, g.refused, g.cells, g.threads, g.per_cu, g.five, g.grid, g.seats, g.slice_shape, g.slice_crowded };
-    for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 } // extern "C"
 #endif
@@ -1460,8 +1466,7 @@ int xpg_six_batch_hbm_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const BatchHbmRoute & r = batch_hbm_route();
     const long long f[3] = { r.lds, r.hbm, r.grid };
-    for (int k = 0; k < n && k < 3; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test view: what xpg_six_batch_hbm_* would do with nb LPs solved as R rows x V variables on num_cus compute units
 int xpg_test_batch_hbm_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n)
@@ -1469,8 +1474,7 @@ int xpg_test_batch_hbm_geometry(int kind, int R, int V, int nb, int num_cus, lon
     if (!out || n < 0 || R <= 0 || V <= 0 || nb <= 0 || num_cus <= 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
     const HbmGeom g = kind == 0 ? batch_hbm_geometry<F64>(R, V, nb, num_cus) : batch_hbm_geometry<R32>(R, V, nb, num_cus);
     const long long f[7] = { g.route, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
-    for (int k = 0; k < n && k < 7; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 } // extern "C"
 #endif
@@ -1516,8 +1520,7 @@ int xpg_six_batch_vc_hbm_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const SixVcHbmRoute & r = six_vc_hbm_route();
     const long long f[5] = { r.lds, r.hbm, r.fallback, r.free_vars, r.grid };
-    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test view: the route rule of xpg_six_batch_vc_hbm_* and the sizes it decides by; vc == NULL: the _dev forms' view
 int xpg_test_six_batch_vc_hbm_plan(int kind, const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int is_max, int nb, int num_cus,
@@ -1526,18 +1529,11 @@ int xpg_test_six_batch_vc_hbm_plan(int kind, const void * vc, int vc_rows, int l
     if (!out || n < 0 || cols < 2 || (vc && vc_rows != cols - 1) || leq_rows < 0 || eq_rows < 0 || (leq_rows == 0 && eq_rows == 0) || nb <= 0 ||
         num_cus <= 0 || (kind != 0 && kind != 1))
         return XPG_ERR_SHAPE;
-    std::vector<int> fv;
-    SixVcHbmPlan g;
-    if (kind == 0) {
-        const bool pat = vc ? vc_sign_pattern((const F64 *)vc, vc_rows, cols, fv) : true;
-        g = six_vc_hbm_plan<F64>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus);
-    } else {
-        const bool pat = vc ? vc_sign_pattern((const R32 *)vc, vc_rows, cols, fv) : true;
-        g = six_vc_hbm_plan<R32>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus);
-    }
+    const VcView v = kind == 0 ? vc_view<F64>(vc, vc_rows, cols) : vc_view<R32>(vc, vc_rows, cols);
+    const SixVcHbmPlan g = kind == 0 ? six_vc_hbm_plan<F64>(v.pattern, v.nfree, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus)
+                                     : six_vc_hbm_plan<R32>(v.pattern, v.nfree, leq_rows, eq_rows, cols, is_max != 0, nb, num_cus);
     const long long f[10] = { g.route, g.nfree, g.Rmax, g.Vmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
-    for (int k = 0; k < n && k < 10; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 } // extern "C"
 #endif
@@ -1569,8 +1565,7 @@ int xpg_mip_hbm_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const MipHbmRoute & r = mip_hbm_route();
     const long long f[5] = { r.lds, r.hbm, r.host, r.free_vars, r.grid };
-    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test view: the route rule of xpg_mip_batch_vc_hbm_* and the sizes it decides by
 int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int cols, int is_bin, int is_max, int extra, int nb, int num_cus,
@@ -1584,8 +1579,7 @@ int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int 
                                    : mip_hbm_plan<R32>(pattern != 0, leq_rows, eq_rows, cols, is_bin != 0, is_max != 0, ex, nb, num_cus);
     const long long f[11] = { g.route, g.extra, g.R, g.V, (long long)g.lds, (long long)g.slot, g.ld, (long long)g.ws_words, g.threads, g.grid,
                               (long long)g.scratch };
-    for (int k = 0; k < n && k < 11; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 } // extern "C"
 #endif
@@ -1626,19 +1620,16 @@ int xpg_has_solution_batch_last_route(long long * out, int n)
     if (!out || n < 0) return XPG_ERR_SHAPE;
     const HsRoute & r = hs_route();
     const long long f[5] = { r.lds, r.hbm, r.host, r.second, r.grid };
-    for (int k = 0; k < n && k < 5; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 // host-only test view: the route rule of xpg_has_solution_batch_* and the sizes it decides by; vc == NULL: the _dev form's view
 int xpg_test_has_solution_batch_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus, long long * out, int n)
 {
     if (!out || n < 0 || cols < 2 || (vc && vc_rows != cols - 1) || leq_rows <= 0 || eq_rows < 0 || nb <= 0 || num_cus <= 0) return XPG_ERR_SHAPE;
-    std::vector<int> fv;
-    const bool pat = vc ? vc_sign_pattern((const R32 *)vc, vc_rows, cols, fv) : true;
-    const HsPlan g = hs_plan<R32>(pat, vc ? (pat ? (int)fv.size() : 0) : -1, leq_rows, eq_rows, cols, nb, num_cus);
+    const VcView v = vc_view<R32>(vc, vc_rows, cols);
+    const HsPlan g = hs_plan<R32>(v.pattern, v.nfree, leq_rows, eq_rows, cols, nb, num_cus);
     const long long f[9] = { g.route, g.nfree, g.Rmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
-    for (int k = 0; k < n && k < 9; k++) out[k] = f[k];
-    return 0;
+    return copy_fields(out, n, f);
 }
 } // extern "C"
 #endif
