@@ -563,9 +563,16 @@ int xpg_test_mip_hbm_plan(int kind, int pattern, int leq_rows, int eq_rows, int 
 /* Host-only views for tests (no device needed).  vc_pattern: 1 when vc [vc_rows][cols] of kind (0 fp64, 1 rational) is a
  * sign pattern, with out_free[j] = 1 for every free variable j < cols - 1; 0 when it is general; XPG_ERR_SHAPE unless
  * vc_rows == cols - 1.  mip_fits: 1 / 0, whether the device tree walk takes a problem of that shape with `extra` free
- * variables (the LDS budget of its largest node LP). */
+ * variables (the LDS budget of its largest node LP, maximising and minimising).  mip_front_route: 1 / 0, whether the one
+ * route rule of xpg_mip_maxm / minm_*, xpg_mip_batch_*, xpg_mip_batch_eq_* and xpg_mip_batch_vc_* sends a call of that
+ * shape to the device tree walk or to the host controller -- fit: the fit test the entry point asks with (1: mip_fits, all
+ * of them but xpg_mip_batch_*; 0: the LDS of the direction is_max alone, xpg_mip_batch_*), pattern / extra: vc_pattern's
+ * verdict and free variables (1 / 0 for x >= 0), allowed: 0 stands for XPG_MIP_DEVICE=0; XPG_ERR_SHAPE for a fit or kind
+ * that is neither 0 nor 1, cols < 2, a negative count or no row at all. */
 int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free);
 int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin, int extra);
+int xpg_test_mip_front_route(int fit, int kind, int pattern, int extra, int leq_rows, int eq_rows, int cols, int is_bin,
+                             int is_max, int allowed);
 /* Host-only view for tests (no device needed): the launch geometry of the batched LP kernel (xpg_six_batch_*) for nb LPs
  * that are solved as R rows x V variables (maxm: R = m, V = cols - 1; minm solves the dual: the two swap) on a device of
  * num_cus compute units.  Fills min(n, 10) entries: out[0] LDS bytes of one LP, [1] 1 when the call is refused

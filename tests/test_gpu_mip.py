@@ -372,3 +372,42 @@ def test_mip_batch_with_root_equalities_matches_oracle(ctx, port, kind):
                     compared += 1
                     seen.add(int(want[0]))
     assert compared > 200 and 0 in seen
+
+
+@pytest.mark.parametrize("kind", [RAT, F64])
+def test_mip_batch_and_mip_batch_vc_route_a_tall_shape_differently_and_agree(ctx, port, kind):
+    """112 inequalities, 8 integer variables: the largest node LP (120 rows) fits 64 KB of LDS minimising (solved as the
+    dual, 8 x 120) and not maximising (120 x 8, the tableau alone 124 800 bytes). xpg_mip_batch_* asks for the direction
+    of the call only and walks the minimisation on the device; xpg_mip_batch_vc_* asks for both directions and hands both
+    calls to the host controller. The rows are 14 copies of x_j <= u_j with a positive integer objective, so the root
+    LP's optimum is integral and every tree is its root: status, optimum and solution (rows of unsolved problems stay as
+    the caller passed them) are the same bits on either route and the oracle's."""
+    from xpoly_amd.six import mip_batch, mip_batch_vc, mip_last_route
+    nb, nv, copies = 4, 8, 14
+    rng = np.random.default_rng(112)
+    u = rng.integers(1, 10, size=(nb, nv)); c = rng.integers(1, 10, size=(nb, nv))
+    unit = np.zeros((nb, nv, nv + 1), dtype=np.int32)
+    unit[:, np.arange(nv), np.arange(nv)] = 1; unit[:, :, nv] = u
+    leq = np.tile(unit, (1, copies, 1)); tg = np.concatenate([c, np.zeros((nb, 1), dtype=np.int64)], axis=1).astype(np.int32)
+    assert leq.shape == (nb, 112, 9)
+    conv = (lambda a: a.astype(np.float64)) if kind == F64 else gen.to_rat
+    leq, tg, vc = conv(leq), conv(tg), gen.vc_nonneg(nv, kind == F64)
+    if kind == RAT:
+        vc = gen.to_rat(vc)
+    for is_max in (False, True):
+        a = mip_batch(ctx, is_max, False, tg, leq, kind=kind)
+        ra = mip_last_route()
+        b = mip_batch_vc(ctx, is_max, False, tg, vc, leq, kind=kind)
+        rb = mip_last_route()
+        print("kind", kind, "is_max", is_max, "mip_batch", ra, "mip_batch_vc", rb)
+        assert ra == (dict(device_trees=0, host_trees=nb, free_vars=0) if is_max else dict(device_trees=nb, host_trees=0, free_vars=0))
+        assert rb == dict(device_trees=0, host_trees=nb, free_vars=0)
+        assert a[3] == b[3] == nb                                   # one node per tree
+        for x, y in zip(a[:3], b[:3]):
+            assert x.tobytes() == y.tobytes(), is_max
+        for i in range(nb):
+            want = port.mip_solve(kind, is_max, False, tg[i], vc, None, leq[i])
+            assert a[0][i] == want[0] and (want[0] == 0 or not is_max), (is_max, i, a[0][i], want[0])    # (every maxm is solved)
+            assert np.array_equal(np.atleast_1d(a[1][i]), np.atleast_1d(want[1])), (is_max, i)
+            if want[0] == 0:
+                assert np.array_equal(a[2][i].reshape(-1), np.asarray(want[2]).reshape(-1)), (is_max, i)

@@ -30,7 +30,7 @@ SYMBOLS = [
     "xpg_lineq_fme_batch_packed_rat32", "xpg_trim", "xpg_lp_chain_aborts", "xpg_test_sweep_tile", "xpg_test_pick_ld", "xpg_test_canon_ops_rat32", "xpg_test_any_ops_rat32",
     "xpg_six_batch_f64_ragged", "xpg_six_batch_rat32_ragged", "xpg_dep_is_empty_batch_ragged_rat32",
     "xpg_lineq_reduce_batch_ragged_rat32", "xpg_lineq_fme_batch_ragged_rat32", "xpg_lineq_reduce_batch_packed_rat32", "xpg_lp_loop_info", "xpg_test_normalize", "xpg_dep_is_empty_batch_mode_rat32",
-    "xpg_mip_batch_vc_rat32", "xpg_mip_batch_vc_f64", "xpg_mip_last_route", "xpg_test_vc_pattern", "xpg_test_mip_fits",
+    "xpg_mip_batch_vc_rat32", "xpg_mip_batch_vc_f64", "xpg_mip_last_route", "xpg_test_vc_pattern", "xpg_test_mip_fits", "xpg_test_mip_front_route",
     "xpg_test_batch_geometry", "xpg_test_warm_batch_geometry",
     "xpg_six_batch_vc_f64", "xpg_six_batch_vc_rat32", "xpg_six_batch_vc_f64_dev", "xpg_six_batch_vc_rat32_dev",
     "xpg_six_batch_last_route", "xpg_test_six_batch_vc_plan",

@@ -83,13 +83,12 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
     // the symbols as free variables: the whole test stays on the device -- reduce, the feasibility objectives, the integer
     // maxm walk, the minm walk of what that left open -- and only the verdicts come back. With symbols, move2var runs on the
     // host in front of the upload; the walks' free list is the caller's free variables, then every symbol.
-    static const bool on_dev = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
     const bool widen_dev = nsym > 0 && symbols_as_vars != 0;
     std::vector<int> fv;
     const bool pattern = !vc_in || vc_sign_pattern(vc_in, rhs_idx, rhs_idx + 1, fv);
     if (widen_dev) for (int j = rhs_idx; j < last; j++) fv.push_back(j);
     const int extra = (int)fv.size();
-    if (on_dev && (nsym == 0 || widen_dev) && pattern && mip_device_fits<R32>(rows, cols, false, 0, extra) &&
+    if (mip_device_allowed() && (nsym == 0 || widen_dev) && pattern && mip_device_fits<R32>(rows, cols, false, 0, extra) &&
         lineq_lds_bytes(rows, cols) <= 160 * 1024 && rows <= 32767) {
         const int n = cols - 1, rmax = rows + n, depth = n + 2;
         const size_t bm = (size_t)nb * rows * cols * 8, bt = (size_t)nb * cols * 8;
@@ -119,18 +118,14 @@ inline int dep_is_empty_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows,
         for (int pass = 0; pass < 2; pass++) {
             const bool is_max = pass == 0;
             const MipGeom g = mip_geom<R32>(ctx, nb, rmax, n + extra, is_max);
-            const size_t lds = g.lds;
-            const int threads = g.threads, grid = g.grid;
             const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
             const int cus = ctx_cus(ctx);
             if (pass == 0) XPG_TRY(dws.alloc(ctx, (size_t)(cus * 32 < nb ? cus * 32 : nb) * ws_words * 8));   // the largest grid of either pass
             XPG_TRY(hipMemsetAsync(dn.p, 0, (size_t)nb * 4, ctx->stream));
-            XPG_TRY(lds_limit((const void *)k_mip_tree<R32>, ctx->device, lds));
-            hipLaunchKernelGGL((k_mip_tree<R32>), dim3(grid), dim3(threads), lds, ctx->stream, nb, (const R32 *)dt.p, (const R32 *)dm.p,
-                               rows, cols, is_max ? 1 : 0, 0, rmax, depth, (unsigned long long *)dws.p, ws_words,
-                               (int32_t *)dst.p, (R32 *)dv.p, (R32 *)0, (int *)dn.p, (const int *)dk.p, (const int *)dact.p, (const uint8_t *)0,
-                               (const R32 *)0, 0, grid, (int *)0, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
-            XPG_TRY(hipGetLastError());
+            // ragged rows kept[b], the still-open marks, no solution wanted, no helpers
+            rc = mip_tree_launch<R32>(ctx, g, 0, nb, dt.p, dm.p, rows, cols, is_max, false, rmax, depth, dws.p, ws_words, dst.p, dv.p, (void *)0, dn.p,
+                                      dk.p, dact.p, (const void *)0, (const void *)0, 0, (void *)0, dfv.p, extra);
+            if (rc) return rc;
             XPG_TRY(hipMemcpyAsync(pass == 0 ? nodes_a.data() : nodes_b.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
             hipLaunchKernelGGL(k_dep_update, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, (const int32_t *)dst.p,
                                (int *)dact.p, (int32_t *)demp.p);

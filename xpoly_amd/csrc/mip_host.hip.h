@@ -259,9 +259,12 @@ inline MipPool & mip_pool() { static MipPool p; return p; }
 template <class F> inline void mip_parallel_for(size_t n, F f) { mip_pool().run(n, std::function<void(size_t)>(f)); }
 
 // Which route the trees of the calling thread's last MIP / has_solution / dep_is_empty call took (xpg_mip_last_route):
-// answers are the same on both routes, so this is the only way to tell them apart. Reset by the C entry points.
+// answers are the same on both routes, so this is the only way to tell them apart. Reset by the C entry points that open with
+// XPG_BIND_MIP, by nothing below them: has_solution's two walks add up.
 struct MipRoute { long long device_trees, host_trees, free_vars; };
 inline MipRoute & mip_route() { static thread_local MipRoute r = {0, 0, 0}; return r; }
+// How a C entry point that resets them opens: the handle's device bound, the counters cleared.
+#define XPG_BIND_MIP(ctx_) XPG_BIND(ctx_); xpg::mip_route() = xpg::MipRoute{0, 0, 0}
 
 // Advances every task to completion; node LPs of equal shape share one kernel launch.
 template <class S> int run_mip_tasks(xpg_ctx * ctx, int kind, std::vector<MipTask<S> > & tasks)
@@ -338,56 +341,15 @@ template <class S> int run_mip_tasks(xpg_ctx * ctx, int kind, std::vector<MipTas
     }
 }
 
-template <class S> inline bool mip_device_fits(int leq_rows, int cols, bool is_bin, int eq_rows = 0, int extra = 0);
-template <class S>
-int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
-                     int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes,
-                     const uint8_t * allow_rational, const S * eqs, int eq_rows, const int * free_var = (const int *)0, int extra = 0);
+// ---- The host half of the MIP entry points, each step stated once: the switch, the fit test, the route rule, the transfer
+// object of a one-launch batch, the launcher of k_mip_tree, the device route, the controller's end and the front. ----------
 
-template <class S>
-int mip_batch_vc_host(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
-                      const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
-                      long long * out_nodes);
-
-// MIP::maxm / minm (lpsol.h:2636-2657, :2681-2702).
-template <class S>
-int mip_solve(xpg_ctx * ctx, int kind, bool is_max, bool is_bin, const S * tgtf, const S * vc, int vc_rows,
-              const S * eqs, int eq_rows, const S * leq, int leq_rows, int cols, const uint8_t * allow_rational,
-              S * out_v, S * out_sol, long * out_nodes)
+// XPG_MIP_DEVICE=0 keeps every tree with the host controller (A/B runs). Read once per process, here alone: mip_front and
+// dep_is_empty_batch (mip_front.hip.h) both ask this reader.
+inline bool mip_device_allowed()
 {
-    if (!ctx || !tgtf || !vc || !out_v || cols < 2 || vc_rows != cols - 1 || eq_rows < 0 || leq_rows < 0 ||
-        (eq_rows == 0 && leq_rows == 0) || (eq_rows > 0 && !eqs) || (leq_rows > 0 && !leq))
-        return XPG_ERR_SHAPE;
-    // a vc that is a sign pattern (every variable x >= 0 or free: vc_sign_pattern, six_host.hip.h) with inequalities and / or
-    // equalities at the root, with or without a rational_indicator, is what the device tree walk takes where its node LPs --
-    // widened by one twin per free variable -- fit; variables bounded otherwise stay with the host controller
-    static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_device) {
-        std::vector<int> fv;
-        if (vc_sign_pattern(vc, vc_rows, cols, fv) && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows, (int)fv.size())) {
-            int32_t st = 0; long long nodes = 0;
-            std::vector<S> sol((size_t)cols, zero<S>());
-            if (out_sol) for (int j = 0; j < cols; j++) sol[(size_t)j] = out_sol[j];
-            const int rc = mip_batch_device<S>(ctx, 1, is_max, is_bin, tgtf, leq, leq_rows, cols, &st, out_v, sol.data(), &nodes, allow_rational, eqs, eq_rows,
-                                               fv.data(), (int)fv.size());
-            if (rc != XPG_ERR_UNSUPPORTED) {
-                if (rc) return rc;
-                if (st == XPG_IP_SUCC && out_sol) for (int j = 0; j < cols; j++) out_sol[j] = sol[(size_t)j];
-                if (out_nodes) *out_nodes = (long)nodes;
-                return st;
-            }
-        }
-    }
-    std::vector<MipTask<S> > tasks(1);
-    tasks[0].start(make_problem(tgtf, vc, vc_rows, eqs, eq_rows, leq, leq_rows, cols), is_max, is_bin, allow_rational);
-    int rc = run_mip_tasks(ctx, kind, tasks);
-    if (rc) return rc;
-    const MipTask<S> & T = tasks[0];
-    *out_v = T.v;
-    if (T.final_status == XPG_IP_SUCC && out_sol && (int)T.sol.size() == cols)
-        for (int j = 0; j < cols; j++) out_sol[j] = T.sol[j];
-    if (out_nodes) *out_nodes = T.nodes;
-    return T.final_status;
+    static const bool on = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
+    return on;
 }
 
 // Whether the node LPs of the deepest path fit the device tree walk's LDS budget, maximising and minimising.
@@ -425,9 +387,95 @@ template <class S> inline MipGeom mip_geom_cus(int cus, int nb, int rmax, int n,
 }
 template <class S> inline MipGeom mip_geom(const xpg_ctx * ctx, int nb, int rmax, int n, bool is_max)
 { return mip_geom_cus<S>(ctx_cus(ctx), nb, rmax, n, is_max); }
-// The same batch with the tree walks on the device (mip_kernels.hip.h): one workgroup per problem. Returns
-// XPG_ERR_UNSUPPORTED where a node LP of the deepest path would not fit the LDS budget -- the caller then takes the
-// host controller below. free_var [extra] (host; may be NULL / 0): the batch's free variables, ascending.
+
+// Which fit test an entry point puts in front of the device tree walk -- the one difference between the entry points that
+// the rule below keeps, as found:
+//   MIP_FIT_BOTH    mip_device_fits: the largest node LP fits 64 KB of LDS maximising AND minimising, and its equality list
+//                   the node (mip_solve, mip_batch_eq, mip_batch_vc)
+//   MIP_FIT_LAUNCH  what mip_batch_device itself refuses: the LDS of the direction the call asks for, alone (mip_batch).
+//                   112 inequalities in 8 integer variables, minimising: the device under this test, the host controller
+//                   under the other.
+// Whether the two should be one is a decision of its own, to be made with a timing.
+enum MipFit { MIP_FIT_LAUNCH = 0, MIP_FIT_BOTH = 1 };
+// THE route rule of mip_front (the front and xpg_test_mip_front_route both ask it): true = the device tree walk
+// (mip_batch_device), false = the host controller (mip_batch_vc_host). pattern / extra: whether vc is a sign pattern
+// (vc_sign_pattern, six_host.hip.h) and its free variables; allowed: mip_device_allowed().
+template <class S>
+inline bool mip_front_route(MipFit fit, bool pattern, int extra, int leq_rows, int eq_rows, int cols, bool is_bin, bool is_max, bool allowed)
+{
+    if (!allowed || !pattern) return false;
+    if (fit == MIP_FIT_BOTH) return mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows, extra);
+    const int n = cols - 1 + extra, rmax = mip_rmax(leq_rows, eq_rows, cols - 1, is_bin);
+    return small_lds_bytes<S>(is_max ? rmax : n, is_max ? n : rmax) <= 64 * 1024;     // mip_geom's lds
+}
+
+// The device side of a one-launch MIP batch of 8-byte cells (k_mip_tree, k_mip_tree_hbm), in the manner of BatchIo
+// (ctx.hip.h): the caller's arrays, the workgroups' workspaces, the answers. The caller's out_sol goes up and the kernels
+// write the rows of solved trees only, so what comes down holds the caller's rows wherever a tree found no solution.
+struct MipIo {
+    DevBuf dfv, dl, dt, dws, dst, dv, dsol, dn, dal, de, dq;
+    // free_var [extra], eqs and allow_rational where the batch has them (their blocks stay NULL otherwise); ws_bytes: the
+    // workspaces of all workgroups; queue_bytes > 0: dq, a zeroed block of that size (k_mip_tree's speculation queue)
+    int up(xpg_ctx * ctx, int nb, const void * tgtf, const void * leq, int leq_rows, const void * eqs, int eq_rows, int cols,
+           const uint8_t * allow_rational, const int * free_var, int extra, const void * out_sol, size_t ws_bytes, size_t queue_bytes = 0)
+    {
+        const size_t bl = (size_t)nb * leq_rows * cols * 8, bt = (size_t)nb * cols * 8, be = (size_t)nb * eq_rows * cols * 8;
+        if (extra > 0) {
+            XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
+            XPG_TRY(hipMemcpyAsync(dfv.p, free_var, (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (eq_rows > 0) {
+            XPG_TRY(de.alloc(ctx, be));
+            XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (allow_rational) {
+            XPG_TRY(dal.alloc(ctx, (size_t)cols));
+            XPG_TRY(hipMemcpyAsync(dal.p, allow_rational, (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (queue_bytes) { XPG_TRY(dq.alloc(ctx, queue_bytes)); XPG_TRY(hipMemsetAsync(dq.p, 0, queue_bytes, ctx->stream)); }
+        XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dws.alloc(ctx, ws_bytes));
+        XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(dsol.alloc(ctx, bt));
+        XPG_TRY(dn.alloc(ctx, (size_t)nb * 4));
+        if (bl) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
+        if (out_sol) XPG_TRY(hipMemcpyAsync(dsol.p, out_sol, bt, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    }
+    // Synchronises once. out_sol and out_nodes (the batch's node count) may be NULL.
+    int down(xpg_ctx * ctx, int nb, int cols, int32_t * out_status, void * out_v, void * out_sol, long long * out_nodes)
+    {
+        std::vector<int32_t> nodes((size_t)nb);
+        XPG_TRY(hipMemcpyAsync(out_status, dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(out_v, dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sol) XPG_TRY(hipMemcpyAsync(out_sol, dsol.p, (size_t)nb * cols * 8, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(nodes.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        if (out_nodes) { long long t = 0; for (int b = 0; b < nb; b++) t += nodes[(size_t)b]; *out_nodes = t; }
+        return 0;
+    }
+};
+
+// THE launch of k_mip_tree: nb trees on g.grid walking workgroups with nhelp helper workgroups behind them (0: none, and
+// spq NULL). Every pointer is a device pointer, as the kernel takes it: NULL where its comment allows.
+template <class S>
+int mip_tree_launch(xpg_ctx * ctx, const MipGeom & g, int nhelp, int nb, const void * tgtf, const void * leq, int leq_rows, int cols,
+                    bool is_max, bool is_bin, int rmax, int depth, void * ws, size_t ws_words, void * status, void * v, void * sol,
+                    void * nodes, const void * rows_of, const void * active, const void * allow, const void * eqs, int eq_rows,
+                    void * spq, const void * free_var, int extra)
+{
+    XPG_TRY(lds_limit((const void *)k_mip_tree<S>, ctx->device, g.lds));
+    hipLaunchKernelGGL((k_mip_tree<S>), dim3(g.grid + nhelp), dim3(g.threads), g.lds, ctx->stream, nb, (const S *)tgtf, (const S *)leq,
+                       leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)ws, ws_words,
+                       (int32_t *)status, (S *)v, (S *)sol, (int *)nodes, (const int *)rows_of, (const int *)active,
+                       (const uint8_t *)allow, (const S *)eqs, eq_rows, g.grid, (int *)spq, (const int *)free_var, extra);
+    XPG_TRY(hipGetLastError());
+    return 0;
+}
+
+// nb MIPs of one shape (x >= 0 but for the free variables free_var [extra], host, ascending; may be NULL / 0) with the tree
+// walks on the device (mip_kernels.hip.h): one workgroup per problem, host arrays in and out, one launch. Returns
+// XPG_ERR_UNSUPPORTED where a node LP of the deepest path would not fit the LDS budget -- the caller then takes the host
+// controller below.
 template <class S>
 int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
                      int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes,
@@ -438,167 +486,35 @@ int mip_batch_device(xpg_ctx * ctx, int nb, bool is_max, bool is_bin, const S * 
     const int depth = n + 2;
     const MipGeom g = mip_geom<S>(ctx, nb, rmax, n + extra, is_max);
     if (g.lds > 64 * 1024) return XPG_ERR_UNSUPPORTED;
-    const size_t lds = g.lds;
-    const int threads = g.threads, grid = g.grid;
     const size_t ws_words = mip_ws_words(rmax, cols, depth, extra);
-    DevBuf dfv;
-    if (extra > 0) {
-        XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
-        XPG_TRY(hipMemcpyAsync(dfv.p, free_var, (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const size_t bl = (size_t)nb * leq_rows * cols * 8, bt = (size_t)nb * cols * 8, be = (size_t)nb * eq_rows * cols * 8;
-    DevBuf dl, dt, dws, dst, dv, dsol, dn, dal, de;
-    if (eq_rows > 0) {
-        XPG_TRY(de.alloc(ctx, be));
-        XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (allow_rational) {
-        XPG_TRY(dal.alloc(ctx, (size_t)cols));
-        XPG_TRY(hipMemcpyAsync(dal.p, allow_rational, (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
-    }
     // Speculative ceiling children (mip_kernels.hip.h, SP_*): for batches that leave the chip under-filled -- one tree per
     // walking workgroup, the batch lasts as long as its deepest tree -- helper workgroups behind the walkers solve the node
     // LPs the walks will need next, one helper per CU. Not with root equalities (the helper builds plain nodes only).
     const int cus = ctx_cus(ctx);
-    const bool spec = eq_rows == 0 && grid == nb && nb <= 8 * cus;
+    const bool spec = eq_rows == 0 && g.grid == nb && nb <= 8 * cus;
     const int nhelp = spec ? cus : 0;        // (256 / 512 / 2048 helpers measured alike: 3.72 / 3.77 / 3.86 ms for 1024 knapsacks, 4.41 without)
-    DevBuf dq;
-    if (spec) { XPG_TRY(dq.alloc(ctx, spq_bytes())); XPG_TRY(hipMemsetAsync(dq.p, 0, spq_bytes(), ctx->stream)); }
-    XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dws.alloc(ctx, (size_t)(grid + nhelp) * ws_words * 8));
-    XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(dsol.alloc(ctx, bt));
-    XPG_TRY(dn.alloc(ctx, (size_t)nb * 4));
-    if (bl) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
-    if (out_sol) XPG_TRY(hipMemcpyAsync(dsol.p, out_sol, bt, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(lds_limit((const void *)k_mip_tree<S>, ctx->device, lds));
-    hipLaunchKernelGGL((k_mip_tree<S>), dim3(grid + nhelp), dim3(threads), lds, ctx->stream, nb, (const S *)dt.p, (const S *)dl.p,
-                       leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)dws.p, ws_words,
-                       (int32_t *)dst.p, (S *)dv.p, out_sol ? (S *)dsol.p : (S *)0, (int *)dn.p, (const int *)0, (const int *)0,
-                       allow_rational ? (const uint8_t *)dal.p : (const uint8_t *)0, eq_rows > 0 ? (const S *)de.p : (const S *)0, eq_rows,
-                       grid, spec ? (int *)dq.p : (int *)0, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
-    XPG_TRY(hipGetLastError());
+    MipIo io;
+    if (const int rc = io.up(ctx, nb, tgtf, leq, leq_rows, eqs, eq_rows, cols, allow_rational, free_var, extra, out_sol,
+                             (size_t)(g.grid + nhelp) * ws_words * 8, spec ? spq_bytes() : 0)) return rc;
+    if (const int rc = mip_tree_launch<S>(ctx, g, nhelp, nb, io.dt.p, io.dl.p, leq_rows, cols, is_max, is_bin, rmax, depth, io.dws.p, ws_words,
+                                          io.dst.p, io.dv.p, out_sol ? io.dsol.p : (void *)0, io.dn.p, (const void *)0, (const void *)0,
+                                          io.dal.p, io.de.p, eq_rows, io.dq.p, io.dfv.p, extra)) return rc;
     if (spec && xpg_hook("XPG_MIP_DEBUG")) {
         int hq[4] = {0, 0, 0, 0};
-        XPG_TRY(hipMemcpyAsync(hq, dq.p, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipMemcpyAsync(hq, io.dq.p, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
         fprintf(stderr, "xpoly_amd: MIP tree walk, %d trees, %d helpers: %d ceiling children requested, %d answers taken parked\n", nb, nhelp, hq[0], hq[3]);
     }
-    std::vector<int32_t> nodes((size_t)nb);
-    XPG_TRY(hipMemcpyAsync(out_status, dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(out_v, dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_sol) XPG_TRY(hipMemcpyAsync(out_sol, dsol.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(nodes.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    if (out_nodes) { long long t = 0; for (int b = 0; b < nb; b++) t += nodes[(size_t)b]; *out_nodes = t; }
+    if (const int rc = io.down(ctx, nb, cols, out_status, out_v, out_sol, out_nodes)) return rc;
     MipRoute & rt = mip_route();
     rt.device_trees += nb;
     if (extra > rt.free_vars) rt.free_vars = extra;
     return 0;
 }
 
-// nb independent MIPs of one shape (x >= 0, inequalities only), advanced together.
-template <class S>
-int mip_batch(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
-              int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes)
-{
-    if (!ctx || nb < 0 || !tgtf || !leq || leq_rows <= 0 || cols < 2 || !out_status || !out_v) return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
-    // the whole tree walk on the device where the node LPs fit (XPG_MIP_DEVICE=0: the host controller, for A/B runs)
-    static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_device) {
-        const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes, (const uint8_t *)0, (const S *)0, 0);
-        if (rc != XPG_ERR_UNSUPPORTED) return rc;
-    }
-    const int rhs = cols - 1;
-    std::vector<S> vc((size_t)rhs * cols, zero<S>());
-    for (int i = 0; i < rhs; i++) vc[(size_t)i * cols + i] = minus_one<S>();
-    std::vector<MipTask<S> > tasks(nb);
-    for (int b = 0; b < nb; b++)
-        tasks[b].start(make_problem<S>(tgtf + (size_t)b * cols, vc.data(), rhs, (const S *)0, 0,
-                                       leq + (size_t)b * leq_rows * cols, leq_rows, cols), is_max, is_bin, (const uint8_t *)0);
-    int rc = run_mip_tasks<S>(ctx, kind, tasks);
-    if (rc) return rc;
-    long long nodes = 0;
-    for (int b = 0; b < nb; b++) {
-        const MipTask<S> & T = tasks[b];
-        out_status[b] = T.final_status;
-        out_v[b] = T.v;
-        nodes += T.nodes;
-        if (T.final_status == XPG_IP_SUCC && out_sol && (int)T.sol.size() == cols)
-            for (int j = 0; j < cols; j++) out_sol[(size_t)b * cols + j] = T.sol[j];
-    }
-    if (out_nodes) *out_nodes = nodes;
-    return 0;
-}
-
-// nb independent MIPs of one shape WITH equalities at the root (x >= 0; the shape PolyTran::FeaSchedule passes,
-// src/eng/poly.cpp:5118-5130, batched): leq may be NULL with leq_rows = 0. The device tree walk where the node LPs fit
-// (every node runs convertEq2Ineq over the root's and the branches' equalities in its workgroup), the host controller
-// -- problems advancing in lock step -- otherwise.
-template <class S>
-int mip_batch_eq(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
-                 const S * eqs, int eq_rows, int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes)
-{
-    if (!ctx || nb < 0 || !tgtf || eq_rows <= 0 || !eqs || leq_rows < 0 || (leq_rows > 0 && !leq) || cols < 2 || !out_status || !out_v)
-        return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
-    static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_device && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows)) {
-        const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes,
-                                           (const uint8_t *)0, eqs, eq_rows);
-        if (rc != XPG_ERR_UNSUPPORTED) return rc;
-    }
-    const int rhs = cols - 1;
-    std::vector<S> vc((size_t)rhs * cols, zero<S>());
-    for (int i = 0; i < rhs; i++) vc[(size_t)i * cols + i] = minus_one<S>();
-    std::vector<MipTask<S> > tasks(nb);
-    for (int b = 0; b < nb; b++)
-        tasks[b].start(make_problem<S>(tgtf + (size_t)b * cols, vc.data(), rhs, eqs + (size_t)b * eq_rows * cols, eq_rows,
-                                       leq_rows > 0 ? leq + (size_t)b * leq_rows * cols : (const S *)0, leq_rows, cols),
-                       is_max, is_bin, (const uint8_t *)0);
-    int rc = run_mip_tasks<S>(ctx, kind, tasks);
-    if (rc) return rc;
-    long long nodes = 0;
-    for (int b = 0; b < nb; b++) {
-        const MipTask<S> & T = tasks[b];
-        out_status[b] = T.final_status;
-        out_v[b] = T.v;
-        nodes += T.nodes;
-        if (T.final_status == XPG_IP_SUCC && out_sol && (int)T.sol.size() == cols)
-            for (int j = 0; j < cols; j++) out_sol[(size_t)b * cols + j] = T.sol[j];
-    }
-    if (out_nodes) *out_nodes = nodes;
-    return 0;
-}
-
-// nb independent MIPs of one shape under the caller's variable constraints vc [cols - 1][cols], shared by the batch (what
-// the single-problem entry points take): equalities and / or inequalities at the root, an optional rational_indicator.
-// A vc that is a sign pattern (vc_sign_pattern: every variable x >= 0 or free) goes to the device tree walk in one launch
-// where the node LPs, widened by the free variables' twins, fit; every other vc -- and what does not fit -- to the host
-// controller with the caller's vc, so the call is defined wherever MIP::maxm / minm is.
-template <class S>
-int mip_batch_vc(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
-                 const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
-                 long long * out_nodes)
-{
-    if (!ctx || nb < 0 || !tgtf || !vc || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) || (eq_rows > 0 && !eqs) ||
-        (leq_rows > 0 && !leq) || cols < 2 || !out_status || !out_v)
-        return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
-    static const bool on_device = [] { const char * e = xpg_env("XPG_MIP_DEVICE"); return !(e && e[0] == '0'); }();
-    if (on_device) {
-        std::vector<int> fv;
-        if (vc_sign_pattern(vc, cols - 1, cols, fv) && mip_device_fits<S>(leq_rows, cols, is_bin, eq_rows, (int)fv.size())) {
-            const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes,
-                                               allow_rational, eqs, eq_rows, fv.data(), (int)fv.size());
-            if (rc != XPG_ERR_UNSUPPORTED) return rc;
-        }
-    }
-    return mip_batch_vc_host<S>(ctx, kind, nb, is_max, is_bin, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, allow_rational, out_status, out_v,
-                                out_sol, out_nodes);
-}
-// The host controller's half of mip_batch_vc: every tree a MipTask under the caller's vc, advanced in lock step (arguments
-// checked by the caller, nb > 0).
+// The host controller's end, the only one: every tree a MipTask under the caller's vc [cols - 1][cols], advanced in lock
+// step, the answers stored as the device route stores them -- out_sol (may be NULL) in the rows of solved trees only
+// (arguments checked by the caller, nb > 0).
 template <class S>
 int mip_batch_vc_host(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
                       const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
@@ -622,6 +538,87 @@ int mip_batch_vc_host(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin,
     }
     if (out_nodes) *out_nodes = nodes;
     return 0;
+}
+
+// THE front of the four entry points below: MIP::maxm / minm (lpsol.h:2636-2657, :2681-2702) for nb problems of one shape
+// under the variable constraints vc [cols - 1][cols] shared by the batch (NULL: x >= 0), with equalities and / or
+// inequalities at the root and an optional rational_indicator. A vc that is a sign pattern (every variable x >= 0 or free)
+// goes to the device tree walk in one launch where mip_front_route finds that the node LPs, widened by one twin per free
+// variable, fit; every other vc, what does not fit and what the launch still refuses go to the host controller under the
+// caller's vc, so the call is defined wherever MIP::maxm / minm is.
+template <class S>
+int mip_front(xpg_ctx * ctx, int kind, MipFit fit, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
+              const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
+              long long * out_nodes)
+{
+    if (!ctx || nb < 0 || !tgtf || eq_rows < 0 || leq_rows < 0 || (eq_rows == 0 && leq_rows == 0) || (eq_rows > 0 && !eqs) ||
+        (leq_rows > 0 && !leq) || cols < 2 || !out_status || !out_v)
+        return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    std::vector<int> fv;
+    const bool pattern = !vc || vc_sign_pattern(vc, cols - 1, cols, fv);
+    if (mip_front_route<S>(fit, pattern, (int)fv.size(), leq_rows, eq_rows, cols, is_bin, is_max, mip_device_allowed())) {
+        const int rc = mip_batch_device<S>(ctx, nb, is_max, is_bin, tgtf, leq, leq_rows, cols, out_status, out_v, out_sol, out_nodes,
+                                           allow_rational, eqs, eq_rows, fv.data(), (int)fv.size());
+        if (rc != XPG_ERR_UNSUPPORTED) return rc;
+    }
+    std::vector<S> nonneg;                                              // x >= 0 as the controller takes it: -x_i <= 0
+    if (!vc) {
+        nonneg.assign((size_t)(cols - 1) * cols, zero<S>());
+        for (int i = 0; i < cols - 1; i++) nonneg[(size_t)i * cols + i] = minus_one<S>();
+        vc = nonneg.data();
+    }
+    return mip_batch_vc_host<S>(ctx, kind, nb, is_max, is_bin, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, allow_rational, out_status, out_v,
+                                out_sol, out_nodes);
+}
+
+// One MIP::maxm / minm: a batch of one with its outputs adapted -- the status is the return value, *out_v is written
+// whatever it is, out_sol (may be NULL) on XPG_IP_SUCC only.
+template <class S>
+int mip_solve(xpg_ctx * ctx, int kind, bool is_max, bool is_bin, const S * tgtf, const S * vc, int vc_rows,
+              const S * eqs, int eq_rows, const S * leq, int leq_rows, int cols, const uint8_t * allow_rational,
+              S * out_v, S * out_sol, long * out_nodes)
+{
+    if (!vc || cols < 2 || vc_rows != cols - 1) return XPG_ERR_SHAPE;
+    int32_t st = 0; long long nodes = 0;
+    std::vector<S> sol((size_t)cols, zero<S>());
+    if (out_sol) for (int j = 0; j < cols; j++) sol[(size_t)j] = out_sol[j];
+    const int rc = mip_front<S>(ctx, kind, MIP_FIT_BOTH, 1, is_max, is_bin, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, allow_rational, &st,
+                                out_v, sol.data(), &nodes);
+    if (rc) return rc;
+    if (st == XPG_IP_SUCC && out_sol) for (int j = 0; j < cols; j++) out_sol[j] = sol[(size_t)j];
+    if (out_nodes) *out_nodes = (long)nodes;
+    return st;
+}
+// nb independent MIPs of one shape (x >= 0, inequalities only).
+template <class S>
+int mip_batch(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
+              int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes)
+{
+    if (!leq || leq_rows <= 0) return XPG_ERR_SHAPE;
+    return mip_front<S>(ctx, kind, MIP_FIT_LAUNCH, nb, is_max, is_bin, tgtf, (const S *)0, (const S *)0, 0, leq, leq_rows, cols, (const uint8_t *)0,
+                        out_status, out_v, out_sol, out_nodes);
+}
+// nb independent MIPs of one shape WITH equalities at the root (x >= 0; the shape PolyTran::FeaSchedule passes,
+// src/eng/poly.cpp:5118-5130, batched): leq may be NULL with leq_rows = 0. On the device every node runs convertEq2Ineq over
+// the root's and the branches' equalities in its workgroup.
+template <class S>
+int mip_batch_eq(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows,
+                 const S * eqs, int eq_rows, int cols, int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes)
+{
+    if (eq_rows <= 0) return XPG_ERR_SHAPE;
+    return mip_front<S>(ctx, kind, MIP_FIT_BOTH, nb, is_max, is_bin, tgtf, (const S *)0, eqs, eq_rows, leq, leq_rows, cols, (const uint8_t *)0,
+                        out_status, out_v, out_sol, out_nodes);
+}
+// nb independent MIPs of one shape under the caller's vc (what the single-problem entry points take).
+template <class S>
+int mip_batch_vc(xpg_ctx * ctx, int kind, int nb, bool is_max, bool is_bin, const S * tgtf, const S * vc, const S * eqs, int eq_rows,
+                 const S * leq, int leq_rows, int cols, const uint8_t * allow_rational, int32_t * out_status, S * out_v, S * out_sol,
+                 long long * out_nodes)
+{
+    if (!vc) return XPG_ERR_SHAPE;
+    return mip_front<S>(ctx, kind, MIP_FIT_BOTH, nb, is_max, is_bin, tgtf, vc, eqs, eq_rows, leq, leq_rows, cols, allow_rational, out_status, out_v,
+                        out_sol, out_nodes);
 }
 
 } // namespace xpg

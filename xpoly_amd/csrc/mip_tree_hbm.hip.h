@@ -155,7 +155,7 @@ void k_mip_tree_hbm(int nb, const S * tgtf_all, const S * leq_all, int leq_rows,
     }
 }
 
-// mip_batch_device's counterpart for a plan on the HBM route: host arrays in and out, one launch, synchronises once.
+// mip_batch_device's counterpart for a plan on the HBM route: host arrays in and out through the same MipIo, one launch.
 template <class S>
 int mip_hbm_launch(xpg_ctx * ctx, const MipHbmPlan & g, int nb, bool is_max, bool is_bin, const S * tgtf, const S * leq, int leq_rows, int cols,
                    int32_t * out_status, S * out_v, S * out_sol, long long * out_nodes, const uint8_t * allow_rational, const S * eqs,
@@ -165,43 +165,19 @@ int mip_hbm_launch(xpg_ctx * ctx, const MipHbmPlan & g, int nb, bool is_max, boo
     const size_t slots_bytes = (size_t)g.grid * g.slot;
     Scratch & slots = ctx->scratch[SCRATCH_BATCH_HBM];
     if (const int rc = scratch_reserve(ctx, slots, slots_bytes, slots_bytes, "hipMalloc(mip_batch_vc_hbm scratch)")) return rc;
-    const size_t bl = (size_t)nb * leq_rows * cols * 8, bt = (size_t)nb * cols * 8, be = (size_t)nb * eq_rows * cols * 8;
-    DevBuf dfv, dl, dt, dws, dst, dv, dsol, dn, dal, de;
-    if (extra > 0) {
-        XPG_TRY(dfv.alloc(ctx, (size_t)extra * 4));
-        XPG_TRY(hipMemcpyAsync(dfv.p, free_var, (size_t)extra * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (eq_rows > 0) {
-        XPG_TRY(de.alloc(ctx, be));
-        XPG_TRY(hipMemcpyAsync(de.p, eqs, be, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (allow_rational) {
-        XPG_TRY(dal.alloc(ctx, (size_t)cols));
-        XPG_TRY(hipMemcpyAsync(dal.p, allow_rational, (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
-    }
-    XPG_TRY(dl.alloc(ctx, bl)); XPG_TRY(dt.alloc(ctx, bt)); XPG_TRY(dws.alloc(ctx, (size_t)g.grid * g.ws_words * 8));
-    XPG_TRY(dst.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dv.alloc(ctx, (size_t)nb * 8)); XPG_TRY(dsol.alloc(ctx, bt));
-    XPG_TRY(dn.alloc(ctx, (size_t)nb * 4));
-    if (bl) XPG_TRY(hipMemcpyAsync(dl.p, leq, bl, hipMemcpyHostToDevice, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(dt.p, tgtf, bt, hipMemcpyHostToDevice, ctx->stream));
-    if (out_sol) XPG_TRY(hipMemcpyAsync(dsol.p, out_sol, bt, hipMemcpyHostToDevice, ctx->stream));
+    MipIo io;
+    if (const int rc = io.up(ctx, nb, tgtf, leq, leq_rows, eqs, eq_rows, cols, allow_rational, free_var, extra, out_sol,
+                             (size_t)g.grid * g.ws_words * 8)) return rc;
     if (const int rc = hbm_static_lds_check(ctx, (const void *)k_mip_tree_hbm<S>, MIP_HBM_LDS_STATIC, "k_mip_tree_hbm: static LDS above MIP_HBM_LDS_STATIC"))
         return rc;
     XPG_TRY(lds_limit((const void *)k_mip_tree_hbm<S>, ctx->device, g.lds));
-    hipLaunchKernelGGL((k_mip_tree_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, (const S *)dt.p,
-                       (const S *)dl.p, leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)dws.p, g.ws_words,
-                       (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), g.ld, (int32_t *)dst.p, (S *)dv.p,
-                       out_sol ? (S *)dsol.p : (S *)0, (int *)dn.p, allow_rational ? (const uint8_t *)dal.p : (const uint8_t *)0,
-                       eq_rows > 0 ? (const S *)de.p : (const S *)0, eq_rows, extra > 0 ? (const int *)dfv.p : (const int *)0, extra);
+    hipLaunchKernelGGL((k_mip_tree_hbm<S>), dim3((unsigned)g.grid), dim3((unsigned)g.threads), g.lds, ctx->stream, nb, (const S *)io.dt.p,
+                       (const S *)io.dl.p, leq_rows, cols, is_max ? 1 : 0, is_bin ? 1 : 0, rmax, depth, (unsigned long long *)io.dws.p, g.ws_words,
+                       (unsigned long long *)slots.buf, (unsigned long long)(g.slot / 8), g.ld, (int32_t *)io.dst.p, (S *)io.dv.p,
+                       out_sol ? (S *)io.dsol.p : (S *)0, (int *)io.dn.p, (const uint8_t *)io.dal.p, (const S *)io.de.p, eq_rows,
+                       (const int *)io.dfv.p, extra);
     XPG_TRY(hipGetLastError());
-    std::vector<int32_t> nodes((size_t)nb);
-    XPG_TRY(hipMemcpyAsync(out_status, dst.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(out_v, dv.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_sol) XPG_TRY(hipMemcpyAsync(out_sol, dsol.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(nodes.data(), dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    if (out_nodes) { long long t = 0; for (int b = 0; b < nb; b++) t += nodes[(size_t)b]; *out_nodes = t; }
-    return 0;
+    return io.down(ctx, nb, cols, out_status, out_v, out_sol, out_nodes);
 }
 
 // mip_batch_vc for node LPs of any size: the arguments and results of mip_batch_vc, the route by mip_hbm_plan. The rule is the

@@ -1270,8 +1270,7 @@ int xpg_mip_maxm_rat32(xpg_ctx * ctx, const xpg_rat32 * tgtf, const xpg_rat32 * 
                        const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
                        int is_bin, const uint8_t * ind, xpg_rat32 * out_v, xpg_rat32 * out_sol)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_solve<R32>(ctx, 1, true, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, vc_rows, (const R32 *)eq,
                           eq_rows, (const R32 *)leq, leq_rows, cols, ind, (R32 *)out_v, (R32 *)out_sol, 0);
 }
@@ -1279,8 +1278,7 @@ int xpg_mip_minm_rat32(xpg_ctx * ctx, const xpg_rat32 * tgtf, const xpg_rat32 * 
                        const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols,
                        int is_bin, const uint8_t * ind, xpg_rat32 * out_v, xpg_rat32 * out_sol)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_solve<R32>(ctx, 1, false, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, vc_rows, (const R32 *)eq,
                           eq_rows, (const R32 *)leq, leq_rows, cols, ind, (R32 *)out_v, (R32 *)out_sol, 0);
 }
@@ -1288,8 +1286,7 @@ int xpg_mip_maxm_f64(xpg_ctx * ctx, const double * tgtf, const double * vc, int 
                      int eq_rows, const double * leq, int leq_rows, int cols, int is_bin, const uint8_t * ind,
                      double * out_v, double * out_sol)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_solve<F64>(ctx, 0, true, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, vc_rows, (const F64 *)eq,
                           eq_rows, (const F64 *)leq, leq_rows, cols, ind, (F64 *)out_v, (F64 *)out_sol, 0);
 }
@@ -1297,8 +1294,7 @@ int xpg_mip_minm_f64(xpg_ctx * ctx, const double * tgtf, const double * vc, int 
                      int eq_rows, const double * leq, int leq_rows, int cols, int is_bin, const uint8_t * ind,
                      double * out_v, double * out_sol)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_solve<F64>(ctx, 0, false, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, vc_rows, (const F64 *)eq,
                           eq_rows, (const F64 *)leq, leq_rows, cols, ind, (F64 *)out_v, (F64 *)out_sol, 0);
 }
@@ -1306,8 +1302,7 @@ int xpg_has_solution_rat32(xpg_ctx * ctx, const xpg_rat32 * leq, int leq_rows, c
                            const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_int_sol,
                            int is_unique_sol)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return has_solution(ctx, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols,
                         rhs_idx, is_int_sol != 0, is_unique_sol != 0);
 }
@@ -1316,16 +1311,14 @@ int xpg_mip_batch_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const xpg
                         int leq_rows, int cols, int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol,
                         long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)leq, leq_rows, cols,
                           out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
 int xpg_mip_batch_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const double * tgtf, const double * leq,
                       int leq_rows, int cols, int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)leq, leq_rows, cols,
                           out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
@@ -1333,8 +1326,7 @@ int xpg_mip_batch_eq_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const 
                            int leq_rows, const xpg_rat32 * eq, int eq_rows, int cols, int32_t * out_status, xpg_rat32 * out_v,
                            xpg_rat32 * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_eq<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows,
                              cols, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
@@ -1342,16 +1334,14 @@ int xpg_mip_batch_eq_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const do
                          const double * eq, int eq_rows, int cols, int32_t * out_status, double * out_v, double * out_sol,
                          long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_eq<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)leq, leq_rows, (const F64 *)eq, eq_rows,
                              cols, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
 int xpg_dep_is_empty_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols,
                                  int32_t * out_empty, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, cols - 1, (const R32 *)0, out_empty, &n);
     if (out_nodes) *out_nodes = n;
@@ -1360,8 +1350,7 @@ int xpg_dep_is_empty_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, 
 int xpg_dep_is_empty_batch_ex_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
                                     const xpg_rat32 * vc, int32_t * out_empty, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, (const R32 *)vc, out_empty, &n);
     if (out_nodes) *out_nodes = n;
@@ -1370,8 +1359,7 @@ int xpg_dep_is_empty_batch_ex_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mat
 int xpg_dep_is_empty_batch_mode_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
                                       const xpg_rat32 * vc, int mode, int32_t * out_empty, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     if (mode != XPG_DEP_PARITY && mode != XPG_DEP_SYMBOLS_AS_VARS) return XPG_ERR_SHAPE;
     long n = 0;
     int rc = dep_is_empty_batch(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, (const R32 *)vc, out_empty, &n, mode == XPG_DEP_SYMBOLS_AS_VARS ? 1 : 0);
@@ -1382,8 +1370,7 @@ int xpg_mip_batch_vc_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, const 
                            const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, const uint8_t * ind,
                            int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_vc<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows,
                              (const R32 *)leq, leq_rows, cols, ind, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
@@ -1391,8 +1378,7 @@ int xpg_mip_batch_vc_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, const do
                          const double * eq, int eq_rows, const double * leq, int leq_rows, int cols, const uint8_t * ind,
                          int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_vc<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows,
                              (const F64 *)leq, leq_rows, cols, ind, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
@@ -1404,7 +1390,7 @@ int xpg_mip_last_route(long long * out, int n)
     const long long f[3] = { r.device_trees, r.host_trees, r.free_vars };
     return copy_fields(out, n, f);
 }
-// host-only test views: the vc classifier and the LDS fit test the MIP entry points route by
+// host-only test views: the vc classifier, the LDS fit test and the route rule of the MIP entry points
 int xpg_test_vc_pattern(int kind, const void * vc, int vc_rows, int cols, uint8_t * out_free)
 {
     if (!vc || !out_free || cols < 2 || vc_rows != cols - 1 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
@@ -1420,6 +1406,15 @@ int xpg_test_mip_fits(int kind, int leq_rows, int eq_rows, int cols, int is_bin,
     if (cols < 2 || leq_rows < 0 || eq_rows < 0 || extra < 0 || (kind != 0 && kind != 1)) return XPG_ERR_SHAPE;
     return (kind == 0 ? mip_device_fits<F64>(leq_rows, cols, is_bin != 0, eq_rows, extra)
                       : mip_device_fits<R32>(leq_rows, cols, is_bin != 0, eq_rows, extra)) ? 1 : 0;
+}
+// mip_front_route as an entry point with fit test `fit` (mip_host.hip.h MipFit) asks it; allowed stands for XPG_MIP_DEVICE
+int xpg_test_mip_front_route(int fit, int kind, int pattern, int extra, int leq_rows, int eq_rows, int cols, int is_bin, int is_max, int allowed)
+{
+    if ((fit != MIP_FIT_LAUNCH && fit != MIP_FIT_BOTH) || (kind != 0 && kind != 1) || cols < 2 || leq_rows < 0 || eq_rows < 0 ||
+        (leq_rows == 0 && eq_rows == 0) || extra < 0)
+        return XPG_ERR_SHAPE;
+    return (kind == 0 ? mip_front_route<F64>((MipFit)fit, pattern != 0, extra, leq_rows, eq_rows, cols, is_bin != 0, is_max != 0, allowed != 0)
+                      : mip_front_route<R32>((MipFit)fit, pattern != 0, extra, leq_rows, eq_rows, cols, is_bin != 0, is_max != 0, allowed != 0)) ? 1 : 0;
 }
 // what batch_dev would launch nb LPs solved as R rows x V variables with, on a device of num_cus compute units
 int xpg_test_batch_geometry(int kind, int R, int V, int nb, int num_cus, long long * out, int n)
@@ -1545,8 +1540,7 @@ int xpg_mip_batch_vc_hbm_rat32(xpg_ctx * ctx, int nb, int is_max, int is_bin, co
                                const xpg_rat32 * eq, int eq_rows, const xpg_rat32 * leq, int leq_rows, int cols, const uint8_t * ind,
                                int32_t * out_status, xpg_rat32 * out_v, xpg_rat32 * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_vc_hbm<R32>(ctx, 1, nb, is_max != 0, is_bin != 0, (const R32 *)tgtf, (const R32 *)vc, (const R32 *)eq, eq_rows,
                                  (const R32 *)leq, leq_rows, cols, ind, out_status, (R32 *)out_v, (R32 *)out_sol, out_nodes);
 }
@@ -1554,8 +1548,7 @@ int xpg_mip_batch_vc_hbm_f64(xpg_ctx * ctx, int nb, int is_max, int is_bin, cons
                              const double * eq, int eq_rows, const double * leq, int leq_rows, int cols, const uint8_t * ind,
                              int32_t * out_status, double * out_v, double * out_sol, long long * out_nodes)
 {
-    XPG_BIND(ctx);
-    mip_route() = MipRoute{0, 0, 0};
+    XPG_BIND_MIP(ctx);
     return mip_batch_vc_hbm<F64>(ctx, 0, nb, is_max != 0, is_bin != 0, (const F64 *)tgtf, (const F64 *)vc, (const F64 *)eq, eq_rows,
                                  (const F64 *)leq, leq_rows, cols, ind, out_status, (F64 *)out_v, (F64 *)out_sol, out_nodes);
 }
