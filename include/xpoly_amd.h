@@ -485,6 +485,42 @@ int xpg_has_solution_batch_last_route(long long * out, int n);
  * [6] threads; [7] grid (0 on route 2); [8] scratch bytes of the launch. */
 int xpg_test_has_solution_batch_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus,
                                      long long * out, int n);
+/* Lineq::has_solution for nb systems of MIXED shapes under one vc in one call -- what a SCoP hands over: DepPolyMgr::build
+ * emits systems whose row counts follow the statements' depths.  System b has leq_rows[b] x cols inequalities at CELL offset
+ * leq_offsets[b] of leq and eq_rows[b] x cols equalities at eq_offsets[b] of eq (the offset convention of the other ragged
+ * entry points; arrays of nb entries); cols, rhs_idx and vc -- the sign pattern of the variables -- are the call's.  eq /
+ * eq_offsets may be NULL when every eq_rows[b] is 0.  XPG_ERR_SHAPE, before anything touches a device: the rule of
+ * xpg_has_solution_batch_rat32, a NULL shape or offset array, a negative entry.  nb = 0 returns 0.
+ * Per system the verdict and the out_status pair are bit for bit those of xpg_has_solution_batch_rat32 called with that
+ * system alone (XPG_HS_NOT_RUN, -7, the rule for a system without inequalities).
+ * is_int_sol = 0: a system takes, inside this call, the route a uniform call of its shape takes --
+ *   - the systems whose own shape the LDS-resident kernel takes: ONE launch of its form over an index list;
+ *   - the systems whose own shape the device-memory kernel takes: ONE launch of that kernel's form;
+ *   - a general vc, a shape past both kernels: xpg_has_solution_rat32 per system; without inequalities: no solve at all.
+ *   A launch is sized by the largest of what the route rule gives its systems, size by size (LDS bytes, threads, slot, tableau
+ *   rows, ld), never by the envelope shape (largest leq_rows, largest eq_rows), which can lie past a route all its systems are
+ *   on.  The concatenated arrays go up as they lie, one copy each; both launches are enqueued before the call's single
+ *   synchronisation.  Slots live in the areas of xpg_six_batch_vc_* / xpg_six_batch_vc_hbm_*; xpg_trim returns them.
+ * is_int_sol = 1: the shape classes on the host, each as xpg_has_solution_batch_rat32 with is_int_sol = 1 answers it.
+ * There is no _dev form: the route rule needs the shapes on the host.
+ * Tests: tests/test_has_solution_ragged_host.py, tests/test_gpu_has_solution_ragged.py. */
+int xpg_has_solution_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, const int32_t * leq_rows, const long long * leq_offsets,
+                                        const xpg_rat32 * eq, const int32_t * eq_rows, const long long * eq_offsets, const xpg_rat32 * vc,
+                                        int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol, unsigned max_iter,
+                                        int32_t * out_has, int32_t * out_status /* [nb][2], may be NULL */);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_has_solution_batch_ragged_rat32 call did.  out[0]
+ * systems on the LDS-resident kernel, [1] on the device-memory kernel, [2] answered per system, [3] systems whose second
+ * solve ran, [4] the grid of the LDS launch, [5] of the device-memory launch (0 without one), [6] systems answered without a
+ * solve.  Fills min(n, 7) entries. */
+int xpg_has_solution_batch_ragged_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the plan of a ragged call (is_int_sol = 0) under vc [vc_rows][cols] on a
+ * device of num_cus compute units -- the function the launches themselves ask.  out_route[b] (may be NULL): 0 LDS-resident
+ * kernel, 1 device-memory kernel, 2 per system, 3 without inequalities.  Fills min(n, 12) entries: the LDS launch -- out[0]
+ * systems, [1] LDS bytes, [2] threads, [3] slot bytes, [4] grid; the device-memory launch -- [5] systems, [6] LDS bytes,
+ * [7] slot bytes, [8] Rmax, [9] ld, [10] threads, [11] grid.  Each size is the largest of what
+ * xpg_test_has_solution_batch_plan reports for a system of that launch; a launch without systems reports zeros. */
+int xpg_test_has_solution_batch_ragged_plan(const void * vc, int vc_rows, int cols, int nb, const int32_t * leq_rows, const int32_t * eq_rows,
+                                            int num_cus, int32_t * out_route /* [nb] */, long long * out, int n);
 
 /* Batches: nb independent problems of one shape, x >= 0, inequalities only
  * (tgtf[nb][cols], leq[nb][leq_rows][cols]).  Every tree is walked on the device by one

@@ -245,9 +245,11 @@ inline int dep_is_empty_all(const std::vector<RMatT *> & polys, std::vector<int3
 
 // Many feasibility questions in few calls: Lineq::has_solution(*leqs[k], *eqs[k], vc, rhs_idx, is_int_sol, is_unique_sol)
 // (linsys.cpp:830-906) under one vc. leqs[k] / eqs[k] may be null or without rows; all non-empty matrices have rhs_idx + 1
-// columns. Systems of one shape (leq rows, eq rows) go up together -- one xpg_has_solution_batch_rat32 call per shape class,
-// each system answered by one workgroup that normalises once and asks maxm, then minm. out[k] = 1 / 0 as has_solution
-// would return, or a negative XPG_ERR_* where the reference is undefined on system k. Returns 0 or a negative XPG_ERR_* code.
+// columns. The systems are packed once, in the order given, and go up in ONE xpg_has_solution_batch_ragged_rat32 call
+// whatever their shapes (leq rows, eq rows): the library sends each system the way a batch of its shape goes -- one launch
+// per kernel, each system answered by one workgroup that normalises once and asks maxm, then minm -- and, for is_int_sol,
+// forms the shape classes itself. out[k] = 1 / 0 as has_solution would return, or a negative XPG_ERR_* where the reference is
+// undefined on system k. Returns 0 or a negative XPG_ERR_* code.
 template <class RMatT>
 inline int has_solution_all(const std::vector<RMatT *> & leqs, const std::vector<RMatT *> & eqs, const RMatT & vc, int rhs_idx,
                             bool is_int_sol, bool is_unique_sol, std::vector<int32_t> & out, xpg_ctx * c = 0)
@@ -255,35 +257,28 @@ inline int has_solution_all(const std::vector<RMatT *> & leqs, const std::vector
     const int nb = (int)leqs.size(), cols = rhs_idx + 1;
     if ((int)eqs.size() != nb || rhs_idx < 1 || (int)vc.get_row_size() != rhs_idx || (int)vc.get_col_size() != cols) return XPG_ERR_SHAPE;
     out.assign((size_t)nb, 0);
+    if (nb == 0) return 0;
     const auto rows_of = [&](const RMatT * m) { return m && m->get_col_size() ? (int)m->get_row_size() : 0; };
-    std::vector<std::pair<std::pair<int, int>, std::vector<int> > > groups;          // (leq rows, eq rows) -> the systems, in order of first sight
+    std::vector<int32_t> lrows((size_t)nb), erows((size_t)nb);
+    std::vector<long long> loff((size_t)nb + 1, 0), eoff((size_t)nb + 1, 0);
     for (int b = 0; b < nb; b++) {
         for (const RMatT * m : { (const RMatT *)leqs[(size_t)b], (const RMatT *)eqs[(size_t)b] })
             if (rows_of(m) > 0 && (int)m->get_col_size() != cols) return XPG_ERR_SHAPE;
-        const std::pair<int, int> key(rows_of(leqs[(size_t)b]), rows_of(eqs[(size_t)b]));
-        size_t g = 0;
-        while (g < groups.size() && groups[g].first != key) g++;
-        if (g == groups.size()) groups.push_back(std::make_pair(key, std::vector<int>()));
-        groups[g].second.push_back(b);
+        lrows[(size_t)b] = rows_of(leqs[(size_t)b]); erows[(size_t)b] = rows_of(eqs[(size_t)b]);
+        loff[(size_t)b + 1] = loff[(size_t)b] + (long long)lrows[(size_t)b] * cols;
+        eoff[(size_t)b + 1] = eoff[(size_t)b] + (long long)erows[(size_t)b] * cols;
     }
-    xpg_ctx * h = c ? c : detail::shared_context();
-    for (size_t g = 0; g < groups.size(); g++) {
-        const int lr = groups[g].first.first, er = groups[g].first.second, n = (int)groups[g].second.size();
-        const size_t lc = (size_t)lr * cols, ec = (size_t)er * cols;
-        std::vector<xpg_rat32> L((size_t)n * lc), E((size_t)n * ec);
-        std::vector<int32_t> has((size_t)n, 0);
-        for (int k = 0; k < n; k++) {
-            const int b = groups[g].second[(size_t)k];
-            if (lc) std::memcpy((void *)(L.data() + (size_t)k * lc), (const void *)leqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * lc);
-            if (ec) std::memcpy((void *)(E.data() + (size_t)k * ec), (const void *)eqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * ec);
-        }
-        const int rc = xpg_has_solution_batch_rat32(h, n, lc ? L.data() : (const xpg_rat32 *)0, lr, ec ? E.data() : (const xpg_rat32 *)0, er,
-                                                    (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, is_int_sol ? 1 : 0,
-                                                    is_unique_sol ? 1 : 0, 0xFFFFFFFFu, has.data(), (int32_t *)0);
-        if (rc != 0) return rc;
-        for (int k = 0; k < n; k++) out[(size_t)groups[g].second[(size_t)k]] = has[(size_t)k];
+    std::vector<xpg_rat32> L((size_t)loff[(size_t)nb]), E((size_t)eoff[(size_t)nb]);
+    for (int b = 0; b < nb; b++) {
+        if (lrows[(size_t)b])
+            std::memcpy((void *)(L.data() + loff[(size_t)b]), (const void *)leqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * (size_t)lrows[(size_t)b] * cols);
+        if (erows[(size_t)b])
+            std::memcpy((void *)(E.data() + eoff[(size_t)b]), (const void *)eqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * (size_t)erows[(size_t)b] * cols);
     }
-    return 0;
+    return xpg_has_solution_batch_ragged_rat32(c ? c : detail::shared_context(), nb, L.empty() ? (const xpg_rat32 *)0 : L.data(), lrows.data(),
+                                               loff.data(), E.empty() ? (const xpg_rat32 *)0 : E.data(), erows.data(), eoff.data(),
+                                               (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, is_int_sol ? 1 : 0,
+                                               is_unique_sol ? 1 : 0, 0xFFFFFFFFu, out.data(), (int32_t *)0);
 }
 
 // Many eliminations in ONE call: Lineq::fme(u[k], results[k]) (linsys.cpp:656-774) on systems of whatever shapes, the constant

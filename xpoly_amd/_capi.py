@@ -40,6 +40,7 @@ SYMBOLS = [
     "xpg_six_batch_vc_hbm_last_route", "xpg_test_six_batch_vc_hbm_plan",
     "xpg_mip_batch_vc_hbm_rat32", "xpg_mip_batch_vc_hbm_f64", "xpg_mip_hbm_last_route", "xpg_test_mip_hbm_plan",
     "xpg_has_solution_batch_rat32", "xpg_has_solution_batch_rat32_dev", "xpg_has_solution_batch_last_route", "xpg_test_has_solution_batch_plan",
+    "xpg_has_solution_batch_ragged_rat32", "xpg_has_solution_batch_ragged_last_route", "xpg_test_has_solution_batch_ragged_plan",
 ]
 
 _lib = None

@@ -79,7 +79,7 @@ template <class S> __device__ __forceinline__ void hbm_carve(Small<S> & P, unsig
 
 // The rules every route on a tableau in device memory shares (k_batch_hbm, k_six_batch_vc_hbm, k_mip_tree_hbm).
 // ld: the widest live width (V + R + 2) rounded up to an even number of cells; a tableau slot starts on a 256-byte line.
-inline size_t hbm_ld(int R, int V) { return ((size_t)V + (size_t)R + 2 + 1) & ~(size_t)1; }
+__host__ __device__ inline size_t hbm_ld(int R, int V) { return ((size_t)V + (size_t)R + 2 + 1) & ~(size_t)1; }
 inline size_t hbm_slot_bytes(int R, size_t ld) { return ((size_t)R * ld * 8 + 255) & ~(size_t)255; }
 // The grid: workgroups per CU by the wavefronts resident there, cut by what 160 KB of LDS hold (lds: dynamic plus static
 // bytes of one workgroup), at least one; times the CUs, cut by the workgroups whose scratch (each bytes) fits

@@ -225,6 +225,16 @@ inline long long six_vc_scratch_cut(long long grid, size_t slot_bytes)
     const long long by_scratch = (long long)(SIX_VC_SCRATCH_MAX / slot_bytes);
     return grid > by_scratch ? (by_scratch > 0 ? by_scratch : 1) : grid;
 }
+// The grid of an LDS-resident launch whose workgroups hold `lds` bytes each and one slot of slot_bytes: what 160 KB hold, 16
+// at the most, on 256 x 64 places; no more than nb; under the scratch cut. (six_vc_geometry for one shape, and the ragged
+// has_solution launch for the largest of its systems, has_solution_batch.hip.h.)
+inline long long six_vc_grid(size_t lds, long long nb, size_t slot_bytes)
+{
+    const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
+    long long grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
+    if (grid > nb) grid = nb;
+    return six_vc_scratch_cut(grid, slot_bytes);
+}
 // The launch of k_six_batch_vc for a shape the device route takes (six_batch_vc_dev asks it, and the route rule of
 // xpg_six_batch_vc_hbm_* reports it): nfree as six_batch_vc_dev takes it.
 struct SixVcGeom { size_t lds; int threads; long long grid; size_t slot_cells; };
@@ -239,10 +249,7 @@ template <class S> inline SixVcGeom six_vc_geometry(int nfree, int nb, int leq_r
     const int R = is_max ? least.rows_max : least.n, V = is_max ? least.n : least.rows_max;
     const int cells = R * (V + R + 2);
     q.threads = cells >= 2048 ? 256 : (cells >= 1024 ? 128 : 64);             // batch_geometry's rule
-    const int per_cu = (int)((160 * 1024) / q.lds) > 0 ? (int)((160 * 1024) / q.lds) : 1;
-    q.grid = 256ll * (per_cu > 16 ? 16 : per_cu) * 64;
-    if (q.grid > nb) q.grid = nb;
-    q.grid = six_vc_scratch_cut(q.grid, q.slot_cells * 8);
+    q.grid = six_vc_grid(q.lds, nb, q.slot_cells * 8);
     return q;
 }
 

@@ -22,7 +22,8 @@
 //   part 4  LP batches beyond one CU's LDS (k_batch_hbm)
 //   part 5  the same with equalities and free variables (k_six_batch_vc_hbm)
 //   part 6  MIP tree walks whose node LPs are beyond 64 KB of LDS (k_mip_tree_hbm)
-//   part 7  batched has_solution (k_has_solution_batch, k_has_solution_batch_hbm)
+//   part 7  batched has_solution (k_has_solution_batch, k_has_solution_batch_hbm, and their forms for mixed shapes,
+//           k_has_solution_ragged, k_has_solution_ragged_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -1622,6 +1623,48 @@ int xpg_test_has_solution_batch_plan(const void * vc, int vc_rows, int leq_rows,
     const VcView v = vc_view<R32>(vc, vc_rows, cols);
     const HsPlan g = hs_plan<R32>(v.pattern, v.nfree, leq_rows, eq_rows, cols, nb, num_cus);
     const long long f[9] = { g.route, g.nfree, g.Rmax, (long long)g.lds, (long long)g.slot, g.ld, g.threads, g.grid, (long long)g.scratch };
+    return copy_fields(out, n, f);
+}
+// ---- the same for systems of mixed shapes under one vc: every system on the route of its own shape, one launch per route ----
+int xpg_has_solution_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, const int32_t * leq_rows, const long long * leq_offsets,
+                                        const xpg_rat32 * eq, const int32_t * eq_rows, const long long * eq_offsets, const xpg_rat32 * vc,
+                                        int vc_rows, int cols, int rhs_idx, int is_int_sol, int is_unique_sol, unsigned max_iter,
+                                        int32_t * out_has, int32_t * out_status)
+{
+    XPG_BIND(ctx);
+    if (is_int_sol)
+        return has_solution_ragged_int(ctx, nb, (const R32 *)leq, leq_rows, leq_offsets, (const R32 *)eq, eq_rows, eq_offsets, (const R32 *)vc, vc_rows,
+                                       cols, rhs_idx, out_has, out_status,
+                                       [&](int lr, int er, int count, const R32 * l, const R32 * e, int32_t * has, int32_t * st) {
+            return xpg_has_solution_batch_rat32(ctx, count, (const xpg_rat32 *)l, lr, (const xpg_rat32 *)e, er, vc, vc_rows, cols, rhs_idx, 1,
+                                                is_unique_sol, max_iter, has, st);
+        });
+    return has_solution_ragged_host<R32>(ctx, nb, (const R32 *)leq, leq_rows, leq_offsets, (const R32 *)eq, eq_rows, eq_offsets, (const R32 *)vc,
+                                         vc_rows, cols, rhs_idx, is_unique_sol != 0, max_iter, out_has, out_status, [&](int b) {
+        return xpg_has_solution_rat32(ctx, leq + leq_offsets[b], leq_rows[b], eq_rows[b] > 0 ? eq + eq_offsets[b] : (const xpg_rat32 *)0, eq_rows[b],
+                                      vc, vc_rows, cols, rhs_idx, 0, is_unique_sol);
+    });
+}
+// what the calling thread's last xpg_has_solution_batch_ragged_rat32 call did (has_solution_batch.hip.h HsRaggedRoute)
+int xpg_has_solution_batch_ragged_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const HsRaggedRoute & r = hs_ragged_route();
+    const long long f[7] = { r.lds, r.hbm, r.host, r.second, r.grid_lds, r.grid_hbm, r.no_solve };
+    return copy_fields(out, n, f);
+}
+// host-only test view: the plan of a ragged call (hs_ragged_plan, which the launches ask too)
+int xpg_test_has_solution_batch_ragged_plan(const void * vc, int vc_rows, int cols, int nb, const int32_t * leq_rows, const int32_t * eq_rows,
+                                            int num_cus, int32_t * out_route, long long * out, int n)
+{
+    if (!vc || !out || n < 0 || cols < 2 || vc_rows != cols - 1 || nb <= 0 || !leq_rows || !eq_rows || num_cus <= 0) return XPG_ERR_SHAPE;
+    for (int b = 0; b < nb; b++) if (leq_rows[b] < 0 || eq_rows[b] < 0) return XPG_ERR_SHAPE;
+    const VcView v = vc_view<R32>(vc, vc_rows, cols);
+    const HsRaggedPlan p = hs_ragged_plan<R32>(v.pattern, v.nfree, nb, leq_rows, eq_rows, cols, num_cus);
+    if (out_route) std::copy(p.route.begin(), p.route.end(), out_route);
+    const HsRaggedLaunch & a = p.at[HS_ROUTE_LDS]; const HsRaggedLaunch & h = p.at[HS_ROUTE_HBM];
+    const long long f[12] = { a.count, (long long)a.lds, a.threads, (long long)a.slot, a.grid,
+                              h.count, (long long)h.lds, (long long)h.slot, h.Rmax, h.ld, h.threads, h.grid };
     return copy_fields(out, n, f);
 }
 } // extern "C"

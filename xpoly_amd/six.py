@@ -802,6 +802,70 @@ def six_batch_ragged(ctx, kind, is_max, tgtfs, leqs, max_iter=0xFFFFFFFF):
     return status, v, sols
 
 
+def _hs_ragged_shapes(systems, cols):
+    """A list of per-system arrays or None -> the [rows_b, cols(,2)] arrays _ragged_pack takes and rows[nb]."""
+    mats = [np.zeros((0, cols, 2), dtype=np.int32) if a is None or len(a) == 0 else as_kind(a, RAT, 2) for a in systems]
+    for m in mats:
+        if m.shape[1] != cols:
+            raise ValueError("every system must have cols = %d columns, got %d" % (cols, m.shape[1]))
+    return mats, np.array([m.shape[0] for m in mats], dtype=np.int32)
+
+
+def has_solution_ragged(ctx, leqs, eqs, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
+    """Lineq::has_solution for rational systems of MIXED shapes under one vc in one call
+    (xpg_has_solution_batch_ragged_rat32): leqs[b] [rows_b, cols(,2)] and eqs[b] [eq_rows_b, cols(,2)], either None or without
+    rows; eqs=None: no system has equalities. Every system takes the route has_solution_batch takes for its shape -- the systems
+    of a route share ONE launch -- and gets that call's answers. Returns has[nb], and with want_status also status[nb, 2]."""
+    vc = as_kind(vc, RAT, 2)
+    cols = vc.shape[1]
+    nb = len(leqs)
+    if eqs is None:
+        eqs = [None] * nb
+    if len(eqs) != nb:
+        raise ValueError("leqs and eqs must list the same systems")
+    lm, leq_rows = _hs_ragged_shapes(leqs, cols)
+    em, eq_rows = _hs_ragged_shapes(eqs, cols)
+    leq_flat, leq_off, _ = _ragged_pack(lm, RAT, 2)
+    eq_flat, eq_off, _ = _ragged_pack(em, RAT, 2)
+    has = np.zeros(nb, dtype=np.int32)
+    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
+    any_eq = bool(eq_rows.sum())
+    ctx.check(lib().xpg_has_solution_batch_ragged_rat32(
+        ctx._h, C.c_int(nb), vp(leq_flat if leq_rows.sum() else None), vp(leq_rows), vp(leq_off), vp(eq_flat if any_eq else None), vp(eq_rows),
+        vp(eq_off if any_eq else None), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_int_sol)),
+        C.c_int(int(is_unique_sol)), C.c_uint(max_iter), vp(has), vp(st)), "xpg_has_solution_batch_ragged_rat32")
+    return (has, st) if want_status else has
+
+
+HAS_SOLUTION_RAGGED_ROUTE_FIELDS = ("lds", "hbm", "host", "second", "grid_lds", "grid_hbm", "no_solve")
+
+
+def has_solution_ragged_last_route():
+    """{'lds', 'hbm', 'host', 'second', 'grid_lds', 'grid_hbm', 'no_solve'}: systems of this thread's last has_solution_ragged
+    call on the LDS-resident kernel / the device-memory kernel / answered per system, the systems whose second solve ran, the
+    grids of the two launches (0 without one), the systems answered without a solve."""
+    return _view("xpg_has_solution_batch_ragged_last_route", HAS_SOLUTION_RAGGED_ROUTE_FIELDS)
+
+
+HAS_SOLUTION_RAGGED_FIELDS = ("lds_count", "lds_lds", "lds_threads", "lds_slot", "lds_grid",
+                              "hbm_count", "hbm_lds", "hbm_slot", "hbm_Rmax", "hbm_ld", "hbm_threads", "hbm_grid")
+
+
+def has_solution_ragged_plan(vc, leq_rows, eq_rows, num_cus=256):
+    """xpg_test_has_solution_batch_ragged_plan (host only, no device): what has_solution_ragged (is_int_sol False) does with
+    systems of leq_rows[b] inequalities and eq_rows[b] equalities under vc [cols - 1, cols(,2)]. Returns (route[nb] -- 0
+    LDS-resident kernel, 1 device-memory kernel, 2 per system, 3 without inequalities --, the two launches' sizes under
+    HAS_SOLUTION_RAGGED_FIELDS)."""
+    vc_a = as_kind(vc, RAT, 2)
+    lr = np.ascontiguousarray(leq_rows, dtype=np.int32); er = np.ascontiguousarray(eq_rows, dtype=np.int32)
+    if lr.shape != er.shape or lr.ndim != 1:
+        raise ValueError("leq_rows and eq_rows must list the same systems")
+    route = np.zeros(len(lr), dtype=np.int32)
+    sizes = _view("xpg_test_has_solution_batch_ragged_plan", HAS_SOLUTION_RAGGED_FIELDS, vp(vc_a), C.c_int(vc_a.shape[0]), C.c_int(vc_a.shape[1]),
+                  C.c_int(len(lr)), vp(lr), vp(er), C.c_int(num_cus), vp(route))
+    return route, sizes
+
+
 def ragged_pack_rat(mats_list):
     """(flat cells, rows[nb], cols[nb], cell offsets[nb + 1]) of a list of rational systems: the arrays the ragged C entry points take."""
     flat, off, parts = _ragged_pack(mats_list, RAT, 2)
