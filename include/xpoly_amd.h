@@ -521,6 +521,52 @@ int xpg_has_solution_batch_ragged_last_route(long long * out, int n);
  * xpg_test_has_solution_batch_plan reports for a system of that launch; a launch without systems reports zeros. */
 int xpg_test_has_solution_batch_ragged_plan(const void * vc, int vc_rows, int cols, int nb, const int32_t * leq_rows, const int32_t * eq_rows,
                                             int num_cus, int32_t * out_route /* [nb] */, long long * out, int n);
+/* Lineq::has_solution(..., is_int_sol = true, is_unique_sol) -- the form DepPoly::is_empty asks (src/eng/poly.cpp:571) -- for nb
+ * systems of one shape in one call that synchronises ONCE: leq [nb][leq_rows][cols], eq [nb][eq_rows][cols] and the free
+ * variables of vc [cols-1][cols] go up once, the feasibility objective is built on the device, both MIP walks and the verdict
+ * run there, and only the verdicts and the status pairs come down.  Host arrays, Rational only (the reference's has_solution
+ * is).  The shape rules are xpg_has_solution_batch_rat32's (XPG_ERR_SHAPE before anything touches a device; nb = 0 returns 0;
+ * without any row every verdict is 0, without an inequality XPG_ERR_REF_UNDEFINED).  out_has[b]: 1 / 0, or the negative status
+ * a walk of system b returned; out_status [nb][2] (may be NULL): the XPG_IP_* status of the maxm walk and of the minm walk,
+ * [1] = XPG_HS_NOT_RUN where maxm decided.  The caller's arrays are written at the very end only.
+ * Per system out_has and the out_status pair are bit for bit what xpg_has_solution_batch_rat32(..., is_int_sol = 1,
+ * is_unique_sol, ...) returns on the same arrays.  The route is the shape's alone (XPG_MIP_DEVICE is not read):
+ *   - vc a sign pattern and the node LPs of the deepest path within 64 KB of LDS in both directions: the tree-walk kernel of
+ *     xpg_mip_batch_vc_* twice -- maxm on all systems, minm under the marks a small kernel sets from maxm's verdicts --
+ *     with no host step between the passes;
+ *   - a sign pattern past that with both directions within the limits of xpg_mip_batch_vc_hbm_*: ONE launch, a workgroup per
+ *     system from the objective to the verdict, node tableaux in device memory, everything sized for the larger direction;
+ *   - anything else (a general vc, a shape past either direction's limits): xpg_has_solution_batch_rat32 with is_int_sol = 1.
+ * There is no _dev form: the walk sizes its workspace by the number of free variables, which a host that never sees vc cannot
+ * know.  Tableau slots live in the area of xpg_six_batch_hbm_* / xpg_mip_batch_vc_hbm_*; xpg_trim returns them.
+ * Tests: tests/test_has_solution_int_host.py, tests/test_gpu_has_solution_int.py. */
+int xpg_has_solution_int_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                     const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_unique_sol, int32_t * out_has,
+                                     int32_t * out_status /* [nb][2], may be NULL */);
+/* The same for systems of MIXED shapes under one vc: the arguments of xpg_has_solution_batch_ragged_rat32 without is_int_sol
+ * and max_iter.  The shape classes are formed on the host, in order of first sight, and each is answered by
+ * xpg_has_solution_int_batch_rat32; the answers come back in the order given.  Fusing the walks of different shapes into one
+ * launch stays open. */
+int xpg_has_solution_int_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, const int32_t * leq_rows, const long long * leq_offsets,
+                                            const xpg_rat32 * eq, const int32_t * eq_rows, const long long * eq_offsets, const xpg_rat32 * vc,
+                                            int vc_rows, int cols, int rhs_idx, int is_unique_sol, int32_t * out_has,
+                                            int32_t * out_status /* [nb][2], may be NULL */);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_has_solution_int_batch_* call did.  out[0] systems
+ * on the LDS-resident walk, [1] on the device-memory kernel, [2] answered by xpg_has_solution_batch_rat32, [3] systems whose
+ * second walk ran, [4] the grid of the maxm pass (of the one launch on the device-memory route; 0 without a launch), [5] the
+ * grid of the minm pass of the LDS-resident walk (else 0).  After the ragged call: the counts summed over its classes, the
+ * largest grids.  Fills min(n, 6) entries. */
+int xpg_has_solution_int_batch_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the route rule of xpg_has_solution_int_batch_* for nb systems of a shape under
+ * vc [vc_rows][cols] on a device of num_cus compute units -- the function the launches themselves ask.  Fills min(n, 17)
+ * entries; where there are two, maxm's then minm's: out[0] route (0 LDS-resident walk, 1 device-memory kernel, 2 neither);
+ * [1] free variables; [2] rows of the largest node LP; [3] [4] LDS bytes per workgroup (route 1: the larger side arrays,
+ * twice); [5] [6] threads; [7] [8] grid (route 1: the one launch's, twice; route 2: 0); [9] [10] helper workgroups behind the
+ * walkers (route 0); [11] bytes of one tableau slot (route 1: the larger direction's); [12] [13] ld; [14] workspace words of
+ * a workgroup (route 1: the objective included); [15] the word the objective starts at (route 1); [16] scratch bytes (route
+ * 0: the workspaces of the larger grid, helpers included; route 1: grid x (slot + workspace)). */
+int xpg_test_has_solution_int_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus,
+                                   long long * out, int n);
 
 /* Batches: nb independent problems of one shape, x >= 0, inequalities only
  * (tgtf[nb][cols], leq[nb][leq_rows][cols]).  Every tree is walked on the device by one

@@ -247,8 +247,9 @@ inline int dep_is_empty_all(const std::vector<RMatT *> & polys, std::vector<int3
 // (linsys.cpp:830-906) under one vc. leqs[k] / eqs[k] may be null or without rows; all non-empty matrices have rhs_idx + 1
 // columns. The systems are packed once, in the order given, and go up in ONE xpg_has_solution_batch_ragged_rat32 call
 // whatever their shapes (leq rows, eq rows): the library sends each system the way a batch of its shape goes -- one launch
-// per kernel, each system answered by one workgroup that normalises once and asks maxm, then minm -- and, for is_int_sol,
-// forms the shape classes itself. out[k] = 1 / 0 as has_solution would return, or a negative XPG_ERR_* where the reference is
+// per kernel, each system answered by one workgroup that normalises once and asks maxm, then minm. With is_int_sol the call is
+// xpg_has_solution_int_batch_ragged_rat32: the library forms the shape classes itself and answers each on the device --
+// objective, both integer walks and the verdict, one synchronisation per class. out[k] = 1 / 0 as has_solution would return, or a negative XPG_ERR_* where the reference is
 // undefined on system k. Returns 0 or a negative XPG_ERR_* code.
 template <class RMatT>
 inline int has_solution_all(const std::vector<RMatT *> & leqs, const std::vector<RMatT *> & eqs, const RMatT & vc, int rhs_idx,
@@ -275,6 +276,11 @@ inline int has_solution_all(const std::vector<RMatT *> & leqs, const std::vector
         if (erows[(size_t)b])
             std::memcpy((void *)(E.data() + eoff[(size_t)b]), (const void *)eqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * (size_t)erows[(size_t)b] * cols);
     }
+    if (is_int_sol)      // the integer form on the device: objective, both walks and the verdict, one synchronisation per shape class
+        return xpg_has_solution_int_batch_ragged_rat32(c ? c : detail::shared_context(), nb, L.empty() ? (const xpg_rat32 *)0 : L.data(),
+                                                       lrows.data(), loff.data(), E.empty() ? (const xpg_rat32 *)0 : E.data(), erows.data(),
+                                                       eoff.data(), (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx,
+                                                       is_unique_sol ? 1 : 0, out.data(), (int32_t *)0);
     return xpg_has_solution_batch_ragged_rat32(c ? c : detail::shared_context(), nb, L.empty() ? (const xpg_rat32 *)0 : L.data(), lrows.data(),
                                                loff.data(), E.empty() ? (const xpg_rat32 *)0 : E.data(), erows.data(), eoff.data(),
                                                (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, is_int_sol ? 1 : 0,

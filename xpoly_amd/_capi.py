@@ -41,6 +41,8 @@ SYMBOLS = [
     "xpg_mip_batch_vc_hbm_rat32", "xpg_mip_batch_vc_hbm_f64", "xpg_mip_hbm_last_route", "xpg_test_mip_hbm_plan",
     "xpg_has_solution_batch_rat32", "xpg_has_solution_batch_rat32_dev", "xpg_has_solution_batch_last_route", "xpg_test_has_solution_batch_plan",
     "xpg_has_solution_batch_ragged_rat32", "xpg_has_solution_batch_ragged_last_route", "xpg_test_has_solution_batch_ragged_plan",
+    "xpg_has_solution_int_batch_rat32", "xpg_has_solution_int_batch_ragged_rat32", "xpg_has_solution_int_batch_last_route",
+    "xpg_test_has_solution_int_plan",
 ]
 
 _lib = None

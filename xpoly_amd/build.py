@@ -37,7 +37,7 @@ DEPS = {
     6: ["lp_kernels.hip.h", "six_host.hip.h", "batch_kernels.hip.h", "batch_hbm.hip.h", "lineq_shared.hip.h", "mip_host.hip.h", "mip_kernels.hip.h",
         "mip_tree_hbm.hip.h", "normalize_dev.hip.h"],
     7: ["lp_kernels.hip.h", "six_host.hip.h", "batch_kernels.hip.h", "batch_hbm.hip.h", "six_batch_vc.hip.h", "six_batch_vc_hbm.hip.h", "normalize_dev.hip.h",
-        "has_solution_batch.hip.h"],
+        "has_solution_batch.hip.h", "lineq_shared.hip.h", "mip_host.hip.h", "mip_kernels.hip.h", "mip_tree_hbm.hip.h", "has_solution_int.hip.h"],
 }
 
 

@@ -23,7 +23,8 @@
 //   part 5  the same with equalities and free variables (k_six_batch_vc_hbm)
 //   part 6  MIP tree walks whose node LPs are beyond 64 KB of LDS (k_mip_tree_hbm)
 //   part 7  batched has_solution (k_has_solution_batch, k_has_solution_batch_hbm, and their forms for mixed shapes,
-//           k_has_solution_ragged, k_has_solution_ragged_hbm)
+//           k_has_solution_ragged, k_has_solution_ragged_hbm), and its integer form on the device (k_hs_int_objective,
+//           k_hs_int_update, k_has_solution_int_hbm)
 #ifndef XPG_PART
 #define XPG_PART (-1)
 #endif
@@ -62,6 +63,7 @@
 #endif
 #if XPG_IN(7)
 #include "has_solution_batch.hip.h"
+#include "has_solution_int.hip.h"
 #endif
 
 using namespace xpg;
@@ -91,6 +93,18 @@ template int batch_dev<R32>(xpg_ctx *, int, int, const R32 *, const R32 *, int, 
 namespace xpg { XPG_MIP_SHARED(extern, F64) XPG_MIP_SHARED(extern, R32) }
 #elif XPG_PART == 2
 namespace xpg { XPG_MIP_SHARED(, F64) XPG_MIP_SHARED(, R32) }
+#endif
+
+// mip_tree_launch<R32> (THE launch of k_mip_tree): part 2 compiles it, part 7 (has_solution's integer form, which runs the walk
+// twice) calls part 2's instance
+#define XPG_MIP_TREE_LAUNCH(X_, S_) \
+    X_ template int mip_tree_launch<S_>(xpg_ctx *, const MipGeom &, int, int, const void *, const void *, int, int, bool, bool, int, int, void *, \
+                                        size_t, void *, void *, void *, void *, const void *, const void *, const void *, const void *, int, void *, \
+                                        const void *, int);
+#if XPG_PART == 7
+namespace xpg { XPG_MIP_TREE_LAUNCH(extern, R32) }
+#elif XPG_PART == 2
+namespace xpg { XPG_MIP_TREE_LAUNCH(, R32) }
 #endif
 
 // six_batch_vc_host<S> / six_batch_vc_dev<S> (k_six_batch_vc, six_solve): part 1 compiles them, part 5 (shapes that do fit
@@ -1665,6 +1679,57 @@ int xpg_test_has_solution_batch_ragged_plan(const void * vc, int vc_rows, int co
     const HsRaggedLaunch & a = p.at[HS_ROUTE_LDS]; const HsRaggedLaunch & h = p.at[HS_ROUTE_HBM];
     const long long f[12] = { a.count, (long long)a.lds, a.threads, (long long)a.slot, a.grid,
                               h.count, (long long)h.lds, (long long)h.slot, h.Rmax, h.ld, h.threads, h.grid };
+    return copy_fields(out, n, f);
+}
+// ---- Lineq::has_solution with is_int_sol = 1 for a batch: the objective, both MIP walks and the verdict on the device, one
+// ---- synchronisation (has_solution_int.hip.h) ----
+int xpg_has_solution_int_batch_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, int leq_rows, const xpg_rat32 * eq, int eq_rows,
+                                     const xpg_rat32 * vc, int vc_rows, int cols, int rhs_idx, int is_unique_sol, int32_t * out_has,
+                                     int32_t * out_status)
+{
+    XPG_BIND(ctx);
+    return has_solution_int_batch<R32>(ctx, nb, (const R32 *)leq, leq_rows, (const R32 *)eq, eq_rows, (const R32 *)vc, vc_rows, cols, rhs_idx,
+                                       is_unique_sol != 0, out_has, out_status, [&](int32_t * has, int32_t * st) {   // the parent's composition
+        return xpg_has_solution_batch_rat32(ctx, nb, leq, leq_rows, eq, eq_rows, vc, vc_rows, cols, rhs_idx, 1, is_unique_sol, 0xFFFFFFFFu, has, st);
+    });
+}
+// the same for systems of mixed shapes under one vc: the shape classes on the host, each answered by the uniform call
+int xpg_has_solution_int_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * leq, const int32_t * leq_rows, const long long * leq_offsets,
+                                            const xpg_rat32 * eq, const int32_t * eq_rows, const long long * eq_offsets, const xpg_rat32 * vc,
+                                            int vc_rows, int cols, int rhs_idx, int is_unique_sol, int32_t * out_has, int32_t * out_status)
+{
+    XPG_BIND(ctx);
+    HsIntRoute sum = {0, 0, 0, 0, 0, 0};
+    const int rc = has_solution_ragged_int(ctx, nb, (const R32 *)leq, leq_rows, leq_offsets, (const R32 *)eq, eq_rows, eq_offsets, (const R32 *)vc,
+                                           vc_rows, cols, rhs_idx, out_has, out_status,
+                                           [&](int lr, int er, int count, const R32 * l, const R32 * e, int32_t * has, int32_t * st) {
+        const int r = xpg_has_solution_int_batch_rat32(ctx, count, (const xpg_rat32 *)l, lr, (const xpg_rat32 *)e, er, vc, vc_rows, cols, rhs_idx,
+                                                       is_unique_sol, has, st);
+        const HsIntRoute & one = hs_int_route();
+        sum.lds += one.lds; sum.hbm += one.hbm; sum.host += one.host; sum.second += one.second;
+        sum.grid = std::max(sum.grid, one.grid); sum.grid2 = std::max(sum.grid2, one.grid2);
+        return r;
+    });
+    hs_int_route() = rc == 0 ? sum : HsIntRoute{0, 0, 0, 0, 0, 0};
+    return rc;
+}
+// what the calling thread's last xpg_has_solution_int_batch_* call did (has_solution_int.hip.h HsIntRoute)
+int xpg_has_solution_int_batch_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const HsIntRoute & r = hs_int_route();
+    const long long f[6] = { r.lds, r.hbm, r.host, r.second, r.grid, r.grid2 };
+    return copy_fields(out, n, f);
+}
+// host-only test view: the route rule of xpg_has_solution_int_batch_* and the sizes it decides by
+int xpg_test_has_solution_int_plan(const void * vc, int vc_rows, int leq_rows, int eq_rows, int cols, int nb, int num_cus, long long * out, int n)
+{
+    if (!vc || !out || n < 0 || cols < 2 || vc_rows != cols - 1 || leq_rows <= 0 || eq_rows < 0 || nb <= 0 || num_cus <= 0) return XPG_ERR_SHAPE;
+    const VcView v = vc_view<R32>(vc, vc_rows, cols);
+    const HsIntPlan g = hs_int_plan<R32>(v.pattern, v.nfree, leq_rows, eq_rows, cols, nb, num_cus);
+    const long long f[17] = { g.route, g.extra, g.rmax, (long long)g.lds[0], (long long)g.lds[1], g.threads[0], g.threads[1], g.grid[0], g.grid[1],
+                              g.nhelp[0], g.nhelp[1], (long long)g.slot, g.ld[0], g.ld[1], (long long)g.ws_words, (long long)g.obj_word,
+                              (long long)g.scratch };
     return copy_fields(out, n, f);
 }
 } // extern "C"

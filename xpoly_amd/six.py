@@ -866,6 +866,83 @@ def has_solution_ragged_plan(vc, leq_rows, eq_rows, num_cus=256):
     return route, sizes
 
 
+def has_solution_int_batch(ctx, leq, eq, vc, is_unique_sol, want_status=False):
+    """Lineq::has_solution(..., is_int_sol=True, is_unique_sol) for nb rational systems of one shape in one call that
+    synchronises once (xpg_has_solution_int_batch_rat32): the arrays of has_solution_batch; the feasibility objective, both MIP
+    walks and the verdict run on the device wherever vc is a sign pattern and the shape is within the walks' limits, anything
+    else as has_solution_batch(is_int_sol=True) answers it. Returns has[nb], and with want_status also status[nb, 2] -- bit for
+    bit what has_solution_batch(..., True, is_unique_sol) returns."""
+    vc = as_kind(vc, RAT, 2)
+    cols = vc.shape[1]
+    leq_a = None if leq is None else as_kind(leq, RAT, 3)
+    eq_a = None if eq is None else as_kind(eq, RAT, 3)
+    if leq_a is None and eq_a is None:
+        raise ValueError("leq and eq are both None: the batch size is unknown")
+    nb = (leq_a if leq_a is not None else eq_a).shape[0]
+    for a in (leq_a, eq_a):
+        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
+            raise ValueError("leq / eq must be [nb, rows, cols]")
+    rows = 0 if leq_a is None else leq_a.shape[1]
+    eq_rows = 0 if eq_a is None else eq_a.shape[1]
+    has = np.zeros(nb, dtype=np.int32)
+    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
+    ctx.check(lib().xpg_has_solution_int_batch_rat32(ctx._h, C.c_int(nb), vp(leq_a if rows else None), C.c_int(rows),
+                                                     vp(eq_a if eq_rows else None), C.c_int(eq_rows), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols),
+                                                     C.c_int(cols - 1), C.c_int(int(is_unique_sol)), vp(has), vp(st)),
+              "xpg_has_solution_int_batch_rat32")
+    return (has, st) if want_status else has
+
+
+def has_solution_int_ragged(ctx, leqs, eqs, vc, is_unique_sol, want_status=False):
+    """has_solution_int_batch for systems of MIXED shapes under one vc (xpg_has_solution_int_batch_ragged_rat32): the lists of
+    has_solution_ragged; the shape classes are formed by the library, each answered by the uniform call, the answers come back
+    in the order given. Returns has[nb], and with want_status also status[nb, 2]."""
+    vc = as_kind(vc, RAT, 2)
+    cols = vc.shape[1]
+    nb = len(leqs)
+    if eqs is None:
+        eqs = [None] * nb
+    if len(eqs) != nb:
+        raise ValueError("leqs and eqs must list the same systems")
+    lm, leq_rows = _hs_ragged_shapes(leqs, cols)
+    em, eq_rows = _hs_ragged_shapes(eqs, cols)
+    leq_flat, leq_off, _ = _ragged_pack(lm, RAT, 2)
+    eq_flat, eq_off, _ = _ragged_pack(em, RAT, 2)
+    has = np.zeros(nb, dtype=np.int32)
+    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
+    any_eq = bool(eq_rows.sum())
+    ctx.check(lib().xpg_has_solution_int_batch_ragged_rat32(
+        ctx._h, C.c_int(nb), vp(leq_flat if leq_rows.sum() else None), vp(leq_rows), vp(leq_off), vp(eq_flat if any_eq else None), vp(eq_rows),
+        vp(eq_off if any_eq else None), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_unique_sol)), vp(has),
+        vp(st)), "xpg_has_solution_int_batch_ragged_rat32")
+    return (has, st) if want_status else has
+
+
+HAS_SOLUTION_INT_ROUTE_FIELDS = ("lds", "hbm", "host", "second", "grid", "grid2")
+
+
+def has_solution_int_last_route():
+    """{'lds', 'hbm', 'host', 'second', 'grid', 'grid2'}: systems of this thread's last has_solution_int_batch /
+    has_solution_int_ragged call on the LDS-resident walk / the device-memory kernel / answered by has_solution_batch, the
+    systems whose second walk ran, the grid of the maxm pass (or of the one device-memory launch) and of the LDS-resident minm
+    pass. After a ragged call: counts summed over the classes, the largest grids."""
+    return _view("xpg_has_solution_int_batch_last_route", HAS_SOLUTION_INT_ROUTE_FIELDS)
+
+
+HAS_SOLUTION_INT_FIELDS = ("route", "free", "rmax", "lds_max", "lds_min", "threads_max", "threads_min", "grid_max", "grid_min",
+                           "help_max", "help_min", "slot", "ld_max", "ld_min", "ws_words", "obj_word", "scratch")
+
+
+def has_solution_int_plan(vc, leq_rows, eq_rows, cols, nb, num_cus=256):
+    """xpg_test_has_solution_int_plan (host only, no device): what has_solution_int_batch does with nb systems of a shape under
+    vc [cols - 1, cols(,2)] -- route (0 LDS-resident walk twice, 1 device-memory kernel, 2 has_solution_batch's composition),
+    free variables, rows of the largest node LP, and per direction (_max: the maxm walk, _min: the minm walk) LDS bytes, threads,
+    grid, helper workgroups and ld; bytes of one tableau slot, workspace words, the word the objective starts at, scratch bytes."""
+    vc_a = as_kind(vc, RAT, 2)
+    return _view("xpg_test_has_solution_int_plan", HAS_SOLUTION_INT_FIELDS, vp(vc_a), C.c_int(vc_a.shape[0]), C.c_int(leq_rows),
+                 C.c_int(eq_rows), C.c_int(cols), C.c_int(nb), C.c_int(num_cus))
+
+
 def ragged_pack_rat(mats_list):
     """(flat cells, rows[nb], cols[nb], cell offsets[nb + 1]) of a list of rational systems: the arrays the ragged C entry points take."""
     flat, off, parts = _ragged_pack(mats_list, RAT, 2)
