@@ -808,6 +808,46 @@ int xpg_lineq_reduce_batch_rat32_dev(xpg_ctx * ctx, int nb, xpg_rat32 * d_mats, 
 int xpg_lineq_fme_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
                                   int u, int darkshadow, xpg_rat32 * d_outs, int cap_rows, int32_t * d_out_rows,
                                   int32_t * d_out_ok);
+/* A PROJECTION: the variables elim[0 .. n_elim) eliminated one after the other, each Lineq::fme's result the input of the
+ * next (DepPoly::eliminateAuxVar, src/eng/poly.cpp:643-651; the scanning bounds, src/eng/poly.cpp:4807-4813), for nb systems of
+ * one shape in ONE launch: every step of a system runs before its wavefront takes the next system, intermediates live in
+ * LDS or in two device slots per resident wavefront, and only the final rows are stored per system.  The list is the
+ * batch's (host memory, at most 64 entries: more is XPG_ERR_UNSUPPORTED); an index may repeat, the repeated step copies
+ * as the reference's does.  darkshadow goes to every step.
+ *   cap_rows      rows an intermediate or a final result may have before it is reduced; <= 0: fme's worst case for `rows`
+ *   cap_out_rows  rows of a system's final slot; <= 0 (or above cap_rows): cap_rows
+ *   out_ok[b]     1: out_steps[b] = n_elim and system b's rows are packed (none where an intermediate came out empty: fme
+ *                 of an empty system is true and empty);  0: step out_steps[b] found the system inconsistent;  -need: step
+ *                 out_steps[b] needs `need` > cap_rows rows, or (out_steps[b] == n_elim) the final result has `need` >
+ *                 cap_out_rows rows.  A system with out_ok[b] <= 0 contributes no rows; the others are packed all the same.
+ * outs, outs_cap_rows, out_view and row_offsets as xpg_lineq_fme_batch_packed_rat32 (neither outs nor out_view: a sizing
+ * call).  XPG_ERR_SHAPE: n_elim <= 0, an index outside [0, rhs_idx), rhs_idx outside [1, cols); XPG_ERR_UNSUPPORTED: the LDS
+ * layout of cap_rows exceeds 160 KB, or cap_rows > 32767. */
+int xpg_lineq_project_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
+                                         const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                         xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                         long long * row_offsets, int32_t * out_ok, int32_t * out_steps);
+/* The same on DEVICE arrays, enqueue only (elim stays a host array: it travels as a kernel argument): d_outs
+ * [nb][cap_out_rows][cols] receives each result's live rows and is not cleared behind them, d_out_rows / d_out_ok /
+ * d_out_steps [nb].  The intermediates' slots belong to the handle (grow-only; xpg_trim returns them).  The row stride of
+ * d_outs is the caller's: nothing is defaulted or clamped here -- cap_rows < rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE;
+ * cap_out_rows <= 0 alone stands for cap_rows (slots of cap_rows rows). */
+int xpg_lineq_project_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
+                                      const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                      xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_lineq_project_batch_* call did.  out[0] launches of
+ * the chain kernel (1; 0 where nothing was launched), [1] its grid, [2] systems per workgroup, [3] LDS bytes per system,
+ * [4] rows of the LDS result area (a step at or under it is built in LDS), [5] bytes of intermediate slots the launch was
+ * given: grid x [2] x 2 x cap_rows x cols x 8, whatever nb is.  Fills min(n, 6) entries. */
+int xpg_lineq_project_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same six figures from the shape alone -- the function the launch itself
+ * asks -- then [6] the cap_rows and [7] the cap_out_rows it settles on.  Fills min(n, 8) entries; XPG_ERR_SHAPE /
+ * XPG_ERR_UNSUPPORTED as the call. */
+int xpg_test_lineq_project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_rows, long long * out, int n);
+/* Host-only view for tests: what both projection calls answer to an elimination list before they look at the handle or at
+ * anything else -- 0, XPG_ERR_SHAPE (n_elim <= 0, no list, an index outside [0, rhs_idx), rhs_idx outside [1, cols)) or
+ * XPG_ERR_UNSUPPORTED (more than 64 entries).  The function the calls themselves ask. */
+int xpg_test_lineq_project_check(int cols, int rhs_idx, const int32_t * elim, int n_elim);
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank);
 int xpg_rat_rank_batch(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols,
                        int32_t * out_rank);

@@ -9,7 +9,8 @@
 //
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
-// should use). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
+// should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
+// calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
 #define XPOLY_AMD_LINEQ_HPP
@@ -162,7 +163,7 @@ public:
                                              darkshadow ? 1 : 0, 0, (xpg_rat32 *)0, 0, &view, off, &ok) != 0) return false;
         const int orows = (int)off[1];
         res.reinit(orows, cols);
-        if (orows * cols) std::memcpy((void *)res.get_matrix(), (const void *)view, sizeof(xpg_rat32) * (size_t)orows * cols);
+        if (orows > 0 && cols > 0) std::memcpy((void *)res.get_matrix(), (const void *)view, sizeof(xpg_rat32) * (size_t)orows * cols);
         return ok != 0;
     }
     // Lineq::has_solution, linsys.cpp:830-906
@@ -343,6 +344,67 @@ inline int fme_all(const std::vector<RMatT *> & systems, const std::vector<int32
         if (orows[(size_t)k] * cols[(size_t)k])
             std::memcpy((void *)res.get_matrix(), (const void *)(outs.data() + ooff[(size_t)k]), sizeof(xpg_rat32) * (size_t)orows[(size_t)k] * cols[(size_t)k]);
         ok[(size_t)live[(size_t)k]] = ook[(size_t)k];
+    }
+    return 0;
+}
+
+// Many projections in few calls: the variables elim[0], elim[1], ... eliminated out of every *systems[k], each Lineq::fme's
+// result the next one's input -- DepPoly::eliminateAuxVar's loop (src/eng/poly.cpp:643-651: for u = rhs - 1 .. l) and the
+// scanning bounds (src/eng/poly.cpp:4807-4813) -- the constant in column rhs_idx of every system. Systems of one shape go up
+// together, one xpg_lineq_project_batch_packed_rat32 call per shape class: every step of a system in one launch, only the
+// final rows come back. ok[k] = 1 and results[k] the projection, or 0 (a step found the system inconsistent, as the loop's
+// fme would return false) with results[k] empty. A class one of whose systems needs more rows than the capacity tried is
+// called again with the need the library reports, at most three times; still short: XPG_ERR_UNSUPPORTED, never a silent
+// empty result. Returns 0 or a negative XPG_ERR_* code.
+template <class RMatT>
+inline int project_all(const std::vector<RMatT *> & systems, const std::vector<int32_t> & elim, int rhs_idx,
+                       std::vector<RMatT> & results, std::vector<int32_t> & ok, xpg_ctx * c = 0, bool darkshadow = false)
+{
+    const int nb = (int)systems.size();
+    results.resize((size_t)nb); ok.assign((size_t)nb, 0);
+    if (elim.empty() || rhs_idx < 1) return XPG_ERR_SHAPE;
+    xpg_ctx * h = c ? c : detail::shared_context();
+    std::vector<char> done((size_t)nb, 0);
+    for (int b0 = 0; b0 < nb; b0++) {
+        if (done[(size_t)b0]) continue;
+        if (systems[(size_t)b0]->size() == 0) {                     // an empty system stays empty (linsys.cpp:661-664), no call
+            results[(size_t)b0].clean(); ok[(size_t)b0] = 1; done[(size_t)b0] = 1;
+            continue;
+        }
+        const int rows = (int)systems[(size_t)b0]->get_row_size(), cols = (int)systems[(size_t)b0]->get_col_size();
+        std::vector<int> cls;
+        for (int b = b0; b < nb; b++)
+            if (!done[(size_t)b] && systems[(size_t)b]->size() != 0 && (int)systems[(size_t)b]->get_row_size() == rows &&
+                (int)systems[(size_t)b]->get_col_size() == cols) {
+                cls.push_back(b); done[(size_t)b] = 1;
+            }
+        const int nc = (int)cls.size();
+        std::vector<xpg_rat32> flat((size_t)nc * rows * cols);
+        for (int k = 0; k < nc; k++)
+            std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
+        int cap = 0;                                                // the library's default first; the final slots take cap too
+        bool answered = false;
+        for (int attempt = 0; attempt < 3 && !answered; attempt++) {
+            std::vector<long long> off((size_t)nc + 1, 0);
+            std::vector<int32_t> kok((size_t)nc, 0), steps((size_t)nc, 0);
+            const xpg_rat32 * view = 0;
+            const int rc = xpg_lineq_project_batch_packed_rat32(h, nc, flat.data(), rows, cols, rhs_idx, elim.data(), (int)elim.size(),
+                                                                darkshadow ? 1 : 0, cap, 0, (xpg_rat32 *)0, 0, &view, off.data(),
+                                                                kok.data(), steps.data());
+            if (rc != 0) return rc;
+            int need = 0;
+            for (int k = 0; k < nc; k++) if (kok[(size_t)k] < 0 && -kok[(size_t)k] > need) need = -kok[(size_t)k];
+            if (need) { cap = need; continue; }                     // a step needed more rows than cap: once more with that many
+            for (int k = 0; k < nc; k++) {
+                const int b = cls[(size_t)k];
+                const long long lo = off[(size_t)k], hi = off[(size_t)k + 1];
+                ok[(size_t)b] = kok[(size_t)k];
+                results[(size_t)b].reinit((unsigned)(hi - lo), (unsigned)cols);
+                if (hi > lo) std::memcpy((void *)results[(size_t)b].get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
+            }
+            answered = true;
+        }
+        if (!answered) return XPG_ERR_UNSUPPORTED;
     }
     return 0;
 }

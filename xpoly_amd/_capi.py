@@ -43,6 +43,8 @@ SYMBOLS = [
     "xpg_has_solution_batch_ragged_rat32", "xpg_has_solution_batch_ragged_last_route", "xpg_test_has_solution_batch_ragged_plan",
     "xpg_has_solution_int_batch_rat32", "xpg_has_solution_int_batch_ragged_rat32", "xpg_has_solution_int_batch_last_route",
     "xpg_test_has_solution_int_plan",
+    "xpg_lineq_project_batch_packed_rat32", "xpg_lineq_project_batch_rat32_dev", "xpg_lineq_project_last_route",
+    "xpg_test_lineq_project_plan", "xpg_test_lineq_project_check",
 ]
 
 _lib = None

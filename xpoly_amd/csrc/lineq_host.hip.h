@@ -181,6 +181,83 @@ inline int lineq_fme_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows, in
     return 0;
 }
 
+// The way down of a packed-result call (fme, projection), after its kernel is enqueued: dout [nb][cap][cols] holds each
+// system's live rows at the front of its slot, dr their counts, dk the verdicts, ds (may be NULL) the steps. The handle's
+// pinned buffer (hpack, or hred when `internal`) was reserved by the caller as [meta_al: offsets, ok, rows, steps][in_stage:
+// the staged input][the slots, when small_out]. small_out: the slots come down with the counts and are packed on the host --
+// one synchronisation, no scan / pack launches (a handful of systems: the drop-in adapter eliminates one per call). Else
+// k_rows_scan, one synchronisation for the offsets, k_pack_rows, and only live rows cross the link. short_msg != NULL: a
+// negative count (a result that needs -count rows) ends the call with XPG_ERR_UNSUPPORTED, the count in row_offsets[0].
+template <class Lap>
+inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & dout, DevBuf & dr, DevBuf & dk, DevBuf * ds, DevBuf & doff,
+                            size_t meta_al, size_t in_stage, bool small_out, bool internal, const char * short_msg, R32 * out,
+                            long long out_cap_rows, const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps, Lap lap)
+{
+    char * hp = hpack_buf(ctx, internal);
+    const size_t bo = (size_t)nb * cap * cols * 8;
+    long long * h_off = (long long *)hp; int32_t * h_ok = (int32_t *)(hp + (size_t)(nb + 1) * 8); int32_t * h_rows = h_ok + nb;
+    int32_t * h_steps = h_rows + nb;
+    XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(h_rows, dr.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (ds) XPG_TRY(hipMemcpyAsync(h_steps, ds->p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (small_out) {
+        char * hs = hp + meta_al + in_stage;
+        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        long long tot = 0;
+        for (int b = 0; b < nb; b++) {
+            if (short_msg && h_rows[b] < 0) { ctx->err = short_msg; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
+            row_offsets[b] = tot; tot += h_rows[b];
+        }
+        row_offsets[nb] = tot;
+        memcpy(out_ok, h_ok, (size_t)nb * 4);
+        if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
+        if (out && out_cap_rows < tot) return XPG_ERR_SHAPE;
+        const size_t rowb = (size_t)cols * 8;
+        for (int b = 0; b < nb; b++) {                             // forward moves: a destination never lies above its source
+            const size_t nbytes = (size_t)(row_offsets[b + 1] - row_offsets[b]) * rowb;
+            if (out) memcpy((char *)out + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
+            if (view) memmove(hs + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
+        }
+        if (view) *view = (const R32 *)hs;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nb, (const int *)dr.p, (long long *)doff.p);
+    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipStreamSynchronize(ctx->stream));
+    if (short_msg)
+        for (int b = 0; b < nb; b++)
+            if (h_rows[b] < 0) { ctx->err = short_msg; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
+    memcpy(row_offsets, h_off, (size_t)(nb + 1) * 8);
+    memcpy(out_ok, h_ok, (size_t)nb * 4);
+    if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
+    const long long total = row_offsets[nb];
+    if (out && out_cap_rows < total) return XPG_ERR_SHAPE;
+    if (total == 0 || (!out && !view)) return 0;                   // (neither: a sizing call)
+    const size_t bp = (size_t)total * cols * 8;
+    lap("scan+meta");
+    DevBuf dpk;
+    XPG_TRY(dpk.alloc(ctx, bp));
+    hipLaunchKernelGGL(k_pack_rows, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, (const R32 *)dout.p, cap, cols,
+                       (const int *)dr.p, (const long long *)doff.p, (R32 *)dpk.p);
+    XPG_TRY(hipGetLastError());
+    lap("pack");
+    if (view) {                                                    // into pinned memory; the caller's copy, if any, from there
+        const int rc = hpack_reserve(ctx, bp, internal);
+        if (rc) return rc;
+        char * hv = hpack_buf(ctx, internal);
+        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        if (out) memcpy(out, hv, bp);
+        *view = (const R32 *)hv;
+    } else {
+        XPG_TRY(hipMemcpyAsync(out, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    lap("d2h");
+    return 0;
+}
+
 // Lineq::fme for nb systems with a PACKED result: row_offsets[nb + 1] (rows, not bytes) and the
 // live rows of every system back to back, instead of nb worst-case slots of cap_rows rows (the typical result is a
 // third of the worst case: 751 MB of slots against 267 MB of rows for 16 384 systems of 40 x 13). The systems go up and
@@ -199,7 +276,7 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
     if (cap < rows) cap = rows;
     const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nb * cap * cols * 8;
     const size_t meta = (size_t)(nb + 1) * 8 + (size_t)nb * 8;       // offsets, then ok and rows
-    DevBuf di, dout, dr, dk, doff, dpk;
+    DevBuf di, dout, dr, dk, doff;
     XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
     XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
     static const bool dbg = xpg_hook("XPG_LINEQ_DEBUG") != 0;
@@ -222,63 +299,107 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
     rc = lineq_fme_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, u, darkshadow, (R32 *)dout.p, cap, (int32_t *)dr.p, (int32_t *)dk.p);
     if (rc) return rc;
     lap("kernel");
-    long long * h_off = (long long *)hp; int32_t * h_ok = (int32_t *)(hp + (size_t)(nb + 1) * 8); int32_t * h_rows = h_ok + nb;
-    XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(h_rows, dr.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (small_out) {
-        // a handful of systems (the drop-in adapter eliminates one per call): the slots themselves come down in the
-        // same round and are packed here -- one synchronisation, no scan / pack launches
-        char * hs = hp + meta_al + (small_in ? bi : 0);
-        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        long long tot = 0;
-        for (int b = 0; b < nb; b++) {
-            if (h_rows[b] < 0) { ctx->err = "fme: a result needs more rows than cap_rows"; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
-            row_offsets[b] = tot; tot += h_rows[b];
-        }
-        row_offsets[nb] = tot;
-        memcpy(out_ok, h_ok, (size_t)nb * 4);
-        if (out && out_cap_rows < tot) return XPG_ERR_SHAPE;
-        const size_t rowb = (size_t)cols * 8;
-        for (int b = 0; b < nb; b++) {                             // forward moves: a destination never lies above its source
-            const size_t nbytes = (size_t)(row_offsets[b + 1] - row_offsets[b]) * rowb;
-            if (out) memcpy((char *)out + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
-            if (view) memmove(hs + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
-        }
-        if (view) *view = (const R32 *)hs;
-        return 0;
-    }
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nb, (const int *)dr.p, (long long *)doff.p);
-    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < nb; b++)
-        if (h_rows[b] < 0) { ctx->err = "fme: a result needs more rows than cap_rows"; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
-    memcpy(row_offsets, h_off, (size_t)(nb + 1) * 8);
-    memcpy(out_ok, h_ok, (size_t)nb * 4);
-    const long long total = row_offsets[nb];
-    if (out && out_cap_rows < total) return XPG_ERR_SHAPE;
-    if (total == 0 || (!out && !view)) return 0;                   // (neither: a sizing call)
-    const size_t bp = (size_t)total * cols * 8;
-    lap("scan+meta");
-    XPG_TRY(dpk.alloc(ctx, bp));
-    hipLaunchKernelGGL(k_pack_rows, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, (const R32 *)dout.p, cap, cols,
-                       (const int *)dr.p, (const long long *)doff.p, (R32 *)dpk.p);
-    XPG_TRY(hipGetLastError());
-    lap("pack");
-    if (view) {                                                    // into pinned memory; the caller's copy, if any, from there
-        rc = hpack_reserve(ctx, bp, internal);
-        if (rc) return rc;
-        char * hv = hpack_buf(ctx, internal);
-        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        if (out) memcpy(out, hv, bp);
-        *view = (const R32 *)hv;
-    } else {
-        XPG_TRY(hipMemcpyAsync(out, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    lap("d2h");
+    return packed_rows_down(ctx, nb, cols, cap, dout, dr, dk, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, internal,
+                            "fme: a result needs more rows than cap_rows", out, out_cap_rows, view, row_offsets, out_ok, (int32_t *)0, lap);
+}
+
+// ---- projection: a list of variables eliminated in ONE launch (k_fme_chain_batch) -------------------------------------------
+// THE plan of a projection call (the launch and xpg_test_lineq_project_plan both ask it): capacities, LDS layout, geometry and
+// the seats' intermediates, from the shape alone. cap_rows <= 0: fme's default for `rows`; cap_out_rows <= 0 (or above cap):
+// cap. The LDS layout is fme_lds(cap, cap, cols), the rule calcBound's chains run under -- measured for k_fme_batch, not again
+// for the chain kernel. Returns 0, XPG_ERR_SHAPE or XPG_ERR_UNSUPPORTED (LDS over 160 KB, cap > 32767).
+struct ProjectPlan { int cap, cap_out, cap_lds; LineqGeom q; long long seats; size_t seat_bytes; };
+inline int project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_rows, ProjectPlan & p)
+{
+    if (nb <= 0 || rows <= 0 || cols <= 1) return XPG_ERR_SHAPE;
+    p.cap = cap_rows <= 0 ? rows * rows / 4 + rows + 1 : cap_rows;
+    if (p.cap < rows) p.cap = rows;
+    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
+    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
+    const FmeLds fl = fme_lds(p.cap, p.cap, cols);
+    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    p.cap_lds = fl.cap_lds;
+    p.q = lineq_geom(nb, 64, fl.lds);
+    p.seats = (long long)p.q.grid * p.q.G;
+    p.seat_bytes = (size_t)p.seats * 2 * (size_t)p.cap * cols * 8;
     return 0;
+}
+// What the calling thread's last xpg_lineq_project_batch_* call did (xpg_lineq_project_last_route): launches of the chain
+// kernel (1), its grid, groups per workgroup, LDS bytes per system, cap_lds, bytes of seat slots the launch was given.
+struct ProjectRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes; };
+inline ProjectRoute & project_route() { static thread_local ProjectRoute r = {0, 0, 0, 0, 0, 0}; return r; }
+
+inline int project_check(int cols, int rhs, const int32_t * elim, int n_elim)
+{
+    if (cols <= 1 || rhs < 1 || rhs >= cols || !elim || n_elim <= 0) return XPG_ERR_SHAPE;
+    for (int k = 0; k < n_elim; k++) if (elim[k] < 0 || elim[k] >= rhs) return XPG_ERR_SHAPE;
+    return n_elim > FME_CHAIN_MAX ? XPG_ERR_UNSUPPORTED : 0;
+}
+// Device arrays, enqueue only: d_outs [nb][cap_out_rows][cols] receives the live rows of each result (nothing behind them),
+// d_rows / d_ok / d_steps [nb] as k_fme_chain_batch writes them. The seats' slots are the handle's (grow-only). The row
+// stride of d_outs is the caller's: cap_rows < rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE, nothing is defaulted or
+// clamped but cap_out_rows <= 0, which stands for cap_rows.
+inline int lineq_project_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
+                                   int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows,
+                                   int32_t * d_ok, int32_t * d_steps)
+{
+    project_route() = ProjectRoute{0, 0, 0, 0, 0, 0};
+    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
+    if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || !d_rows || !d_ok || !d_steps) return XPG_ERR_SHAPE;
+    // the caller laid d_outs out with these capacities: none is replaced here (cap_out_rows <= 0 alone stands for cap_rows)
+    if (cap_rows < rows || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    ProjectPlan p;
+    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, p)) return rc;
+    Scratch & slots = ctx->scratch[SCRATCH_LINEQ_PROJECT];
+    if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_project seats)")) return rc;
+    ElimList el;
+    el.n = n_elim;
+    for (int k = 0; k < FME_CHAIN_MAX; k++) el.u[k] = k < n_elim ? elim[k] : 0;
+    XPG_TRY(lds_limit((const void *)k_fme_chain_batch, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_fme_chain_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, el,
+                       darkshadow, (R32 *)slots.buf, p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps,
+                       p.cap_lds, p.q.sys_lds);
+    XPG_TRY(hipGetLastError());
+    project_route() = ProjectRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes};
+    return 0;
+}
+// Host arrays with a PACKED result, as lineq_fme_batch_packed: one upload, the one launch, k_rows_scan / k_pack_rows, one
+// synchronisation before the rows come down (none after it where the slots are small enough to come down with the counts).
+// A system that ends with out_ok <= 0 contributes no rows; the others are packed all the same. XPG_ERR_SHAPE when `out` holds
+// fewer than row_offsets[nb] rows (row_offsets, out_ok and out_steps are filled); neither out nor view: a sizing call.
+inline int lineq_project_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, const int32_t * elim,
+                                      int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
+                                      const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
+{
+    if (view) *view = 0;
+    project_route() = ProjectRoute{0, 0, 0, 0, 0, 0};
+    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
+    if (!ctx || nb < 0 || !mats || rows <= 0 || !row_offsets || !out_ok || !out_steps || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
+    if (nb == 0) { row_offsets[0] = 0; return 0; }
+    ProjectPlan p;
+    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, p)) return rc;
+    const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nb * p.cap_out * cols * 8;
+    const size_t meta = (size_t)(nb + 1) * 8 + (size_t)nb * 12;      // offsets, then ok, rows and steps
+    const size_t meta_al = (meta + 255) & ~(size_t)255;
+    DevBuf di, dout, dr, dk, ds, doff;
+    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
+    XPG_TRY(ds.alloc(ctx, (size_t)nb * 4)); XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
+    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
+    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
+    if (rc) return rc;
+    char * hp = hpack_buf(ctx, false);
+    if (small_in) {
+        memcpy(hp + meta_al, mats, bi);
+        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = lineq_project_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, elim, n_elim, darkshadow, p.cap, p.cap_out, (R32 *)dout.p,
+                                 (int32_t *)dr.p, (int32_t *)dk.p, (int32_t *)ds.p);
+    if (rc) return rc;
+    return packed_rows_down(ctx, nb, cols, p.cap_out, dout, dr, dk, &ds, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
+                            out, out_cap_rows, view, row_offsets, out_ok, out_steps, [](const char *) {});
 }
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for nb systems at once: for every variable j the

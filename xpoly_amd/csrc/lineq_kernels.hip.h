@@ -385,6 +385,121 @@ __global__ __launch_bounds__(64) void k_reduce_batch(int nb, R32 * mats, int row
     }
 }
 
+// One elimination of Lineq::fme (linsys.cpp:656-774): variable u out of the tmp.r rows that w_load put into tmp (LDS), the
+// result built and reduced in res_lds where its nfree + P x N rows fit cap_lds, else directly in `go` (device memory with
+// room for cap rows; flat pointers). It is k_fme_batch's body, statement for statement, as k_fme_chain_batch runs it once
+// per entry of its elimination list. k_fme_batch keeps its own text: calling this function from it moved its SGPR spills
+// from 75 to 77 (profiles/lineq_project_isa.txt), so a change to either copy has to be made in both -- the tests hold
+// the two against each other bit for bit (tests/test_gpu_lineq_project.py). tmp is normalised in place; res.a / res.r
+// say where the result is and how many rows it has. capx >= the rows of either matrix (the cell loops' divisor).
+struct FmeStep { bool ok; bool in_lds; int over; };        // over: -1, or the rows the result needs where cap holds fewer
+__device__ __forceinline__ FmeStep w_fme_step(WMat & tmp, WMat & res, R32 * const res_lds, R32 * const go, const int cols,
+                                              const int rhs, const int u, const int darkshadow, const int cap,
+                                              const int cap_lds, const int capx, WScratch & s)
+{
+    LQ_T0
+    const int rows = tmp.r;
+    res.r = 0; res.cn = tmp.cn;
+    // classify rows: 0 = no u (copy), 1 = positive, 2 = negative; 3 = inconsistent constant row
+    int * kind = s.map;
+    int * bad_at = &s.flags[1];
+    if (lane_id() == 0) *bad_at = INT_MAX;
+    wave_sync();
+    for (int i = lane_id(); i < rows; i += wave_lanes()) {
+        bool have = false;
+        for (int j = 0; j < rhs && !have; j++) have = ne(tmp.a[i * cols + j], R32(0, 1));
+        if (!have && w_cmp_value(tmp, rhs, i, R32(0, 1)) == CST_LT) atomicMin(bad_at, i);
+        const R32 c = tmp.a[i * cols + u];
+        kind[i] = ne(c, R32(0, 1)) ? (gt(c, R32(0, 1)) ? 1 : 2) : 0;
+    }
+    wave_sync();
+    const int stop = *bad_at == INT_MAX ? rows : *bad_at;      // rows before the first bad one are processed
+    LQ_T(1)
+    // the row lists: rows without u go first, in order (linsys.cpp:724-730); positive and negative rows of u
+    int nfree = 0, np = 0, nn = 0;
+    for (int base = 0; base < stop; base += wave_lanes()) {
+        const int i = base + lane_id();
+        const int kd = i < stop ? kind[i] : -1;
+        const unsigned long long bf = grp_ballot(kd == 0), bp = grp_ballot(kd == 1), bn = grp_ballot(kd == 2);
+        if (kd == 0) kind[i] = -(nfree + grp_rank(bf)) - 1;       // destination row, encoded negative
+        else if (kd == 1) s.pos[np + grp_rank(bp)] = (short)i;
+        else if (kd == 2) s.negs[nn + grp_rank(bn)] = (short)i;
+        nfree += __popcll(bf); np += __popcll(bp); nn += __popcll(bn);
+    }
+    wave_sync();
+    // where this system's result lives
+    const int need = nfree + (np + nn == 1 ? 1 : np * nn);
+    const bool in_lds = need <= cap_lds;
+    res.a = in_lds ? res_lds : go;
+    // normalise the rows that contain u (linsys.cpp:711-723): the rows are independent, so the factors are
+    // found one lane per row (kept in the still empty result matrix) and applied one lane per cell
+    R32 * fac = cap_lds ? res_lds : go;                       // (the host keeps cap_lds * cols >= cap_in when cap_lds > 0)
+    for (int i = lane_id(); i < stop; i += wave_lanes()) {
+        int mode = SCALE_KEEP;
+        if (kind[i] > 0) {
+            const R32 c = tmp.a[i * cols + u];
+            R32 f(1, 1);
+            if (kind[i] == 1) { if (ne(c, R32(1, 1))) f = q_div(tmp.cn, R32(1, 1), c); }
+            else if (ne(c, R32(-1, 1))) f = q_div(tmp.cn, R32(1, 1), neg(c));
+            mode = scale_mode(f);
+            fac[i] = f;
+        }
+        s.drop[i] = (unsigned char)mode;
+    }
+    wave_sync();
+    const FastDiv by_cols(cols, capx * cols + wave_lanes());
+    for (int t = lane_id(); t < stop * cols; t += wave_lanes()) {
+        const int i = by_cols.quot(t), mode = s.drop[i];
+        if (mode != SCALE_KEEP) tmp.a[t] = q_scaled(tmp.cn, tmp.a[t], fac[i], mode);
+    }
+    wave_sync();
+    if (darkshadow) {
+        for (int i = lane_id(); i < stop; i += wave_lanes())
+            if (kind[i] == 2) tmp.a[i * cols + rhs] = q_sub(tmp.cn, tmp.a[i * cols + rhs], R32(1, 1));
+        wave_sync();
+    }
+    LQ_T(2)
+    // rows without u are copied first
+    wave_sync();
+    for (int t = lane_id(); t < stop * cols; t += wave_lanes()) {
+        const int i = by_cols.quot(t), j = t - i * cols;
+        if (kind[i] < 0) res.a[(-kind[i] - 1) * cols + j] = tmp.a[t];
+    }
+    res.r = nfree;
+    LQ_T(3)
+    bool ok = true;
+    int status_rows = -1;
+    if (stop < rows) {                                              // inconsistent constant row
+        ok = false;
+    } else {
+        int extra = 0;
+        if (np + nn == 1) extra = 1;
+        else if (np + nn > 1) extra = np * nn;
+        if (res.r + extra > cap) { status_rows = res.r + extra; ok = false; }
+        else if (np + nn == 1) {
+            const int pi = np == 1 ? s.pos[0] : s.negs[0];
+            for (int j = lane_id(); j < cols; j += wave_lanes()) res.a[res.r * cols + j] = tmp.a[pi * cols + j];
+            res.r += 1;
+        } else if (np + nn > 1) {                                   // every (pos, neg) pair summed
+            const int base = res.r * cols, total = np * nn * cols;
+            const FastDiv by_nn(nn, np * nn);
+            for (int t = lane_id(); t < total; t += wave_lanes()) {
+                const int pair = by_cols.quot(t), j = t - pair * cols;
+                const int pq = by_nn.quot(pair);
+                const int pi = s.pos[pq], ni = s.negs[pair - pq * nn];
+                res.a[base + t] = q_add(tmp.cn, tmp.a[pi * cols + j], tmp.a[ni * cols + j]);
+            }
+            res.r += np * nn;
+        }
+        wave_sync();
+        LQ_T(4)
+        if (status_rows < 0 && res.r > 0) ok = w_reduce(res, rhs, true, s);
+        LQ_T(5)
+    }
+    FmeStep st; st.ok = ok; st.in_lds = in_lds; st.over = status_rows;
+    return st;
+}
+
 // Lineq::fme (linsys.cpp:656-774) for one system per wave. out has cap rows; cap_lds of them have room in LDS
 // (see the layout note in the body).
 // Inputs are [nb][cap_in][cols] with in_rows[b] live rows each (NULL: all cap_in rows), which
@@ -521,6 +636,56 @@ __global__ __launch_bounds__(64) void k_fme_batch(int nb, const R32 * mats, int 
         }
         wave_sync();
         LQ_T(6)
+        LQ_FLUSH
+    }
+}
+
+// A projection: the variables el.u[0 .. el.n) eliminated one after the other (DepPoly::eliminateAuxVar, eng/poly.cpp:643-651;
+// the scanning bounds, eng/poly.cpp:4807-4813), each step's result the next step's input, ALL steps of a system before the
+// wave takes its next system. The list travels as a kernel argument (no upload of its own); an index may repeat.
+enum { FME_CHAIN_MAX = 64 };
+struct ElimList { int n; int u[FME_CHAIN_MAX]; };
+// mats [nb][rows][cols]; LDS of a seat (the wave of one workgroup slot): [result area (cap_lds x cols)] [step input (cap x cols)]
+// [scratch], fme_lds(cap, cap, cols) as for calcBound's chains. Intermediates belong to the SEAT, not to the system: a step
+// whose nfree + P x N rows fit cap_lds is built and reduced in LDS and loaded into the input area from there; a larger one is
+// built and reduced in one of the seat's two cap-row slots of `seats` [seats][2][cap][cols] (the sides alternate) and loaded
+// from there. The last step's rows go to the system's own slot of outs [nb][cap_out][cols]; nothing is stored behind them.
+//   out_ok[b] 1, out_steps[b] el.n: out_rows[b] rows (0 after an empty intermediate: fme of an empty system is true and empty)
+//   out_ok[b] 0, out_steps[b] k:    step k found the system inconsistent; no rows
+//   out_ok[b] -need:                step out_steps[b] needs `need` > cap rows, or (out_steps[b] == el.n) the final result has
+//                                   `need` > cap_out rows; no rows
+__global__ __launch_bounds__(64) void k_fme_chain_batch(int nb, const R32 * mats, int rows, int cols, int rhs, ElimList el,
+                                                        int darkshadow, R32 * seats, int cap, R32 * outs, int cap_out,
+                                                        int * out_rows, int * out_ok, int * out_steps, int cap_lds, int sys_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
+    R32 * const res_lds = (R32 *)lds;
+    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
+    R32 * const seat = seats + (size_t)sys_first() * 2 * cap * cols;
+    LQ_CLEAR
+    for (int b = sys_first(); b < nb; b += sys_stride()) {
+        w_load(tmp, mats + (size_t)b * rows * cols, rows, cols);
+        int okv = 1, steps = el.n, kept = 0, side = 0;
+        for (int k = 0; k < el.n; k++) {
+            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * cap * cols, cols, rhs, el.u[k], darkshadow, cap,
+                                          cap_lds, cap, s);
+            wave_sync();
+            if (st.over >= 0) { okv = -st.over; steps = k; break; }
+            if (!st.ok) { okv = 0; steps = k; break; }
+            if (res.r == 0) break;                                      // empty from here on: every later step copies nothing
+            if (k + 1 == el.n) {
+                if (res.r > cap_out) okv = -res.r;
+                else { w_store(res, outs + (size_t)b * cap_out * cols); kept = res.r; }
+                break;
+            }
+            w_load(tmp, res.a, res.r, cols);                            // from LDS, or from the side just written
+            if (!st.in_lds) side ^= 1;
+        }
+        if (lane_id() == 0) { out_rows[b] = kept; out_ok[b] = okv; out_steps[b] = steps; }
+        wave_sync();
         LQ_FLUSH
     }
 }

@@ -124,6 +124,42 @@ class Lineq:
             C.memmove(packed.ctypes.data, view.value, packed.nbytes)
         return ok, off, packed
 
+    def project_packed(self, mats, rhs_idx, elim, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_project_batch_packed_rat32: the variables of `elim` eliminated one after the other (each Lineq::fme's result
+        the next one's input) in one launch. Returns (ok[nb], steps[nb], [rows of system b]): ok 1 with steps == len(elim), 0
+        with the step that found the system inconsistent, or -need with the step that needs `need` rows (steps == len(elim):
+        the final result against cap_out_rows); a system with ok <= 0 has no rows. copy=False: the rows are views of the
+        handle's pinned buffer, valid until the next packed call on this handle."""
+        a = _stack(mats)
+        nb, rows, cols = a.shape[:3]
+        el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
+        off = np.zeros(nb + 1, dtype=np.int64); ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, steps, []
+        view = C.c_void_p()
+        self.ctx.check(lib().xpg_lineq_project_batch_packed_rat32(
+            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), vp(el), C.c_int(el.size),
+            C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view),
+            vp(off), vp(ok), vp(steps)), "xpg_lineq_project_batch_packed_rat32")
+        total = int(off[nb])
+        if not copy and total:
+            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
+        else:
+            packed = np.empty((total, cols, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        return ok, steps, [packed[off[b]: off[b + 1]] for b in range(nb)]
+
+    @staticmethod
+    def project_last_route():
+        """xpg_lineq_project_last_route of the calling thread's last projection call, as a dict."""
+        out = np.zeros(6, dtype=np.int64)
+        rc = lib().xpg_lineq_project_last_route(vp(out), C.c_int(6))
+        if rc != 0:
+            raise ValueError("xpg_lineq_project_last_route: %d" % rc)
+        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes"), (int(x) for x in out)))
+
     def reduce_ragged(self, mats_list, rhs_idx=None, is_intersect=True):
         """Lineq::reduce on systems of different shapes in one call: (ok[nb], [system b's surviving rows])."""
         from .six import _ragged_pack
@@ -286,6 +322,18 @@ def fme_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, u, darkshadow, outs_ptr, cap
                                                   C.c_int(rhs_idx), C.c_int(u), C.c_int(int(darkshadow)), C.c_void_p(outs_ptr),
                                                   C.c_int(cap_rows), C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr)),
               "xpg_lineq_fme_batch_rat32_dev")
+
+
+def project_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, elim, darkshadow, cap_rows, cap_out_rows, outs_ptr, out_rows_ptr,
+                out_ok_ptr, out_steps_ptr):
+    """xpg_lineq_project_batch_rat32_dev: a list of eliminations on device arrays in one launch, enqueue only. `elim` is a
+    host list; outs is [nb][cap_out_rows][cols] (cap_out_rows <= 0: cap_rows)."""
+    el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
+    ctx.check(lib().xpg_lineq_project_batch_rat32_dev(ctx._h, C.c_int(nb), C.c_void_p(mats_ptr), C.c_int(rows), C.c_int(cols),
+                                                      C.c_int(rhs_idx), vp(el), C.c_int(el.size), C.c_int(int(darkshadow)),
+                                                      C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
+                                                      C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr)),
+              "xpg_lineq_project_batch_rat32_dev")
 
 
 def rank_dev(ctx, nb, mats_ptr, rows, cols, out_rank_ptr):
