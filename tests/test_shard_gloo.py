@@ -160,11 +160,13 @@ def test_bench_without_gpus_fails_loudly():
     assert "XPG_ERR_NO_DEVICE" in r.stderr or "No HIP GPUs" in r.stderr or "no GPU" in r.stderr.lower(), r.stderr[-3000:]
 
 
-def test_numa_placement_reads_sysfs_only(tmp_path):
+def test_numa_placement_reads_sysfs_only(tmp_path, monkeypatch):
     """A rank binds itself to the NUMA node of its GPU before its first GPU call (bench.py, xpoly_amd/shard.py): the node
     comes from sysfs -- AMD display / accelerator functions in bus order -- and an unknown topology changes nothing."""
     import os
     from xpoly_amd.shard import _parse_cpulist, gpu_numa_nodes, pin_to_gpu_numa
+    for name in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):     # the made-up topology below is numbered from 0: no remapping
+        monkeypatch.delenv(name, raising=False)
     assert _parse_cpulist("0-3,8,10-11\n") == [0, 1, 2, 3, 8, 10, 11]
     devs = tmp_path / "bus" / "pci" / "devices"
     for bdf, vendor, cls, node in (("0000:05:00.0", "0x1002", "0x120000", "0"), ("0000:25:00.0", "0x1002", "0x120000", "1"),

@@ -1,5 +1,5 @@
 # builds the stamped diagnostic library and prints the phase times of pick / prep
 cd $GRAFT_REPO_ROOT
 mkdir -p tools/_build gpurun_out
-hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -DXPG_STAMPS -o tools/_build/libxpoly_stamps.so xpoly_amd/csrc/xpoly_amd.hip
+python -c "from xpoly_amd import build; build.build(extra=['-DXPG_STAMPS'], out='tools/_build/libxpoly_stamps.so', obj='tools/_build/obj_stamps')"
 XPG_SO_PATH=$PWD/tools/_build/libxpoly_stamps.so PYTHONPATH=$PWD python tools/lab/probe_stamps.py 2>&1 | tee gpurun_out/stamps.log

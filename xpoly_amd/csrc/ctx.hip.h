@@ -13,6 +13,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/xpoly_amd.h"
+#include "scalar.hip.h"
+
+static_assert(sizeof(xpg::F64) == 8 && sizeof(xpg::R32) == 8, "both scalars are 8 bytes");
+static_assert(sizeof(xpg_rat32) == sizeof(xpg::R32), "ABI layout of a rational");
 
 namespace xpg {
 struct LoopState;

@@ -1,7 +1,7 @@
 // The front ends on top of the MIP walk: Lineq::has_solution (src/com/linsys.cpp:830-906) and DepPoly::is_empty
 // (src/eng/poly.cpp:530-573), with the two small kernels the latter runs between Lineq::reduce and the walks. A header of its
-// own because the walk (mip_kernels.hip.h) and its host half (mip_host.hip.h) are included by more than one part of the
-// library (xpoly_amd.hip), and these -- non-template kernels and the instantiations has_solution pulls in -- belong to one.
+// own because the walk (mip_kernels.hip.h) and its host half (mip_host.hip.h) are included by more than one source of the
+// library (api_mip.hip, api_mip_hbm.hip, api_has_solution.hip), and these -- non-template kernels and the instantiations has_solution pulls in -- belong to one.
 #pragma once
 #include "mip_host.hip.h"
 

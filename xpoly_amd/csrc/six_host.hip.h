@@ -177,6 +177,28 @@ template <class S> bool vc_sign_pattern(const S * vc, int vc_rows, int cols, std
     return true;
 }
 
+// What the host-only test views (xpg_test_*_plan) know of a vc: whether it is a sign pattern; nfree as the plans take it (the
+// free variables of a pattern, 0 for a general vc, -1 for vc == NULL: the _dev forms' view); and the columns without a nonzero
+// (lpsol.h:1322), which a general vc has too.
+namespace {
+struct VcView { bool pattern; int nfree, zero_cols; };
+template <class S> VcView vc_view(const void * vc, int vc_rows, int cols)
+{
+    VcView v = {true, -1, 0};
+    if (!vc) return v;
+    const S * c = (const S *)vc;
+    std::vector<int> fv;
+    v.pattern = vc_sign_pattern(c, vc_rows, cols, fv);
+    v.nfree = v.pattern ? (int)fv.size() : 0;
+    for (int j = 0; j < cols - 1; j++) {
+        bool nz = false;
+        for (int i = 0; i < vc_rows && !nz; i++) nz = !eq(c[(size_t)i * cols + j], zero<S>());
+        v.zero_cols += nz ? 0 : 1;
+    }
+    return v;
+}
+}
+
 // SIX::reviseTargetFunc on the all-ones objective (lpsol.h:2053-2074, linsys.cpp:851-862): Lineq::has_solution's objective,
 // for its single-problem front end (mip_front.hip.h) and its batched one (has_solution_batch.hip.h).
 inline std::vector<R32> feasibility_objective(const R32 * leq, int leq_rows, const R32 * eqs, int eq_rows, int cols, int rhs)
