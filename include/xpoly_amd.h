@@ -782,7 +782,7 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
  * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
  * scratch slots of xpg_six_batch_vc_*, xpg_six_batch_hbm_*, xpg_six_batch_vc_hbm_* and xpg_mip_batch_vc_hbm_* (which
- * shares xpg_six_batch_hbm_*'s). */
+ * shares xpg_six_batch_hbm_*'s), of xpg_lineq_project_batch_* and of xpg_lineq_bounds_batch_*. */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the
@@ -848,6 +848,44 @@ int xpg_test_lineq_project_plan(int nb, int rows, int cols, int cap_rows, int ca
  * anything else -- 0, XPG_ERR_SHAPE (n_elim <= 0, no list, an index outside [0, rhs_idx), rhs_idx outside [1, cols)) or
  * XPG_ERR_UNSUPPORTED (more than 64 entries).  The function the calls themselves ask. */
 int xpg_test_lineq_project_check(int cols, int rhs_idx, const int32_t * elim, int n_elim);
+/* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems of one shape in ONE launch: the bounds of every variable j
+ * alone (the other rhs_idx - 1 variables eliminated, inner to outer).  The rhs_idx chains of a system share their beginnings
+ * -- each starts by eliminating rhs_idx-1 .. j+1 -- so a wavefront walks those prefixes once and runs only the tail j-1 .. 0
+ * per variable: (rhs_idx - 1)(rhs_idx + 2) / 2 elimination steps per system instead of rhs_idx (rhs_idx - 1), intermediates
+ * in LDS or in three device slots per resident wavefront.  The results are those of the chains run one by one, bit for bit.
+ *   cap_rows      rows an intermediate or a result may have before it is reduced; <= 0: 4 * rows + 16
+ *   cap_out_rows  rows of a result's slot; <= 0 (or above cap_rows): cap_rows
+ *   row_offsets   [nb * rhs_idx + 1], entry b * rhs_idx + j the first row of variable j's bounds of system b (the layout of
+ *                 xpg_lineq_calc_bound_batch_packed_rat32)
+ *   out_ok[b]     1: every chain ran, out_chain[b] = -1, out_steps[b] = 0 (a chain with an empty intermediate ends empty).
+ *                 Else the verdict of the LOWEST failing chain out_chain[b] -- the one the reference, which runs variable 0
+ *                 first and returns at once, meets -- at step out_steps[b] of that chain's list:  0: the step found the system
+ *                 inconsistent;  -need: the step needs `need` > cap_rows rows, or (out_steps[b] == rhs_idx - 1) the chain's
+ *                 result has `need` > cap_out_rows rows.  A system with out_ok[b] <= 0 contributes no rows; the others are
+ *                 packed all the same (unlike xpg_lineq_calc_bound_batch_packed_rat32, which packs nothing).
+ * outs, outs_cap_rows and out_view as xpg_lineq_project_batch_packed_rat32 (neither outs nor out_view: a sizing call).
+ * XPG_ERR_SHAPE: rhs_idx outside [1, cols), rows <= 0, cols <= 1, a missing output; XPG_ERR_UNSUPPORTED: the LDS layout of
+ * cap_rows exceeds 160 KB, or cap_rows > 32767.  nb == 0: returns 0, row_offsets[0] = 0. */
+int xpg_lineq_bounds_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx, int cap_rows,
+                                        int cap_out_rows, xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                        long long * row_offsets, int32_t * out_ok, int32_t * out_chain, int32_t * out_steps);
+/* The same on DEVICE arrays, enqueue only: d_outs [nb][rhs_idx][cap_out_rows][cols] receives each result's live rows and is not
+ * cleared behind them, d_out_rows [nb][rhs_idx] their counts (all 0 for a system with d_out_ok <= 0), d_out_ok / d_out_chain
+ * / d_out_steps [nb].  The intermediates' slots belong to the handle (grow-only; xpg_trim returns them).  The row stride of
+ * d_outs is the caller's: cap_rows < rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE; cap_out_rows <= 0 alone stands for
+ * cap_rows. */
+int xpg_lineq_bounds_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx, int cap_rows,
+                                     int cap_out_rows, xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok,
+                                     int32_t * d_out_chain, int32_t * d_out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_lineq_bounds_batch_* call did.  out[0] launches (1; 0
+ * where nothing was launched), [1] grid, [2] systems per workgroup, [3] LDS bytes per system, [4] rows of the LDS result
+ * area, [5] bytes of slots the launch was given: grid x [2] x 3 x cap_rows x cols x 8, whatever nb is, [6] elimination steps
+ * per system, (rhs_idx - 1)(rhs_idx + 2) / 2.  Fills min(n, 7) entries. */
+int xpg_lineq_bounds_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same seven figures from the shape alone -- the function the launch itself
+ * asks -- then [7] the cap_rows and [8] the cap_out_rows it settles on.  Fills min(n, 9) entries; XPG_ERR_SHAPE /
+ * XPG_ERR_UNSUPPORTED as the call. */
+int xpg_test_lineq_bounds_plan(int nb, int rows, int cols, int rhs_idx, int cap_rows, int cap_out_rows, long long * out, int n);
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank);
 int xpg_rat_rank_batch(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols,
                        int32_t * out_rank);

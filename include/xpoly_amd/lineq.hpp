@@ -33,7 +33,7 @@ template <class RMatT> class Lineq {
     static void put(RMatT & m, const std::vector<xpg_rat32> & a, int rows, int cols)
     {
         m.reinit(rows, cols);
-        if (rows * cols) std::memcpy((void *)m.get_matrix(), (const void *)a.data(), sizeof(xpg_rat32) * (size_t)rows * cols);
+        if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a.data(), sizeof(xpg_rat32) * (size_t)rows * cols);
     }
 public:
     explicit Lineq(RMatT * m, int rhs_idx = -1, xpg_ctx * c = 0) : m_ctx(c), m_coeff(m), m_rhs_idx(rhs_idx)
@@ -178,7 +178,7 @@ public:
         return r == 1;
     }
     // Lineq::calcBound, linsys.cpp:1047-1078: the bounds of variable j alone (every other variable eliminated, inner to
-    // outer) for every j, all chains on the device in one call.
+    // outer) for every j, all chains on the device in one call and one launch (xpg_lineq_bounds_batch_packed_rat32).
     //   bool calcBound(List<RMat*> & limits)   -- the reference's own signature (linsys.h:151): `limits` holds m_rhs_idx
     //                                             matrices the caller owns, *limits.get_head_nth(j) receives variable j's
     //                                             (linsys.cpp:1072-1074), so the call site at linsys.cpp:312 compiles unchanged
@@ -192,9 +192,9 @@ private:
         for (int attempt = 0; attempt < 2; attempt++) {
             std::vector<long long> off((size_t)nv + 1, 0);
             const xpg_rat32 * view = 0;
-            int32_t ok = 0;
-            if (xpg_lineq_calc_bound_batch_packed_rat32(ctx(), 1, (const xpg_rat32 *)m_coeff->get_matrix(), rows, cols, nv, cap, (xpg_rat32 *)0, 0,
-                                                        &view, off.data(), &ok) != 0) return false;
+            int32_t ok = 0, chain = -1, step = 0;
+            if (xpg_lineq_bounds_batch_packed_rat32(ctx(), 1, (const xpg_rat32 *)m_coeff->get_matrix(), rows, cols, nv, cap, 0, (xpg_rat32 *)0, 0,
+                                                    &view, off.data(), &ok, &chain, &step) != 0) return false;
             if (ok < 0) { cap = -ok; continue; }
             if (ok == 0) return false;                       // "system inconsistency!" (linsys.cpp:1065-1068)
             for (int j = 0; j < nv; j++) {
@@ -411,7 +411,9 @@ inline int project_all(const std::vector<RMatT *> & systems, const std::vector<i
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for many systems: limits[k][j] receives the bounds of variable j of *systems[k]
 // alone (the constant in column rhs_idx[k]); ok[k] is calcBound's bool. Systems of one shape go up together -- one call per
-// shape class (SCoPs have a handful), every elimination chain of a class on the device at once. Returns 0 or XPG_ERR_*.
+// shape class (SCoPs have a handful), xpg_lineq_bounds_batch_packed_rat32: every elimination chain of a class in one launch.
+// A class one of whose systems needs more rows than the capacity tried is called again with the largest need the library
+// reports, at most three times; still short: XPG_ERR_UNSUPPORTED, never a silent ok = 0. Returns 0 or XPG_ERR_*.
 template <class RMatT>
 inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vector<int32_t> & rhs_idx,
                           std::vector<std::vector<RMatT> > & limits, std::vector<int32_t> & ok, xpg_ctx * c = 0)
@@ -436,11 +438,13 @@ inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vecto
         for (int k = 0; k < nc; k++)
             std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
         int cap = 4 * rows + 16;
-        for (int attempt = 0; attempt < 3; attempt++) {
+        bool answered = false;
+        for (int attempt = 0; attempt < 3 && !answered; attempt++) {
             std::vector<long long> off((size_t)nc * nv + 1, 0);
-            std::vector<int32_t> kok((size_t)nc, 0);
+            std::vector<int32_t> kok((size_t)nc, 0), kchain((size_t)nc, 0), ksteps((size_t)nc, 0);
             const xpg_rat32 * view = 0;
-            const int rc = xpg_lineq_calc_bound_batch_packed_rat32(h, nc, flat.data(), rows, cols, nv, cap, (xpg_rat32 *)0, 0, &view, off.data(), kok.data());
+            const int rc = xpg_lineq_bounds_batch_packed_rat32(h, nc, flat.data(), rows, cols, nv, cap, 0, (xpg_rat32 *)0, 0, &view, off.data(),
+                                                               kok.data(), kchain.data(), ksteps.data());
             if (rc != 0) return rc;
             int need = 0;
             for (int k = 0; k < nc; k++) if (kok[(size_t)k] < 0 && -kok[(size_t)k] > need) need = -kok[(size_t)k];
@@ -456,8 +460,9 @@ inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vecto
                     if (hi > lo) std::memcpy((void *)m.get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
                 }
             }
-            break;
+            answered = true;
         }
+        if (!answered) return XPG_ERR_UNSUPPORTED;
     }
     return 0;
 }

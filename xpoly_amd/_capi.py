@@ -45,6 +45,8 @@ SYMBOLS = [
     "xpg_test_has_solution_int_plan",
     "xpg_lineq_project_batch_packed_rat32", "xpg_lineq_project_batch_rat32_dev", "xpg_lineq_project_last_route",
     "xpg_test_lineq_project_plan", "xpg_test_lineq_project_check",
+    "xpg_lineq_bounds_batch_packed_rat32", "xpg_lineq_bounds_batch_rat32_dev", "xpg_lineq_bounds_last_route",
+    "xpg_test_lineq_bounds_plan",
 ]
 
 _lib = None

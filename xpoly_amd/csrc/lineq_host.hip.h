@@ -188,6 +188,8 @@ inline int lineq_fme_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows, in
 // one synchronisation, no scan / pack launches (a handful of systems: the drop-in adapter eliminates one per call). Else
 // k_rows_scan, one synchronisation for the offsets, k_pack_rows, and only live rows cross the link. short_msg != NULL: a
 // negative count (a result that needs -count rows) ends the call with XPG_ERR_UNSUPPORTED, the count in row_offsets[0].
+// out_ok == NULL: the results are not one per verdict (calcBound's nb * rhs results) -- dk is not read, the caller brings its
+// verdicts down itself, enqueued before this call so that its synchronisation covers them.
 template <class Lap>
 inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & dout, DevBuf & dr, DevBuf & dk, DevBuf * ds, DevBuf & doff,
                             size_t meta_al, size_t in_stage, bool small_out, bool internal, const char * short_msg, R32 * out,
@@ -197,7 +199,7 @@ inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & d
     const size_t bo = (size_t)nb * cap * cols * 8;
     long long * h_off = (long long *)hp; int32_t * h_ok = (int32_t *)(hp + (size_t)(nb + 1) * 8); int32_t * h_rows = h_ok + nb;
     int32_t * h_steps = h_rows + nb;
-    XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_ok) XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipMemcpyAsync(h_rows, dr.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (ds) XPG_TRY(hipMemcpyAsync(h_steps, ds->p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (small_out) {
@@ -210,7 +212,7 @@ inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & d
             row_offsets[b] = tot; tot += h_rows[b];
         }
         row_offsets[nb] = tot;
-        memcpy(out_ok, h_ok, (size_t)nb * 4);
+        if (out_ok) memcpy(out_ok, h_ok, (size_t)nb * 4);
         if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
         if (out && out_cap_rows < tot) return XPG_ERR_SHAPE;
         const size_t rowb = (size_t)cols * 8;
@@ -229,7 +231,7 @@ inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & d
         for (int b = 0; b < nb; b++)
             if (h_rows[b] < 0) { ctx->err = short_msg; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
     memcpy(row_offsets, h_off, (size_t)(nb + 1) * 8);
-    memcpy(out_ok, h_ok, (size_t)nb * 4);
+    if (out_ok) memcpy(out_ok, h_ok, (size_t)nb * 4);
     if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
     const long long total = row_offsets[nb];
     if (out && out_cap_rows < total) return XPG_ERR_SHAPE;
@@ -328,6 +330,30 @@ inline int project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_ro
 // kernel (1), its grid, groups per workgroup, LDS bytes per system, cap_lds, bytes of seat slots the launch was given.
 struct ProjectRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes; };
 inline ProjectRoute & project_route() { static thread_local ProjectRoute r = {0, 0, 0, 0, 0, 0}; return r; }
+// THE plan of a fused calcBound call (k_calc_bound_batch; the launch and xpg_test_lineq_bounds_plan both ask it). As
+// project_plan, but cap_rows <= 0 is the packed calcBound's default 4 * rows + 16, a seat has THREE cap-row slots (two sides
+// and the held prefix), and the plan knows the steps a system takes: rhs - 1 prefix steps and rhs (rhs - 1) / 2 tail steps.
+struct BoundsPlan { int cap, cap_out, cap_lds; LineqGeom q; long long seats, steps; size_t seat_bytes; };
+inline int bounds_plan(int nb, int rows, int cols, int rhs, int cap_rows, int cap_out_rows, BoundsPlan & p)
+{
+    if (nb <= 0 || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols) return XPG_ERR_SHAPE;
+    p.cap = cap_rows <= 0 ? 4 * rows + 16 : cap_rows;
+    if (p.cap < rows) p.cap = rows;
+    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
+    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
+    const FmeLds fl = fme_lds(p.cap, p.cap, cols);
+    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    p.cap_lds = fl.cap_lds;
+    p.q = lineq_geom(nb, 64, fl.lds);
+    p.seats = (long long)p.q.grid * p.q.G;
+    p.seat_bytes = (size_t)p.seats * 3 * (size_t)p.cap * cols * 8;
+    p.steps = (long long)(rhs - 1) * (rhs + 2) / 2;
+    return 0;
+}
+// What the calling thread's last xpg_lineq_bounds_batch_* call did (xpg_lineq_bounds_last_route): ProjectRoute's figures and
+// the elimination steps per system.
+struct BoundsRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, steps; };
+inline BoundsRoute & bounds_route() { static thread_local BoundsRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
 
 inline int project_check(int cols, int rhs, const int32_t * elim, int n_elim)
 {
@@ -506,6 +532,79 @@ inline int lineq_calc_bound_batch(xpg_ctx * ctx, int nb, const R32 * mats, int r
     XPG_TRY(hipMemcpyAsync(out_ok, chain.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+// ---- calcBound fused: every chain of every system in ONE launch (k_calc_bound_batch) -----------------------------------------
+// Device arrays, enqueue only: d_outs [nb][rhs][cap_out_rows][cols] receives the live rows of variable j's bounds in slot
+// (b, j), d_rows [nb][rhs] their counts, d_ok / d_chain / d_steps [nb] as the kernel writes them. As lineq_project_batch_dev:
+// the seats' slots are the handle's (grow-only, a slot of their own), the row stride of d_outs is the caller's -- cap_rows <
+// rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE, only cap_out_rows <= 0 stands for cap_rows.
+inline int lineq_bounds_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, int cap_rows, int cap_out_rows,
+                                  R32 * d_outs, int32_t * d_rows, int32_t * d_ok, int32_t * d_chain, int32_t * d_steps)
+{
+    bounds_route() = BoundsRoute{0, 0, 0, 0, 0, 0, 0};
+    if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols || !d_rows || !d_ok || !d_chain || !d_steps)
+        return XPG_ERR_SHAPE;
+    if (cap_rows < rows || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    BoundsPlan p;
+    if (const int rc = bounds_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, p)) return rc;
+    Scratch & slots = ctx->scratch[SCRATCH_LINEQ_BOUNDS];
+    if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_bounds seats)")) return rc;
+    XPG_TRY(lds_limit((const void *)k_calc_bound_batch, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_calc_bound_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, (R32 *)slots.buf,
+                       p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_chain, (int *)d_steps, p.cap_lds, p.q.sys_lds);
+    XPG_TRY(hipGetLastError());
+    bounds_route() = BoundsRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, p.steps};
+    return 0;
+}
+// Host arrays with a PACKED result in the layout of the packed calcBound: row_offsets [nb * rhs + 1], entry b * rhs + j where
+// the bounds of variable j of system b start. One upload, the one launch, packed_rows_down over the nb * rhs results; the
+// verdicts (ok, chain, steps: [nb] each) come down through hred beside it, under the same synchronisation. A system with
+// out_ok <= 0 contributes no rows, the others are packed all the same; out / view / sizing call as lineq_project_batch_packed.
+inline int lineq_bounds_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, int cap_rows, int cap_out_rows,
+                                     R32 * out, long long out_cap_rows, const R32 ** view, long long * row_offsets, int32_t * out_ok,
+                                     int32_t * out_chain, int32_t * out_steps)
+{
+    if (view) *view = 0;
+    bounds_route() = BoundsRoute{0, 0, 0, 0, 0, 0, 0};
+    if (!ctx || nb < 0 || !mats || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols || !row_offsets || !out_ok || !out_chain || !out_steps ||
+        (out && out_cap_rows < 0))
+        return XPG_ERR_SHAPE;
+    if (nb == 0) { row_offsets[0] = 0; return 0; }
+    BoundsPlan p;
+    if (const int rc = bounds_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, p)) return rc;
+    if ((long long)nb * rhs > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    const int nres = nb * rhs;
+    const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nres * p.cap_out * cols * 8, bv = (size_t)nb * 4;
+    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 12;  // offsets, then (unused) ok, rows and (unused) steps
+    const size_t meta_al = (meta + 255) & ~(size_t)255;
+    DevBuf di, dout, dr, dv, doff;                                   // dv: ok, chain and steps, [3][nb]
+    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nres * 4)); XPG_TRY(dv.alloc(ctx, 3 * bv));
+    XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
+    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
+    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
+    if (rc) return rc;
+    if ((rc = hpack_reserve(ctx, 3 * bv, true))) return rc;
+    char * hp = hpack_buf(ctx, false);
+    int32_t * hv = (int32_t *)hpack_buf(ctx, true);
+    if (small_in) {
+        memcpy(hp + meta_al, mats, bi);
+        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int32_t * const d_ok = (int32_t *)dv.p;
+    rc = lineq_bounds_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, p.cap, p.cap_out, (R32 *)dout.p, (int32_t *)dr.p, d_ok, d_ok + nb,
+                                d_ok + 2 * (size_t)nb);
+    if (rc) return rc;
+    XPG_TRY(hipMemcpyAsync(hv, dv.p, 3 * bv, hipMemcpyDeviceToHost, ctx->stream));
+    rc = packed_rows_down(ctx, nres, cols, p.cap_out, dout, dr, dv, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
+                          out, out_cap_rows, view, row_offsets, (int32_t *)0, (int32_t *)0, [](const char *) {});
+    if (rc == 0 || rc == XPG_ERR_SHAPE) {                            // (it has synchronised: a buffer too small still gets its verdicts)
+        memcpy(out_ok, hv, bv); memcpy(out_chain, hv + nb, bv); memcpy(out_steps, hv + 2 * (size_t)nb, bv);
+    }
+    return rc;
 }
 
 // Matrix<Rational>::rank on device arrays, enqueue only: d_rank [nb].

@@ -388,7 +388,7 @@ __global__ __launch_bounds__(64) void k_reduce_batch(int nb, R32 * mats, int row
 // One elimination of Lineq::fme (linsys.cpp:656-774): variable u out of the tmp.r rows that w_load put into tmp (LDS), the
 // result built and reduced in res_lds where its nfree + P x N rows fit cap_lds, else directly in `go` (device memory with
 // room for cap rows; flat pointers). It is k_fme_batch's body, statement for statement, as k_fme_chain_batch runs it once
-// per entry of its elimination list. k_fme_batch keeps its own text: calling this function from it moved its SGPR spills
+// per entry of its elimination list and k_calc_bound_batch once per step of its walk. k_fme_batch keeps its own text: calling this function from it moved its SGPR spills
 // from 75 to 77 (profiles/lineq_project_isa.txt), so a change to either copy has to be made in both -- the tests hold
 // the two against each other bit for bit (tests/test_gpu_lineq_project.py). tmp is normalised in place; res.a / res.r
 // say where the result is and how many rows it has. capx >= the rows of either matrix (the cell loops' divisor).
@@ -685,6 +685,91 @@ __global__ __launch_bounds__(64) void k_fme_chain_batch(int nb, const R32 * mats
             if (!st.in_lds) side ^= 1;
         }
         if (lane_id() == 0) { out_rows[b] = kept; out_ok[b] = okv; out_steps[b] = steps; }
+        wave_sync();
+        LQ_FLUSH
+    }
+}
+
+// Lineq::calcBound (linsys.cpp:1047-1078): for every variable j of a system the other rhs - 1 variables eliminated, inner to
+// outer, ALL rhs chains of a system before the wave takes its next system. Chain j is rhs-1 .. j+1, then j-1 .. 0, so every
+// chain starts with a prefix of rhs-1 .. 1: with P_j the system with the variables above j eliminated (P_{rhs-1} the input,
+// P_{j-1} = fme(P_j, j)), chain j is P_j followed by the tail j-1 .. 0. The prefixes are walked once, j = rhs-1 down to 0:
+// (rhs-1) + rhs(rhs-1)/2 steps per system instead of rhs(rhs-1). fme is a pure function of its input matrix and u, so every
+// result has the bits the chain run on its own has. LDS of a seat as in k_fme_chain_batch; `seats` is [seats][3][cap][cols]:
+// two alternating sides for the intermediates that do not fit cap_lds rows, and a HOLD slot for the current prefix P_j (a
+// step normalises its input in place, so P_j is loaded twice: for its tail and for the step that makes P_{j-1}).
+// outs [nb][rhs][cap_out][cols], out_rows [nb][rhs]; nothing is stored behind a result's rows.
+//   out_ok[b] 1, out_chain[b] -1, out_steps[b] 0: every chain ran (a chain with an empty intermediate ends empty and ok)
+//   else the verdict of the LOWEST failing chain, the one the reference meets first (it runs j = 0 first and returns):
+//   out_ok[b] 0 (inconsistent) or -need (step out_steps[b] of chain out_chain[b] needs `need` > cap rows, or, with
+//   out_steps[b] == rhs - 1, that chain's final result has `need` > cap_out rows); all rhs counts of the system are 0.
+// A prefix step is a step of chain 0 (index rhs-1-u) and of every chain below u: its failure ends the walk. A failing tail is
+// recorded and the walk goes on -- a lower chain may fail in another way, and overwrites the record.
+__global__ __launch_bounds__(64) void k_calc_bound_batch(int nb, const R32 * mats, int rows, int cols, int rhs, R32 * seats, int cap,
+                                                         R32 * outs, int cap_out, int * out_rows, int * out_ok, int * out_chain,
+                                                         int * out_steps, int cap_lds, int sys_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
+    R32 * const res_lds = (R32 *)lds;
+    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
+    const int slot = cap * cols;                                        // (cells; the LDS layout holds as many, so they fit an int)
+    R32 * const seat = seats + (size_t)sys_first() * 3 * slot;          // sides 0 and 1, then the hold slot
+    LQ_CLEAR
+    for (int b = sys_first(); b < nb; b += sys_stride()) {
+        bool held = false;                                              // P_j: the input, then the hold slot
+        int pj_rows = rows;
+        int okv = 1, chain = -1, steps = 0, side = 0;
+        bool walk = true;
+        for (int j = rhs - 1; j >= 0 && walk; j--) {
+            w_load(tmp, held ? seat + 2 * slot : mats + (size_t)b * rows * cols, pj_rows, cols);
+            bool fin_res = false;                                       // no step (j == 0, or P_j empty): P_j itself, unreduced
+            int fin_r = pj_rows;
+            int tok = 1, tstep = 0;
+            // t < j: step t of chain j's tail, u = j-1-t (index rhs-2-u of the chain's list); t == j: the tail is stored, then
+            // the prefix step u = j. One call site of the step for both (two: 138 VGPRs against 132, profiles/calc_bound_isa.txt).
+            for (int t = 0; t <= j; t++) {
+                const bool prefix = t == j;
+                if (prefix) {
+                    int kept = 0;
+                    if (tok == 1) {
+                        R32 * const dst = outs + ((size_t)b * rhs + j) * cap_out * cols;
+                        if (fin_r > cap_out) { tok = -fin_r; tstep = rhs - 1; }
+                        else { if (fin_res) w_store(res, dst); else w_store(tmp, dst); kept = fin_r; }
+                    }
+                    if (tok != 1) { okv = tok; chain = j; steps = tstep; }
+                    if (lane_id() == 0) out_rows[(size_t)b * rhs + j] = kept;
+                    wave_sync();
+                    if (j == 0 || pj_rows == 0) break;                  // (an empty prefix stays empty)
+                    // P_j again: the tail's first step normalised it in place
+                    w_load(tmp, held ? seat + 2 * slot : mats + (size_t)b * rows * cols, pj_rows, cols);
+                } else if (tok != 1 || fin_r == 0) continue;            // (empty from here on: every later step copies nothing)
+                const int u = prefix ? j : j - 1 - t;
+                const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (prefix ? 2 : side) * slot, cols, rhs, u, 0, cap, cap_lds, cap, s);
+                wave_sync();
+                if (st.over >= 0 || !st.ok) {
+                    const int v = st.over >= 0 ? -st.over : 0;
+                    if (prefix) { okv = v; chain = 0; steps = rhs - 1 - j; walk = false; }
+                    else { tok = v; tstep = rhs - 2 - u; }
+                } else if (prefix) {
+                    if (st.in_lds) w_store(res, seat + 2 * slot);       // else it was built there
+                    held = true; pj_rows = res.r;
+                    wave_sync();
+                } else {
+                    fin_res = true; fin_r = res.r;
+                    if (u > 0 && res.r > 0) {
+                        w_load(tmp, res.a, res.r, cols);                // from LDS, or from the side just written
+                        if (!st.in_lds) side ^= 1;
+                    }
+                }
+            }
+        }
+        if (lane_id() == 0) {                                           // (lane 0 wrote the counts: its stores keep their order)
+            if (okv != 1) for (int j = 0; j < rhs; j++) out_rows[(size_t)b * rhs + j] = 0;
+            out_ok[b] = okv; out_chain[b] = chain; out_steps[b] = steps;
+        }
         wave_sync();
         LQ_FLUSH
     }

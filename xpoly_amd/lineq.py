@@ -243,6 +243,44 @@ class Lineq:
             C.memmove(packed.ctypes.data, view.value, packed.nbytes)
         return ok, [[packed[int(off[b * rhs_idx + j]): int(off[b * rhs_idx + j + 1])].copy() for j in range(rhs_idx)] for b in range(nb)]
 
+    def bounds_packed(self, mats, rhs_idx, cap_rows=0, cap_out_rows=0, copy=True):
+        """xpg_lineq_bounds_batch_packed_rat32: Lineq::calcBound for every system in one launch. Returns (ok[nb], chain[nb],
+        steps[nb], bounds[b][j]): ok 1 with chain -1, or the verdict of the lowest failing chain -- 0 (step `steps` of chain
+        `chain` found the system inconsistent) or -need (that step needs `need` rows; steps == rhs_idx - 1: the chain's result
+        against cap_out_rows). A system with ok <= 0 has every bound empty, the others are packed all the same. copy=False: the
+        bounds are views of the handle's pinned buffer, valid until the next packed call on this handle."""
+        a = _stack(mats)
+        nb, rows, cols = a.shape[:3]
+        nres = nb * rhs_idx
+        off = np.zeros(max(nres, 0) + 1, dtype=np.int64)
+        ok = np.zeros(nb, dtype=np.int32); chain = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, chain, steps, []
+        view = C.c_void_p()
+        self.ctx.check(lib().xpg_lineq_bounds_batch_packed_rat32(
+            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), C.c_int(cap_rows or 0),
+            C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view), vp(off), vp(ok), vp(chain), vp(steps)),
+            "xpg_lineq_bounds_batch_packed_rat32")
+        total = int(off[-1])
+        if not copy and total:
+            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
+        else:
+            packed = np.empty((total, cols, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        o = off.tolist()
+        return ok, chain, steps, [[packed[o[b * rhs_idx + j]: o[b * rhs_idx + j + 1]] for j in range(rhs_idx)] for b in range(nb)]
+
+    @staticmethod
+    def bounds_last_route():
+        """xpg_lineq_bounds_last_route of the calling thread's last fused calcBound call, as a dict."""
+        out = np.zeros(7, dtype=np.int64)
+        rc = lib().xpg_lineq_bounds_last_route(vp(out), C.c_int(7))
+        if rc != 0:
+            raise ValueError("xpg_lineq_bounds_last_route: %d" % rc)
+        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "steps"), (int(x) for x in out)))
+
     def rank(self, mats):
         a = _stack(mats)
         nb, rows, cols = a.shape[:3]
@@ -334,6 +372,17 @@ def project_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, elim, darkshadow, cap_ro
                                                       C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
                                                       C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr)),
               "xpg_lineq_project_batch_rat32_dev")
+
+
+def bounds_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, cap_rows, cap_out_rows, outs_ptr, out_rows_ptr, out_ok_ptr, out_chain_ptr,
+               out_steps_ptr):
+    """xpg_lineq_bounds_batch_rat32_dev: Lineq::calcBound on device arrays in one launch, enqueue only. outs is
+    [nb][rhs_idx][cap_out_rows][cols] (cap_out_rows <= 0: cap_rows), out_rows [nb][rhs_idx], the other three [nb]."""
+    ctx.check(lib().xpg_lineq_bounds_batch_rat32_dev(ctx._h, C.c_int(nb), C.c_void_p(mats_ptr), C.c_int(rows), C.c_int(cols),
+                                                     C.c_int(rhs_idx), C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
+                                                     C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_chain_ptr),
+                                                     C.c_void_p(out_steps_ptr)),
+              "xpg_lineq_bounds_batch_rat32_dev")
 
 
 def rank_dev(ctx, nb, mats_ptr, rows, cols, out_rank_ptr):
