@@ -782,7 +782,8 @@ int xpg_lineq_reduce_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
 /* Gives the device blocks and pinned staging a handle keeps between host-array calls back to the runtime (they are
  * kept to spare one-system callers four hipMalloc / hipFree pairs per call; at most 1 GiB / 16 blocks), and the
  * scratch slots of xpg_six_batch_vc_*, xpg_six_batch_hbm_*, xpg_six_batch_vc_hbm_* and xpg_mip_batch_vc_hbm_* (which
- * shares xpg_six_batch_hbm_*'s), of xpg_lineq_project_batch_* and of xpg_lineq_bounds_batch_*. */
+ * shares xpg_six_batch_hbm_*'s), of xpg_lineq_project_batch_* (xpg_lineq_levels_batch_* shares them) and of
+ * xpg_lineq_bounds_batch_*. */
 int xpg_trim(xpg_ctx * ctx);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems: for each variable j every
  * other variable is eliminated (innermost first) by chained fme launches that stay on the
@@ -848,6 +849,48 @@ int xpg_test_lineq_project_plan(int nb, int rows, int cols, int cap_rows, int ca
  * anything else -- 0, XPG_ERR_SHAPE (n_elim <= 0, no list, an index outside [0, rhs_idx), rhs_idx outside [1, cols)) or
  * XPG_ERR_UNSUPPORTED (more than 64 entries).  The function the calls themselves ask. */
 int xpg_test_lineq_project_check(int cols, int rhs_idx, const int32_t * elim, int n_elim);
+/* A projection that KEEPS EVERY LEVEL: loop-bound generation (LoopTran::transformIterSpace, src/eng/ldtran.cpp:178-196 and
+ * :241-257) eliminates rhs_idx-1 .. 1 and records the system after each step, which bounds a loop of its own.  For nb systems
+ * of one shape the variables elim[0 .. n_elim) are eliminated one after the other in ONE launch, as the projection does, and
+ * the rows after EACH step are stored and packed: level k of system b is the system with elim[0 .. k] eliminated.  The list
+ * follows the projection's rules (xpg_test_lineq_project_check); darkshadow goes to every step.
+ *   cap_rows      rows an intermediate may have before it is reduced; <= 0: fme's worst case for `rows`
+ *   cap_out_rows  rows of a level's slot; <= 0: min(cap_rows, 4 * rows + 16) -- the slots follow nb * n_elim, not the grid, so
+ *                 the default is not the worst case; above cap_rows: cap_rows
+ *   row_offsets   [nb * n_elim + 1], entry b * n_elim + k the first row of level k of system b (the layout
+ *                 xpg_lineq_bounds_batch_packed_rat32 uses for [nb][rhs_idx])
+ *   out_ok[b]     1: out_steps[b] = n_elim and every level is packed (after an empty intermediate every later level has 0
+ *                 rows: fme of an empty system is true and empty);  0: step out_steps[b] found the system inconsistent;
+ *                 -need, with out_steps[b] = k:  need > cap_rows: step k's unreduced result needs `need` rows;
+ *                 cap_out_rows < need <= cap_rows: level k's reduced result has `need` rows and does not fit its slot.  The
+ *                 two cannot be confused: a reduced result never has more rows than its step built, which were at most
+ *                 cap_rows.  A system with out_ok[b] <= 0 contributes no rows at ANY level, those before its failing step
+ *                 included; the others are packed all the same.
+ * outs, outs_cap_rows and out_view as xpg_lineq_project_batch_packed_rat32 (neither outs nor out_view: a sizing call).
+ * XPG_ERR_SHAPE / XPG_ERR_UNSUPPORTED as the projection; nb * n_elim above INT_MAX is XPG_ERR_UNSUPPORTED.  nb == 0: returns
+ * 0, row_offsets[0] = 0. */
+int xpg_lineq_levels_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
+                                        const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                        xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                        long long * row_offsets, int32_t * out_ok, int32_t * out_steps);
+/* The same on DEVICE arrays, enqueue only (elim stays a host array): d_outs [nb][n_elim][cap_out_rows][cols] receives each
+ * level's live rows and is not cleared behind them, d_out_rows [nb][n_elim] their counts (all 0 for a system with d_out_ok <=
+ * 0), d_out_ok / d_out_steps [nb].  The intermediates' slots are the projection's (grow-only; xpg_trim returns them).  Both
+ * capacities are the caller's, nothing is defaulted or clamped: cap_rows < rows, cap_out_rows <= 0 or cap_out_rows > cap_rows
+ * is XPG_ERR_SHAPE.  This differs on purpose from xpg_lineq_project_batch_rat32_dev, where cap_out_rows <= 0 stands for
+ * cap_rows: here cap_out_rows is the row stride of nb x n_elim slots of d_outs, and no default of it is a safe guess. */
+int xpg_lineq_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
+                                     const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                     xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_lineq_levels_batch_* call did.  out[0 .. 6) as
+ * xpg_lineq_project_last_route (launches, grid, systems per workgroup, LDS bytes per system, rows of the LDS result area,
+ * bytes of intermediate slots: independent of nb), [6] bytes of the level slots, nb x n_elim x cap_out_rows x cols x 8.  Fills
+ * min(n, 7) entries. */
+int xpg_lineq_levels_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same seven figures from the shape alone -- the function the launch itself
+ * asks -- then [7] the cap_rows and [8] the cap_out_rows it settles on.  Fills min(n, 9) entries; XPG_ERR_SHAPE (n_elim <= 0
+ * too) / XPG_ERR_UNSUPPORTED (n_elim > 64 too) as the call. */
+int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, long long * out, int n);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems of one shape in ONE launch: the bounds of every variable j
  * alone (the other rhs_idx - 1 variables eliminated, inner to outer).  The rhs_idx chains of a system share their beginnings
  * -- each starts by eliminating rhs_idx-1 .. j+1 -- so a wavefront walks those prefixes once and runs only the tail j-1 .. 0

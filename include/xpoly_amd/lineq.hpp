@@ -10,7 +10,7 @@
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
 // should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
-// calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
+// levels_all, calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
 #define XPOLY_AMD_LINEQ_HPP
@@ -219,6 +219,84 @@ public:
         if ((int)limits.get_elem_count() != m_rhs_idx) return false;      // the reference ASSERTs (linsys.cpp:1050-1051)
         return calc_bound_into([&](int j, const std::vector<xpg_rat32> & a, int r, int c) { put(*limits.get_head_nth((unsigned)j), a, r, c); });
     }
+    // Loop-bound generation, LoopTran::transformIterSpace (src/eng/ldtran.cpp:178-196 unimodular, :241-257 nonsingular):
+    //     newb = aux_limits.get_tail();
+    //     for (i = m_rhs_idx - 1; i > 0; i--) { *newb = *A; lineq.fme(i, res); *A = res; newb = aux_limits.get_prev(); }
+    //     *newb = *A;
+    // in ONE call and one launch (xpg_lineq_levels_batch_packed_rat32: every level of the projection is kept). `aux_limits`
+    // holds m_rhs_idx matrices the caller owns (else false); walking from get_tail() by get_prev() the tail receives the
+    // system unchanged, each further entry the next level -- variables m_rhs_idx-1 .. 1 eliminated one after the other --
+    // and the head the outermost bound: what the loop leaves in the list. A (may be null; may be the system itself, as in
+    // the reference) receives the last level, as the loop leaves *A. false where a step found the system inconsistent (the
+    // reference ASSERTs there) or the call failed: the list is then left as it was. m_rhs_idx == 1 copies and makes no call.
+    //   bool fmeLevels(ListT & aux_limits, RMat * A = 0)           -- a list with get_tail / get_prev / get_elem_count
+    //   bool fmeLevels(std::vector<RMat> & aux_limits, RMat * A = 0) -- value semantics: resized to m_rhs_idx, [0] the
+    //                                                                 outermost bound (the head), back() the system
+private:
+    static void put_rows(RMatT & m, const xpg_rat32 * a, int rows, int cols)
+    {
+        m.reinit((unsigned)rows, (unsigned)cols);
+        if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a, sizeof(xpg_rat32) * (size_t)rows * cols);
+    }
+    // sink(pos, cells, rows, cols): pos 0 is the system itself (the tail), pos k + 1 level k; called only once every level
+    // is there, read straight out of the handle's pinned buffer. A capacity found short is raised to the need reported --
+    // need > cap: a step's unreduced rows, else a level's slot -- and the call made again, at most four times.
+    template <class Sink> bool levels_into(Sink sink)
+    {
+        const int nv = m_rhs_idx, n = nv - 1;
+        if (nv < 1) return false;
+        const int rows = m_coeff->size() == 0 ? 0 : (int)m_coeff->get_row_size(), cols = (int)m_coeff->get_col_size();
+        const xpg_rat32 * in = rows ? (const xpg_rat32 *)m_coeff->get_matrix() : (const xpg_rat32 *)0;
+        if (n == 0 || rows == 0) {                               // nothing to eliminate, or an empty system: it stays empty
+            sink(0, in, rows, cols);
+            for (int k = 0; k < n; k++) sink(k + 1, (const xpg_rat32 *)0, 0, cols);
+            return true;
+        }
+        std::vector<int32_t> elim((size_t)n);
+        for (int k = 0; k < n; k++) elim[(size_t)k] = nv - 1 - k;
+        int cap = rows * rows / 4 + rows + 1, cap_out = cap < 4 * rows + 16 ? cap : 4 * rows + 16;
+        for (int attempt = 0; attempt < 4; attempt++) {
+            std::vector<long long> off((size_t)n + 1, 0);
+            const xpg_rat32 * view = 0;
+            int32_t ok = 0, step = 0;
+            if (xpg_lineq_levels_batch_packed_rat32(ctx(), 1, in, rows, cols, nv, elim.data(), n, 0, cap, cap_out, (xpg_rat32 *)0, 0, &view,
+                                                    off.data(), &ok, &step) != 0) return false;
+            if (ok < 0) { if (-ok > cap) cap = -ok; else cap_out = -ok; continue; }
+            if (ok == 0) return false;                           // "system inconsistency!" (ldtran.cpp:186-188)
+            sink(0, in, rows, cols);
+            for (int k = 0; k < n; k++)
+                sink(k + 1, off[(size_t)k + 1] > off[(size_t)k] ? view + (size_t)off[(size_t)k] * cols : (const xpg_rat32 *)0,
+                     (int)(off[(size_t)k + 1] - off[(size_t)k]), cols);
+            return true;
+        }
+        return false;
+    }
+public:
+    bool fmeLevels(std::vector<RMatT> & aux_limits, RMatT * A = 0)
+    {
+        if (m_rhs_idx < 1) return false;
+        const size_t nv = (size_t)m_rhs_idx;
+        std::vector<RMatT> got(nv);
+        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { put_rows(got[nv - 1 - (size_t)pos], a, r, c); })) return false;
+        aux_limits.swap(got);
+        if (A) *A = aux_limits[0];
+        return true;
+    }
+    template <class ListT, class = decltype(std::declval<ListT &>().get_tail()), class = decltype(std::declval<ListT &>().get_prev()),
+              class = decltype(std::declval<ListT &>().get_elem_count())>
+    bool fmeLevels(ListT & aux_limits, RMatT * A = 0)
+    {
+        if (m_rhs_idx < 1 || (int)aux_limits.get_elem_count() != m_rhs_idx) return false;   // the reference ASSERTs (ldtran.cpp:191-192)
+        std::vector<RMatT *> dst;                                // the tail first; none of them is the system itself
+        for (RMatT * newb = aux_limits.get_tail(); (int)dst.size() < m_rhs_idx; newb = aux_limits.get_prev()) {
+            if (!newb || newb == m_coeff) return false;
+            dst.push_back(newb);
+            if ((int)dst.size() == m_rhs_idx) break;
+        }
+        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { put_rows(*dst[(size_t)pos], a, r, c); })) return false;
+        if (A) *A = *dst.back();
+        return true;
+    }
 };
 
 // One SCoP's worth of dependence tests in ONE call: DepPoly::is_empty (src/eng/poly.cpp:530-573, called per polyhedron by
@@ -401,6 +479,80 @@ inline int project_all(const std::vector<RMatT *> & systems, const std::vector<i
                 ok[(size_t)b] = kok[(size_t)k];
                 results[(size_t)b].reinit((unsigned)(hi - lo), (unsigned)cols);
                 if (hi > lo) std::memcpy((void *)results[(size_t)b].get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
+            }
+            answered = true;
+        }
+        if (!answered) return XPG_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// Loop-nest limits for many statements in few calls: the variables elim[0], elim[1], ... eliminated out of every *systems[k]
+// as project_all does, but EVERY level is kept -- levels[k][step] is *systems[k] with elim[0 .. step] eliminated, the system
+// that bounds one loop of the nest (LoopTran::transformIterSpace, src/eng/ldtran.cpp:178-196, :241-257, with elim =
+// rhs_idx-1 .. 1; Lineq::fmeLevels above is the same for one system). Systems of one shape go up together, one
+// xpg_lineq_levels_batch_packed_rat32 call per shape class: one launch instead of one fme_all call per level, no
+// intermediate crosses the link twice. ok[k] = 1 with levels[k] filled, or 0 (a step found the system inconsistent) with
+// every level of k empty. A class found short of rows is called again with the need the library reports -- above the
+// capacity tried: a step's unreduced rows, cap_rows; else a level's slot, cap_out_rows -- at most four times; still short:
+// XPG_ERR_UNSUPPORTED, never a silent empty level. Returns 0 or a negative XPG_ERR_* code.
+template <class RMatT>
+inline int levels_all(const std::vector<RMatT *> & systems, const std::vector<int32_t> & elim, int rhs_idx,
+                      std::vector<std::vector<RMatT> > & levels, std::vector<int32_t> & ok, xpg_ctx * c = 0, bool darkshadow = false)
+{
+    const int nb = (int)systems.size(), n = (int)elim.size();
+    levels.assign((size_t)nb, std::vector<RMatT>());
+    ok.assign((size_t)nb, 0);
+    if (elim.empty() || rhs_idx < 1) return XPG_ERR_SHAPE;
+    xpg_ctx * h = c ? c : detail::shared_context();
+    std::vector<char> done((size_t)nb, 0);
+    for (int b0 = 0; b0 < nb; b0++) {
+        if (done[(size_t)b0]) continue;
+        if (systems[(size_t)b0]->size() == 0) {                     // an empty system stays empty (linsys.cpp:661-664), no call
+            levels[(size_t)b0].resize((size_t)n);
+            for (int k = 0; k < n; k++) levels[(size_t)b0][(size_t)k].clean();
+            ok[(size_t)b0] = 1; done[(size_t)b0] = 1;
+            continue;
+        }
+        const int rows = (int)systems[(size_t)b0]->get_row_size(), cols = (int)systems[(size_t)b0]->get_col_size();
+        std::vector<int> cls;
+        for (int b = b0; b < nb; b++)
+            if (!done[(size_t)b] && systems[(size_t)b]->size() != 0 && (int)systems[(size_t)b]->get_row_size() == rows &&
+                (int)systems[(size_t)b]->get_col_size() == cols) {
+                cls.push_back(b); done[(size_t)b] = 1;
+            }
+        const int nc = (int)cls.size();
+        std::vector<xpg_rat32> flat((size_t)nc * rows * cols);
+        for (int k = 0; k < nc; k++)
+            std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
+        int cap = rows * rows / 4 + rows + 1, cap_out = cap < 4 * rows + 16 ? cap : 4 * rows + 16;   // the library's defaults, spelled out
+        bool answered = false;
+        for (int attempt = 0; attempt < 4 && !answered; attempt++) {
+            std::vector<long long> off((size_t)nc * n + 1, 0);
+            std::vector<int32_t> kok((size_t)nc, 0), steps((size_t)nc, 0);
+            const xpg_rat32 * view = 0;
+            const int rc = xpg_lineq_levels_batch_packed_rat32(h, nc, flat.data(), rows, cols, rhs_idx, elim.data(), n, darkshadow ? 1 : 0,
+                                                               cap, cap_out, (xpg_rat32 *)0, 0, &view, off.data(), kok.data(), steps.data());
+            if (rc != 0) return rc;
+            int need_cap = 0, need_out = 0;
+            for (int k = 0; k < nc; k++) {
+                const int need = -kok[(size_t)k];
+                if (need > cap) { if (need > need_cap) need_cap = need; }
+                else if (need > need_out) need_out = need;          // (need <= 0: the system was answered)
+            }
+            if (need_cap) cap = need_cap;
+            if (need_out) cap_out = need_out;
+            if (need_cap || need_out) continue;
+            for (int k = 0; k < nc; k++) {
+                const int b = cls[(size_t)k];
+                ok[(size_t)b] = kok[(size_t)k];
+                levels[(size_t)b].resize((size_t)n);
+                for (int j = 0; j < n; j++) {
+                    const long long lo = off[(size_t)k * n + j], hi = off[(size_t)k * n + j + 1];
+                    RMatT & m = levels[(size_t)b][(size_t)j];
+                    m.reinit((unsigned)(hi - lo), (unsigned)cols);
+                    if (hi > lo) std::memcpy((void *)m.get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
+                }
             }
             answered = true;
         }

@@ -47,6 +47,8 @@ SYMBOLS = [
     "xpg_test_lineq_project_plan", "xpg_test_lineq_project_check",
     "xpg_lineq_bounds_batch_packed_rat32", "xpg_lineq_bounds_batch_rat32_dev", "xpg_lineq_bounds_last_route",
     "xpg_test_lineq_bounds_plan",
+    "xpg_lineq_levels_batch_packed_rat32", "xpg_lineq_levels_batch_rat32_dev", "xpg_lineq_levels_last_route",
+    "xpg_test_lineq_levels_plan",
 ]
 
 _lib = None

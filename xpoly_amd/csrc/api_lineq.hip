@@ -204,6 +204,43 @@ int xpg_test_lineq_project_plan(int nb, int rows, int cols, int cap_rows, int ca
 // host-only test view: what the projection entry points answer to an elimination list before they look at anything else
 // (lineq_host.hip.h project_check, the function they ask): 0, XPG_ERR_SHAPE or XPG_ERR_UNSUPPORTED
 int xpg_test_lineq_project_check(int cols, int rhs_idx, const int32_t * elim, int n_elim) { return project_check(cols, rhs_idx, elim, n_elim); }
+// ---- projection that keeps every level: loop-nest limits in one launch (lineq_host.hip.h) ------------------------------------
+int xpg_lineq_levels_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
+                                        const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                        xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                        long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_levels_batch_packed(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+                                     (R32 *)outs, outs_cap_rows, (const R32 **)out_view, row_offsets, out_ok, out_steps);
+}
+int xpg_lineq_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
+                                     const int32_t * elim, int n_elim, int darkshadow, int cap_rows, int cap_out_rows,
+                                     xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_levels_batch_dev(ctx, nb, (const R32 *)d_mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+                                  (R32 *)d_outs, d_out_rows, d_out_ok, d_out_steps);
+}
+// what the calling thread's last xpg_lineq_levels_batch_* call did (lineq_host.hip.h LevelsRoute)
+int xpg_lineq_levels_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const LevelsRoute & r = levels_route();
+    const long long f[7] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.level_bytes };
+    return copy_fields(out, n, f);
+}
+// host-only test view: the plan of a levels call from its shape alone (lineq_host.hip.h levels_plan), with the capacities it
+// settles on behind the route's seven figures
+int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    LevelsPlan l;
+    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
+    const long long f[9] = { 1, l.p.q.grid, l.p.q.G, l.p.q.sys_lds, l.p.cap_lds, (long long)l.p.seat_bytes, (long long)l.level_bytes, l.p.cap,
+                             l.p.cap_out };
+    return copy_fields(out, n, f);
+}
 // ---- calcBound fused: the bounds of every variable of every system in one launch (lineq_host.hip.h) ---------------------------
 int xpg_lineq_bounds_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx, int cap_rows,
                                         int cap_out_rows, xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,

@@ -428,6 +428,104 @@ inline int lineq_project_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, i
                             out, out_cap_rows, view, row_offsets, out_ok, out_steps, [](const char *) {});
 }
 
+// ---- projection that keeps every level: the list eliminated in ONE launch, the rows after EACH step stored (k_fme_levels_batch)
+// THE plan of a levels call (the launch and xpg_test_lineq_levels_plan both ask it): project_plan's capacities, LDS layout,
+// geometry and seats -- the walk is the projection's -- except that the level slots follow nb * n_elim, not the grid, so
+// cap_out_rows <= 0 is min(cap_rows, 4 * rows + 16) (the packed calcBound's default for a result) instead of cap_rows: at the
+// projection's worst-case default the slots of 1024 nests of 60 rows and depth 6 would be gigabytes.
+struct LevelsPlan { ProjectPlan p; size_t level_bytes; };
+inline int levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, LevelsPlan & l)
+{
+    if (n_elim <= 0) return XPG_ERR_SHAPE;
+    if (n_elim > FME_CHAIN_MAX) return XPG_ERR_UNSUPPORTED;
+    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, l.p)) return rc;
+    if (cap_out_rows <= 0) l.p.cap_out = l.p.cap < 4 * rows + 16 ? l.p.cap : 4 * rows + 16;
+    l.level_bytes = (size_t)nb * n_elim * (size_t)l.p.cap_out * cols * 8;
+    return 0;
+}
+// What the calling thread's last xpg_lineq_levels_batch_* call did (xpg_lineq_levels_last_route): ProjectRoute's figures and
+// the bytes of the level slots.
+struct LevelsRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, level_bytes; };
+inline LevelsRoute & levels_route() { static thread_local LevelsRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
+// Device arrays, enqueue only: d_outs [nb][n_elim][cap_out_rows][cols] receives the live rows of level k of system b in slot
+// (b, k) (nothing behind them), d_rows [nb][n_elim] their counts, d_ok / d_steps [nb] as k_fme_levels_batch writes them. The
+// seats are the projection's (the same grow-only scratch, the same two slots per seat). Both capacities are the caller's, who
+// laid d_outs out with them: cap_rows < rows, cap_out_rows <= 0 or cap_out_rows > cap_rows is XPG_ERR_SHAPE.
+inline int lineq_levels_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
+                                  int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows,
+                                  int32_t * d_ok, int32_t * d_steps)
+{
+    levels_route() = LevelsRoute{0, 0, 0, 0, 0, 0, 0};
+    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
+    if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || !d_rows || !d_ok || !d_steps) return XPG_ERR_SHAPE;
+    if (cap_rows < rows || cap_out_rows <= 0 || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    if ((long long)nb * n_elim > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    LevelsPlan l;
+    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
+    const ProjectPlan & p = l.p;
+    Scratch & slots = ctx->scratch[SCRATCH_LINEQ_PROJECT];
+    if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_levels seats)")) return rc;
+    ElimList el;
+    el.n = n_elim;
+    for (int k = 0; k < FME_CHAIN_MAX; k++) el.u[k] = k < n_elim ? elim[k] : 0;
+    XPG_TRY(lds_limit((const void *)k_fme_levels_batch, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_fme_levels_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, el,
+                       darkshadow, (R32 *)slots.buf, p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps,
+                       p.cap_lds, p.q.sys_lds);
+    XPG_TRY(hipGetLastError());
+    levels_route() = LevelsRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)l.level_bytes};
+    return 0;
+}
+// Host arrays with a PACKED result in the layout of lineq_bounds_batch_packed: row_offsets [nb * n_elim + 1], entry
+// b * n_elim + k where level k of system b starts. One upload, the one launch, packed_rows_down over the nb * n_elim results;
+// the verdicts (ok, steps: [nb] each) come down through hred beside it, under the same synchronisation. A system with
+// out_ok <= 0 contributes no rows at any level, the others are packed all the same; out / view / sizing call as
+// lineq_project_batch_packed.
+inline int lineq_levels_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, const int32_t * elim,
+                                     int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
+                                     const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
+{
+    if (view) *view = 0;
+    levels_route() = LevelsRoute{0, 0, 0, 0, 0, 0, 0};
+    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
+    if (!ctx || nb < 0 || !mats || rows <= 0 || !row_offsets || !out_ok || !out_steps || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
+    if (nb == 0) { row_offsets[0] = 0; return 0; }
+    LevelsPlan l;
+    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
+    if ((long long)nb * n_elim > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    const int nres = nb * n_elim;
+    const size_t bi = (size_t)nb * rows * cols * 8, bo = l.level_bytes, bv = (size_t)nb * 4;
+    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 12;  // offsets, then (unused) ok, rows and (unused) steps
+    const size_t meta_al = (meta + 255) & ~(size_t)255;
+    DevBuf di, dout, dr, dv, doff;                                   // dv: ok and steps, [2][nb]
+    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nres * 4)); XPG_TRY(dv.alloc(ctx, 2 * bv));
+    XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
+    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
+    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
+    if (rc) return rc;
+    if ((rc = hpack_reserve(ctx, 2 * bv, true))) return rc;
+    char * hp = hpack_buf(ctx, false);
+    int32_t * hv = (int32_t *)hpack_buf(ctx, true);
+    if (small_in) {
+        memcpy(hp + meta_al, mats, bi);
+        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int32_t * const d_ok = (int32_t *)dv.p;
+    rc = lineq_levels_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, elim, n_elim, darkshadow, l.p.cap, l.p.cap_out, (R32 *)dout.p,
+                                (int32_t *)dr.p, d_ok, d_ok + nb);
+    if (rc) return rc;
+    XPG_TRY(hipMemcpyAsync(hv, dv.p, 2 * bv, hipMemcpyDeviceToHost, ctx->stream));
+    rc = packed_rows_down(ctx, nres, cols, l.p.cap_out, dout, dr, dv, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
+                          out, out_cap_rows, view, row_offsets, (int32_t *)0, (int32_t *)0, [](const char *) {});
+    if (rc == 0 || rc == XPG_ERR_SHAPE) {                            // (it has synchronised: a buffer too small still gets its verdicts)
+        memcpy(out_ok, hv, bv); memcpy(out_steps, hv + nb, bv);
+    }
+    return rc;
+}
+
 // Lineq::calcBound (linsys.cpp:1047-1078) for nb systems at once: for every variable j the
 // other variables are eliminated innermost-first by chained k_fme_batch launches that stay on
 // the device (ragged row counts travel in an int array). bounds is [nb][rhs][cap][cols],

@@ -690,6 +690,62 @@ __global__ __launch_bounds__(64) void k_fme_chain_batch(int nb, const R32 * mats
     }
 }
 
+// A projection that KEEPS EVERY LEVEL: loop-bound generation (LoopTran::transformIterSpace, eng/ldtran.cpp:178-196 and :241-257)
+// eliminates rhs-1 .. 1 and records the system after each step -- level k, with el.u[0 .. k] eliminated, bounds a loop of its
+// own. The walk is k_fme_chain_batch's (a wavefront per system, every step through w_fme_step, intermediates in the LDS result
+// area or in the seat's two alternating slots of `seats` [seats][2][cap][cols], seats reused above the grid) with a loop of
+// its own, so that the chain kernel keeps its text and its registers (profiles/lineq_levels_isa.txt). New is the store: after
+// step k succeeds its rows go -- whole cells across the lanes, from LDS or from the side just written -- to slot (b, k) of
+// outs [nb][el.n][cap_out][cols] and their count to out_rows [nb][el.n], BEFORE they are loaded as step k+1's input (the next
+// step normalises its input in place). Nothing is stored behind a level's rows.
+//   out_ok[b] 1, out_steps[b] el.n: every level is stored (after an empty intermediate every later level has 0 rows: fme of
+//                                   an empty system is true and empty)
+//   out_ok[b] 0, out_steps[b] k:    step k found the system inconsistent
+//   out_ok[b] -need, out_steps[b] k: need > cap: step k's unreduced result needs `need` rows; cap_out < need <= cap: level
+//                                   k's reduced result has `need` rows and does not fit its slot. The two cannot be confused:
+//                                   a reduced result never has more rows than its step built, and that was at most cap.
+// A system with out_ok[b] <= 0 has 0 rows at EVERY level, those before its failing step included: lane 0 zeroes the counts it
+// has already written (its stores keep their order), as k_calc_bound_batch does.
+__global__ __launch_bounds__(64) void k_fme_levels_batch(int nb, const R32 * mats, int rows, int cols, int rhs, ElimList el,
+                                                         int darkshadow, R32 * seats, int cap, R32 * outs, int cap_out,
+                                                         int * out_rows, int * out_ok, int * out_steps, int cap_lds, int sys_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
+    R32 * const res_lds = (R32 *)lds;
+    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
+    R32 * const seat = seats + (size_t)sys_first() * 2 * cap * cols;
+    LQ_CLEAR
+    for (int b = sys_first(); b < nb; b += sys_stride()) {
+        w_load(tmp, mats + (size_t)b * rows * cols, rows, cols);
+        int * const cnt = out_rows + (size_t)b * el.n;
+        int okv = 1, steps = el.n, side = 0, k = 0;
+        for (; k < el.n; k++) {
+            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * cap * cols, cols, rhs, el.u[k], darkshadow, cap,
+                                          cap_lds, cap, s);
+            wave_sync();
+            if (st.over >= 0) { okv = -st.over; steps = k; break; }
+            if (!st.ok) { okv = 0; steps = k; break; }
+            if (res.r > cap_out) { okv = -res.r; steps = k; break; }
+            if (res.r == 0) break;                                      // empty from here on: this and every later level
+            w_store(res, outs + ((size_t)b * el.n + k) * cap_out * cols);
+            if (lane_id() == 0) cnt[k] = res.r;
+            if (k + 1 < el.n) {
+                w_load(tmp, res.a, res.r, cols);                        // from LDS, or from the side just written
+                if (!st.in_lds) side ^= 1;
+            }
+        }
+        if (lane_id() == 0) {
+            for (int j = okv == 1 ? k : 0; j < el.n; j++) cnt[j] = 0;   // the levels not reached; all of them after a failure
+            out_ok[b] = okv; out_steps[b] = steps;
+        }
+        wave_sync();
+        LQ_FLUSH
+    }
+}
+
 // Lineq::calcBound (linsys.cpp:1047-1078): for every variable j of a system the other rhs - 1 variables eliminated, inner to
 // outer, ALL rhs chains of a system before the wave takes its next system. Chain j is rhs-1 .. j+1, then j-1 .. 0, so every
 // chain starts with a prefix of rhs-1 .. 1: with P_j the system with the variables above j eliminated (P_{rhs-1} the input,

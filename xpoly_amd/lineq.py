@@ -160,6 +160,45 @@ class Lineq:
             raise ValueError("xpg_lineq_project_last_route: %d" % rc)
         return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes"), (int(x) for x in out)))
 
+    def levels_packed(self, mats, rhs_idx, elim, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_levels_batch_packed_rat32: the projection that keeps every level -- the variables of `elim` eliminated one
+        after the other in one launch, the rows after EACH step kept (loop-nest limits, LoopTran::transformIterSpace). Returns
+        (ok[nb], steps[nb], levels) with levels[b][k] the rows of system b once elim[0 .. k] are eliminated: ok 1 with steps ==
+        len(elim), 0 with the step that found the system inconsistent, or -need with the step k concerned -- need > cap_rows:
+        step k's unreduced result needs `need` rows; else level k has `need` > cap_out_rows rows. A system with ok <= 0 has no
+        rows at any level. copy=False: the levels are views of the handle's pinned buffer, valid until the next packed call."""
+        a = _stack(mats)
+        nb, rows, cols = a.shape[:3]
+        el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
+        n = int(el.size)
+        off = np.zeros(nb * n + 1, dtype=np.int64); ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, steps, []
+        view = C.c_void_p()
+        self.ctx.check(lib().xpg_lineq_levels_batch_packed_rat32(
+            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), vp(el), C.c_int(n),
+            C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view),
+            vp(off), vp(ok), vp(steps)), "xpg_lineq_levels_batch_packed_rat32")
+        total = int(off[-1])
+        if not copy and total:
+            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
+        else:
+            packed = np.empty((total, cols, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        o = off.tolist()
+        return ok, steps, [[packed[o[b * n + k]: o[b * n + k + 1]] for k in range(n)] for b in range(nb)]
+
+    @staticmethod
+    def levels_last_route():
+        """xpg_lineq_levels_last_route of the calling thread's last levels call, as a dict."""
+        out = np.zeros(7, dtype=np.int64)
+        rc = lib().xpg_lineq_levels_last_route(vp(out), C.c_int(7))
+        if rc != 0:
+            raise ValueError("xpg_lineq_levels_last_route: %d" % rc)
+        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "level_bytes"), (int(x) for x in out)))
+
     def reduce_ragged(self, mats_list, rhs_idx=None, is_intersect=True):
         """Lineq::reduce on systems of different shapes in one call: (ok[nb], [system b's surviving rows])."""
         from .six import _ragged_pack
@@ -372,6 +411,19 @@ def project_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, elim, darkshadow, cap_ro
                                                       C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
                                                       C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr)),
               "xpg_lineq_project_batch_rat32_dev")
+
+
+def levels_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, elim, darkshadow, cap_rows, cap_out_rows, outs_ptr, out_rows_ptr,
+               out_ok_ptr, out_steps_ptr):
+    """xpg_lineq_levels_batch_rat32_dev: every level of a projection on device arrays in one launch, enqueue only. `elim` is a
+    host list; outs is [nb][len(elim)][cap_out_rows][cols], out_rows [nb][len(elim)], the other two [nb]. Both capacities are
+    the caller's: none is defaulted."""
+    el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
+    ctx.check(lib().xpg_lineq_levels_batch_rat32_dev(ctx._h, C.c_int(nb), C.c_void_p(mats_ptr), C.c_int(rows), C.c_int(cols),
+                                                     C.c_int(rhs_idx), vp(el), C.c_int(el.size), C.c_int(int(darkshadow)),
+                                                     C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
+                                                     C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr)),
+              "xpg_lineq_levels_batch_rat32_dev")
 
 
 def bounds_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, cap_rows, cap_out_rows, outs_ptr, out_rows_ptr, out_ok_ptr, out_chain_ptr,
