@@ -891,6 +891,47 @@ int xpg_lineq_levels_last_route(long long * out, int n);
  * asks -- then [7] the cap_rows and [8] the cap_out_rows it settles on.  Fills min(n, 9) entries; XPG_ERR_SHAPE (n_elim <= 0
  * too) / XPG_ERR_UNSUPPORTED (n_elim > 64 too) as the call. */
 int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, long long * out, int n);
+/* The projection and the levels for systems of MIXED shapes and lists in ONE launch: the statements of a SCoP sit at
+ * different depths, so rows, cols, rhs_idx and the list rhs_idx-1 .. 1 differ from statement to statement.  mats holds the
+ * systems, system b (rows[b] x cols[b]) at cell offsets[b]; rhs_idx[b] its constant column (NULL: the last column of each);
+ * its list is elim[elim_offsets[b] .. elim_offsets[b + 1]) (elim_offsets[0] = 0), under the projection's rules.  Every step of
+ * every system runs in one launch, whose LDS layout and capacities are those of the ENVELOPE -- the widest system's columns,
+ * the capacities of the system with the most rows -- while each system keeps its own row stride, so its results are, bit for
+ * bit, those of the uniform calls with the same capacities.
+ *   cap_rows      rows an intermediate may have before it is reduced; <= 0: fme's worst case for the LARGEST rows[b]
+ *   cap_out_rows  rows of an output slot; <= 0: cap_rows (projection), min(cap_rows, 4 * max rows + 16) (levels)
+ *   projection    out_cell_offsets [nb + 1], out_rows [nb]: result b (out_rows[b] rows, cols[b] wide) starts at CELL
+ *                 out_cell_offsets[b] (the convention of xpg_lineq_fme_batch_ragged_rat32)
+ *   levels        out_cell_offsets [elim_offsets[nb] + 1], out_rows [elim_offsets[nb]]: level k of system b is entry
+ *                 elim_offsets[b] + k
+ *   out_ok, out_steps [nb]: as xpg_lineq_project_batch_packed_rat32 / xpg_lineq_levels_batch_packed_rat32, `need` judged
+ *                 against the call's cap_rows / cap_out_rows.  A system with out_ok[b] <= 0 contributes no cells.
+ * outs (may be NULL) has room for outs_cap_cells cells, out_view (may be NULL) receives a pointer into the handle's pinned
+ * buffer, valid until the handle's next packed call; neither: a sizing call.  XPG_ERR_SHAPE where outs is too small (offsets,
+ * counts and verdicts are filled).  Decided before anything is launched: XPG_ERR_SHAPE -- an empty list, an index outside
+ * [0, rhs_idx[b]), rhs_idx[b] outside [1, cols[b]), rows[b] <= 0; XPG_ERR_UNSUPPORTED -- a list above 64 entries, the
+ * envelope's LDS layout over 160 KB, cap_rows > 32767.  nb == 0: returns 0, out_cell_offsets[0] = 0.  The intermediates'
+ * slots are the projection's (xpg_trim returns them). */
+int xpg_lineq_project_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                         const long long * offsets, const int32_t * rhs_idx, const int32_t * elim,
+                                         const int32_t * elim_offsets, int darkshadow, int cap_rows, int cap_out_rows, xpg_rat32 * outs,
+                                         long long outs_cap_cells, const xpg_rat32 ** out_view, long long * out_cell_offsets,
+                                         int32_t * out_rows, int32_t * out_ok, int32_t * out_steps);
+int xpg_lineq_levels_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                        const long long * offsets, const int32_t * rhs_idx, const int32_t * elim,
+                                        const int32_t * elim_offsets, int darkshadow, int cap_rows, int cap_out_rows, xpg_rat32 * outs,
+                                        long long outs_cap_cells, const xpg_rat32 ** out_view, long long * out_cell_offsets,
+                                        int32_t * out_rows, int32_t * out_ok, int32_t * out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last ragged projection / levels call did.  out[0] launches of
+ * the chain kernel (1; 0 where nothing ran), [1] its grid, [2] systems per workgroup, [3] LDS bytes per system, [4] rows of
+ * the LDS result area, [5] bytes of intermediate slots (grid x [2] x 2 x cap_rows x widest cols x 8), [6] bytes of output
+ * slots (cap_out_rows x cols[b] x 8 per result).  Fills min(n, 7) entries. */
+int xpg_lineq_ragged_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same seven figures from the shapes and lists alone -- the function the
+ * launch itself asks, with its error codes -- then [7] the cap_rows, [8] the cap_out_rows, [9] the columns and [10] the rows
+ * of the envelope.  levels != 0: the levels call's plan.  Fills min(n, 11) entries. */
+int xpg_test_lineq_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, const int32_t * elim,
+                               const int32_t * elim_offsets, int levels, int cap_rows, int cap_out_rows, long long * out, int n);
 /* Lineq::calcBound, src/com/linsys.cpp:1047-1078, for nb systems of one shape in ONE launch: the bounds of every variable j
  * alone (the other rhs_idx - 1 variables eliminated, inner to outer).  The rhs_idx chains of a system share their beginnings
  * -- each starts by eliminating rhs_idx-1 .. j+1 -- so a wavefront walks those prefixes once and runs only the tail j-1 .. 0

@@ -10,7 +10,7 @@
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
 // should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
-// levels_all, calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
+// levels_all, project_each, levels_nests, calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
 #define XPOLY_AMD_LINEQ_HPP
@@ -559,6 +559,135 @@ inline int levels_all(const std::vector<RMatT *> & systems, const std::vector<in
         if (!answered) return XPG_ERR_UNSUPPORTED;
     }
     return 0;
+}
+
+namespace detail {
+// What project_each and levels_nests share: the systems that travel (`live`: indices into `systems`, each with its list in
+// `lists`) go up in ONE xpg_lineq_{project,levels}_batch_ragged_rat32 call whatever their shapes and lists; a call found
+// short of rows is made again with the largest need reported -- above the capacity tried: a step's unreduced rows, cap_rows;
+// else an output slot, cap_out_rows -- at most four times, then XPG_ERR_UNSUPPORTED. sink(i, k, cells, rows, cols) receives
+// result k of live system i (k == 0 alone for a projection) out of the handle's pinned buffer, once every answer is there;
+// ok[live[i]] the verdict (1, or 0: a step found the system inconsistent, every result of it empty).
+template <class RMatT, class Sink>
+inline int chain_ragged(bool levels, const std::vector<RMatT *> & systems, const std::vector<int> & live, const std::vector<std::vector<int32_t> > & lists,
+                        const std::vector<int32_t> & rhs_idx, std::vector<int32_t> & ok, xpg_ctx * h, bool darkshadow, Sink sink)
+{
+    const int nl = (int)live.size();
+    if (nl == 0) return 0;
+    std::vector<int32_t> rows((size_t)nl), cols((size_t)nl), rr((size_t)nl), eoff((size_t)nl + 1, 0), flat_el;
+    std::vector<long long> off((size_t)nl + 1, 0);
+    for (int i = 0; i < nl; i++) {
+        const RMatT & m = *systems[(size_t)live[(size_t)i]];
+        rows[(size_t)i] = (int32_t)m.get_row_size(); cols[(size_t)i] = (int32_t)m.get_col_size();
+        rr[(size_t)i] = rhs_idx[(size_t)live[(size_t)i]];
+        off[(size_t)i + 1] = off[(size_t)i] + (long long)rows[(size_t)i] * cols[(size_t)i];
+        flat_el.insert(flat_el.end(), lists[(size_t)i].begin(), lists[(size_t)i].end());
+        eoff[(size_t)i + 1] = (int32_t)flat_el.size();
+    }
+    std::vector<xpg_rat32> flat((size_t)off[(size_t)nl]);
+    for (int i = 0; i < nl; i++)
+        std::memcpy((void *)(flat.data() + off[(size_t)i]), (const void *)systems[(size_t)live[(size_t)i]]->get_matrix(),
+                    sizeof(xpg_rat32) * (size_t)rows[(size_t)i] * cols[(size_t)i]);
+    const int nres = levels ? (int)flat_el.size() : nl;
+    int cap = 0, cap_out = 0;                                       // the library's defaults first
+    for (int attempt = 0; attempt < 4; attempt++) {
+        std::vector<long long> ooff((size_t)nres + 1, 0);
+        std::vector<int32_t> orows((size_t)nres, 0), kok((size_t)nl, 0), steps((size_t)nl, 0);
+        const xpg_rat32 * view = 0;
+        const int rc = (levels ? xpg_lineq_levels_batch_ragged_rat32 : xpg_lineq_project_batch_ragged_rat32)(
+            h, nl, flat.data(), rows.data(), cols.data(), off.data(), rr.data(), flat_el.data(), eoff.data(), darkshadow ? 1 : 0, cap, cap_out,
+            (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), steps.data());
+        if (rc != 0) return rc;
+        if (cap == 0) {                                             // the capacities that call settled on (xpoly_amd.h), spelled out
+            int most = 0;
+            for (int i = 0; i < nl; i++) if (rows[(size_t)i] > most) most = rows[(size_t)i];
+            cap = most * most / 4 + most + 1;
+            cap_out = levels && 4 * most + 16 < cap ? 4 * most + 16 : cap;
+        }
+        int need_cap = 0, need_out = 0;
+        for (int i = 0; i < nl; i++) {
+            const int need = -kok[(size_t)i];
+            if (need > cap) { if (need > need_cap) need_cap = need; }
+            else if (need > need_out) need_out = need;              // (need <= 0: the system was answered)
+        }
+        if (need_cap) cap = need_cap;
+        if (need_out) cap_out = need_out;
+        if (!levels) cap_out = cap;                                 // (a projection's final slot takes cap)
+        if (need_cap || need_out) continue;
+        for (int i = 0; i < nl; i++) {
+            ok[(size_t)live[(size_t)i]] = kok[(size_t)i];
+            const int first = levels ? eoff[(size_t)i] : i, n = levels ? eoff[(size_t)i + 1] - eoff[(size_t)i] : 1;
+            for (int k = 0; k < n; k++)
+                sink(i, k, view ? view + ooff[(size_t)(first + k)] : view, (int)orows[(size_t)(first + k)], (int)cols[(size_t)i]);
+        }
+        return 0;
+    }
+    return XPG_ERR_UNSUPPORTED;
+}
+template <class RMatT> inline void put_cells(RMatT & m, const xpg_rat32 * a, int rows, int cols)
+{
+    m.reinit((unsigned)rows, (unsigned)cols);
+    if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a, sizeof(xpg_rat32) * (size_t)rows * cols);
+}
+} // namespace detail
+
+// Many projections in ONE call whatever the shapes: project_all with a list and a constant column PER SYSTEM -- the variables
+// elims[k][0], elims[k][1], ... eliminated out of *systems[k], the constant in column rhs_idx[k]. Statements of different depth
+// (other rows, columns, rhs_idx and lists) go up together in one xpg_lineq_project_batch_ragged_rat32 call: one upload, one
+// launch. ok[k] = 1 and results[k] the projection, or 0 (a step found the system inconsistent) with results[k] empty. Empty
+// systems stay empty (linsys.cpp:661-664) and do not travel. A call found short of rows is made again with the largest need
+// the library reports, at most four times; still short: XPG_ERR_UNSUPPORTED, never a silent empty result. Returns 0 or a
+// negative XPG_ERR_* code (XPG_ERR_SHAPE: a missing or empty list).
+template <class RMatT>
+inline int project_each(const std::vector<RMatT *> & systems, const std::vector<std::vector<int32_t> > & elims, const std::vector<int32_t> & rhs_idx,
+                        std::vector<RMatT> & results, std::vector<int32_t> & ok, xpg_ctx * c = 0, bool darkshadow = false)
+{
+    const int nb = (int)systems.size();
+    results.resize((size_t)nb); ok.assign((size_t)nb, 0);
+    if ((int)elims.size() != nb || (int)rhs_idx.size() != nb) return XPG_ERR_SHAPE;
+    std::vector<int> live;
+    std::vector<std::vector<int32_t> > lists;
+    for (int b = 0; b < nb; b++) {
+        if (elims[(size_t)b].empty() || rhs_idx[(size_t)b] < 1) return XPG_ERR_SHAPE;
+        if (systems[(size_t)b]->size() == 0) { results[(size_t)b].clean(); ok[(size_t)b] = 1; }
+        else { live.push_back(b); lists.push_back(elims[(size_t)b]); }
+    }
+    return detail::chain_ragged(false, systems, live, lists, rhs_idx, ok, c ? c : detail::shared_context(), darkshadow,
+                                [&](int i, int, const xpg_rat32 * a, int r, int cc) { detail::put_cells(results[(size_t)live[(size_t)i]], a, r, cc); });
+}
+
+// Loop-nest limits for the statements of a SCoP in ONE call: levels_all for nests of DIFFERENT depths. System k has rhs_idx[k]
+// variables and is walked as LoopTran::transformIterSpace walks it (src/eng/ldtran.cpp:178-196, :241-257): rhs_idx[k]-1 .. 1
+// eliminated one after the other, levels[k][step] the system after step `step` (rhs_idx[k] - 1 of them; Lineq::fmeLevels is
+// the same for one system). All nests that have something to eliminate go up in one xpg_lineq_levels_batch_ragged_rat32 call:
+// one upload, one launch, no intermediate crosses the link twice. Empty systems and nests of depth 1 are answered here, as
+// fmeLevels answers them: ok 1, every level (none at depth 1) empty. ok[k] = 0: a step found the system inconsistent, every
+// level of k empty. Retries and return codes as project_each.
+template <class RMatT>
+inline int levels_nests(const std::vector<RMatT *> & systems, const std::vector<int32_t> & rhs_idx, std::vector<std::vector<RMatT> > & levels,
+                        std::vector<int32_t> & ok, xpg_ctx * c = 0, bool darkshadow = false)
+{
+    const int nb = (int)systems.size();
+    levels.assign((size_t)nb, std::vector<RMatT>());
+    ok.assign((size_t)nb, 0);
+    if ((int)rhs_idx.size() != nb) return XPG_ERR_SHAPE;
+    std::vector<int> live;
+    std::vector<std::vector<int32_t> > lists;
+    for (int b = 0; b < nb; b++) {
+        const int nv = rhs_idx[(size_t)b];
+        if (nv < 1) return XPG_ERR_SHAPE;
+        levels[(size_t)b].resize((size_t)(nv - 1));
+        if (nv == 1 || systems[(size_t)b]->size() == 0) {          // nothing to eliminate, or an empty system: it stays empty
+            for (int k = 0; k + 1 < nv; k++) levels[(size_t)b][(size_t)k].clean();
+            ok[(size_t)b] = 1;
+            continue;
+        }
+        std::vector<int32_t> el;
+        for (int u = nv - 1; u > 0; u--) el.push_back(u);
+        live.push_back(b); lists.push_back(el);
+    }
+    return detail::chain_ragged(true, systems, live, lists, rhs_idx, ok, c ? c : detail::shared_context(), darkshadow,
+                                [&](int i, int k, const xpg_rat32 * a, int r, int cc) { detail::put_cells(levels[(size_t)live[(size_t)i]][(size_t)k], a, r, cc); });
 }
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for many systems: limits[k][j] receives the bounds of variable j of *systems[k]

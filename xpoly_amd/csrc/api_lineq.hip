@@ -241,6 +241,47 @@ int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_r
                              l.p.cap_out };
     return copy_fields(out, n, f);
 }
+// ---- projection / levels of systems of mixed shapes and lists in one launch (lineq_host.hip.h) --------------------------------
+int xpg_lineq_project_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                         const long long * offsets, const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets,
+                                         int darkshadow, int cap_rows, int cap_out_rows, xpg_rat32 * outs, long long outs_cap_cells,
+                                         const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok,
+                                         int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_chain_ragged_packed(ctx, nb, (const R32 *)mats, rows, cols, offsets, rhs_idx, elim, elim_offsets, false, darkshadow, cap_rows,
+                                     cap_out_rows, (R32 *)outs, outs_cap_cells, (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_steps);
+}
+int xpg_lineq_levels_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                        const long long * offsets, const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets,
+                                        int darkshadow, int cap_rows, int cap_out_rows, xpg_rat32 * outs, long long outs_cap_cells,
+                                        const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok,
+                                        int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_chain_ragged_packed(ctx, nb, (const R32 *)mats, rows, cols, offsets, rhs_idx, elim, elim_offsets, true, darkshadow, cap_rows,
+                                     cap_out_rows, (R32 *)outs, outs_cap_cells, (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_steps);
+}
+// what the calling thread's last ragged projection / levels call did (lineq_host.hip.h RaggedRoute)
+int xpg_lineq_ragged_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const RaggedRoute & r = ragged_route();
+    const long long f[7] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.out_bytes };
+    return copy_fields(out, n, f);
+}
+// host-only test view: the plan of a ragged call from its shapes and lists alone (lineq_host.hip.h ragged_chain_plan, the
+// function the launch asks -- the error codes are its own), with the envelope it settles on behind the route's seven figures
+int xpg_test_lineq_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, const int32_t * elim,
+                               const int32_t * elim_offsets, int levels, int cap_rows, int cap_out_rows, long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    RaggedChainPlan p;
+    if (const int rc = ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, levels != 0, cap_rows, cap_out_rows, p)) return rc;
+    const long long f[11] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.cap, p.cap_out,
+                              p.cols, p.rows };
+    return copy_fields(out, n, f);
+}
 // ---- calcBound fused: the bounds of every variable of every system in one launch (lineq_host.hip.h) ---------------------------
 int xpg_lineq_bounds_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx, int cap_rows,
                                         int cap_out_rows, xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,

@@ -29,7 +29,7 @@ struct Scratch {
 enum { SCRATCH_SIX_VC,       // k_six_batch_vc's scratch slots, one per workgroup
        SCRATCH_BATCH_HBM,    // k_batch_hbm's and k_mip_tree_hbm's tableau slots, one per workgroup
        SCRATCH_SIX_VC_HBM,   // k_six_batch_vc_hbm's slots, one per workgroup
-       SCRATCH_LINEQ_PROJECT,   // k_fme_chain_batch's and k_fme_levels_batch's intermediates, two slots per seat
+       SCRATCH_LINEQ_PROJECT,   // k_fme_chain_batch's, k_fme_levels_batch's and k_fme_chain_ragged's intermediates, two slots per seat
        SCRATCH_LINEQ_BOUNDS,    // k_calc_bound_batch's intermediates and held prefix, three slots per seat
        SCRATCH_COUNT };
 }

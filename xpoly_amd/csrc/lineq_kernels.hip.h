@@ -746,6 +746,86 @@ __global__ __launch_bounds__(64) void k_fme_levels_batch(int nb, const R32 * mat
     }
 }
 
+// The two walks above for systems of MIXED shapes and lists in one launch: the statements of a SCoP sit at different depths, so
+// rows, cols, rhs and the list rhs-1 .. 1 differ from system to system. A system is read from its descriptor in device memory
+// instead of from kernel arguments, its list from one concatenated array (no ElimList argument). The walk is unchanged -- a
+// wavefront per system, every step through w_fme_step, intermediates in the LDS result area or in the seat's two alternating
+// slots, seats reused above the grid -- and keeps a loop of its own, so that the two uniform kernels keep their text and their
+// registers (profiles/lineq_ragged_isa.txt).
+//   The LDS block, the seats and cap / cap_lds / cap_out belong to the LAUNCH: sized by the host from the envelope (the widest
+// system's `ecols`, the largest capacity: lineq_host.hip.h ragged_chain_plan), [result area (cap_lds x ecols)] [step input (cap
+// x ecols)] [scratch], each area at the same place for every system. INSIDE an area a system uses its OWN cols as row stride,
+// so its cells -- and with them every loop bound, divisor and result bit -- are those of the uniform kernels; a narrower system
+// leaves the tail of an area unused. cap_lds x ecols >= cap cells, so the row factors of a step fit the result area whatever
+// cols is; a step with need <= cap_lds rows is built in LDS (need x cols <= cap_lds x ecols cells).
+//   Consecutive systems of one wavefront may differ in cols, rows and list. Nothing of the previous system is read: w_load
+// writes the rows x cols cells every later loop is bounded by; w_fme_step writes bad_at, kind[0 .. rows), the row lists, drop[]
+// and the factors before it reads them (a factor only where its own drop[] entry, written in the same pass, says so); w_reduce
+// and w_remove_iden write map[] / removed[] / kind[] for [0, m.r) first. The one read past a live entry -- w_iden_rows' four
+// hashes per trip, up to three behind the last row -- is inside the scratch of cap + 1 entries and cannot change a result
+// (a row's own index is visited after any larger one), whatever an earlier system of another width left there. The scratch
+// itself never moves with cols. The wave_sync that ends a system orders lane 0's verdicts and every lane's LDS reads before the
+// next system's w_load, as in the uniform kernels.
+//   outs: the slot(s) of system b start at cell d.out_off, cap_out x d.cols cells each. KEEP_LEVELS false: one slot, the last
+// step's rows, out_rows[b] (k_fme_chain_batch's verdicts). KEEP_LEVELS true: slot k receives level k and out_rows[d.list_at + k]
+// its count (k_fme_levels_batch's verdicts, the counts of a failed system zeroed in the same way). `need` is judged against
+// the launch's cap / cap_out.
+struct RaggedSys { long long in_off, out_off; int rows, cols, rhs, list_at, list_n, pad; };
+template <bool KEEP_LEVELS>
+__global__ __launch_bounds__(64) void k_fme_chain_ragged(int nb, const RaggedSys * __restrict__ sys, const int * __restrict__ lists,
+                                                         const R32 * mats, int darkshadow, R32 * seats, int cap, int ecols, R32 * outs,
+                                                         int cap_out, int * out_rows, int * out_ok, int * out_steps, int cap_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    // a whole wavefront per system (block (64, 1), what lineq_geom gives fme): the seat is the workgroup, the system index is
+    // uniform and its descriptor comes in as scalars
+    R32 * const res_lds = (R32 *)lds_all;
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * ecols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * ecols), cap);
+    const size_t slot = (size_t)cap * ecols;
+    R32 * const seat = seats + (size_t)blockIdx.x * 2 * slot;
+    LQ_CLEAR
+    for (int b = (int)blockIdx.x; b < nb; b += (int)gridDim.x) {
+        const RaggedSys d = sys[b];
+        const int cols = d.cols, n = d.list_n;
+        const int * const el = lists + d.list_at;
+        WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+        WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
+        w_load(tmp, mats + d.in_off, d.rows, cols);
+        int * const cnt = out_rows + (KEEP_LEVELS ? d.list_at : b);
+        int okv = 1, steps = n, kept = 0, side = 0, k = 0;
+        for (; k < n; k++) {
+            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * slot, cols, d.rhs, el[k], darkshadow, cap, cap_lds, cap, s);
+            wave_sync();
+            if (st.over >= 0) { okv = -st.over; steps = k; break; }
+            if (!st.ok) { okv = 0; steps = k; break; }
+            if (KEEP_LEVELS) {
+                if (res.r > cap_out) { okv = -res.r; steps = k; break; }
+                if (res.r == 0) break;                                  // empty from here on: this and every later level
+                w_store(res, outs + d.out_off + (size_t)k * cap_out * cols);
+                if (lane_id() == 0) cnt[k] = res.r;
+                if (k + 1 == n) { k = n; break; }
+            } else {
+                if (res.r == 0) break;                                  // empty from here on: every later step copies nothing
+                if (k + 1 == n) {
+                    if (res.r > cap_out) okv = -res.r;
+                    else { w_store(res, outs + d.out_off); kept = res.r; }
+                    break;
+                }
+            }
+            w_load(tmp, res.a, res.r, cols);                            // from LDS, or from the side just written
+            if (!st.in_lds) side ^= 1;
+        }
+        if (lane_id() == 0) {
+            if (KEEP_LEVELS) { for (int j = okv == 1 ? k : 0; j < n; j++) cnt[j] = 0; }   // the levels not reached; all after a failure
+            else cnt[0] = kept;
+            out_ok[b] = okv; out_steps[b] = steps;
+        }
+        wave_sync();
+        LQ_FLUSH
+    }
+}
+
 // Lineq::calcBound (linsys.cpp:1047-1078): for every variable j of a system the other rhs - 1 variables eliminated, inner to
 // outer, ALL rhs chains of a system before the wave takes its next system. Chain j is rhs-1 .. j+1, then j-1 .. 0, so every
 // chain starts with a prefix of rhs-1 .. 1: with P_j the system with the variables above j eliminated (P_{rhs-1} the input,
@@ -1269,6 +1349,35 @@ __global__ __launch_bounds__(256) void k_pack_rows(int nb, const R32 * __restric
             if ((cells & 1) && threadIdx.x == 0) dst[cells - 1] = src[cells - 1];
         } else {
             for (size_t t = threadIdx.x; t < cells; t += blockDim.x) dst[t] = src[t];
+        }
+    }
+}
+// The same two for k_fme_chain_ragged's slots, whose rows differ in width: counted and packed in CELLS. Result r of system b
+// is out_rows[d.list_at + k] (levels != 0: one per list entry) or out_rows[b] (one per system).
+// cells[r] = live rows x the system's cols, what k_rows_scan turns into cell offsets.
+__global__ __launch_bounds__(256) void k_ragged_cells(int nb, const RaggedSys * __restrict__ sys, int levels, const int * __restrict__ rows,
+                                                      int * __restrict__ cells)
+{
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += gridDim.x * blockDim.x) {
+        const RaggedSys d = sys[b];
+        const int first = levels ? d.list_at : b, n = levels ? d.list_n : 1;
+        for (int k = 0; k < n; k++) cells[first + k] = rows[first + k] > 0 ? rows[first + k] * d.cols : 0;
+    }
+}
+// The live cells of every slot of system b to packed[off[r] ..], a workgroup per system, cell by cell (a slot starts on any
+// cell: cap_out x cols may be odd).
+__global__ __launch_bounds__(256) void k_pack_ragged(int nb, const RaggedSys * __restrict__ sys, int levels, const R32 * __restrict__ slots,
+                                                     int cap_out, const int * __restrict__ cells, const long long * __restrict__ off,
+                                                     R32 * __restrict__ packed)
+{
+    for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+        const RaggedSys d = sys[b];
+        const int first = levels ? d.list_at : b, n = levels ? d.list_n : 1;
+        for (int k = 0; k < n; k++) {
+            const int c = cells[first + k];
+            const R32 * src = slots + d.out_off + (size_t)k * cap_out * d.cols;
+            R32 * dst = packed + off[first + k];
+            for (int t = threadIdx.x; t < c; t += blockDim.x) dst[t] = src[t];
         }
     }
 }

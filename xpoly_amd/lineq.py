@@ -199,6 +199,72 @@ class Lineq:
             raise ValueError("xpg_lineq_levels_last_route: %d" % rc)
         return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "level_bytes"), (int(x) for x in out)))
 
+    def _chain_ragged(self, levels, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy):
+        """xpg_lineq_{project,levels}_batch_ragged_rat32: (ok[nb], steps[nb], results) with results[r] the rows of result r --
+        one per system, or (levels) one per list entry, level k of system b at elim_offsets[b] + k -- and the offsets of the
+        lists. The rows are cols[b] wide."""
+        from .six import _ragged_pack
+        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
+        nb = len(parts)
+        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
+        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+        if elims is None:                                   # loop-nest limits: rhs_idx - 1 .. 1 of each system
+            elims = [list(range(int(r) - 1, 0, -1)) for r in (rhs if rhs is not None else cols - 1)]
+        if len(elims) != nb or (rhs is not None and rhs.size != nb):
+            raise ValueError("one list and one rhs_idx per system: %d systems, %d lists" % (nb, len(elims)))
+        lists = [np.asarray(e, dtype=np.int32).reshape(-1) for e in elims]
+        eoff = np.zeros(nb + 1, dtype=np.int32)
+        eoff[1:] = np.cumsum([e.size for e in lists])
+        el = np.ascontiguousarray(np.concatenate(lists)) if nb and int(eoff[nb]) else np.zeros(1, dtype=np.int32)
+        nres = int(eoff[nb]) if levels else nb
+        ooff = np.zeros(nres + 1, dtype=np.int64); orows = np.zeros(max(nres, 1), dtype=np.int32)
+        ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, steps, [], eoff
+        name = "xpg_lineq_levels_batch_ragged_rat32" if levels else "xpg_lineq_project_batch_ragged_rat32"
+        view = C.c_void_p()
+        self.ctx.check(getattr(lib(), name)(
+            self.ctx._h, C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs), vp(el), vp(eoff), C.c_int(int(darkshadow)),
+            C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view), vp(ooff), vp(orows), vp(ok),
+            vp(steps)), name)
+        total = int(ooff[nres])
+        if not copy and total:
+            buf = (C.c_int32 * (total * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
+        else:
+            packed = np.empty((total, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        o = ooff.tolist()
+        width = np.repeat(cols, np.diff(eoff)).tolist() if levels else cols.tolist()
+        return ok, steps, [packed[o[r]: o[r + 1]].reshape(-1, width[r], 2) for r in range(nres)], eoff
+
+    def project_ragged(self, mats_list, rhs_idx, elims, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_project_batch_ragged_rat32: Lineq.project_packed for systems of DIFFERENT shapes, each with its own
+        rhs_idx[b] (None: its last column) and its own list elims[b], in ONE launch. Returns (ok[nb], steps[nb], [rows of system
+        b]) with project_packed's verdicts; the capacities are the call's -- cap_rows defaults to fme's worst case for the system
+        with the most rows. copy=False: views of the handle's pinned buffer, valid until the next packed call on this handle."""
+        ok, steps, res, _ = self._chain_ragged(False, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy)
+        return ok, steps, res
+
+    def levels_ragged(self, mats_list, rhs_idx, elims=None, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_levels_batch_ragged_rat32: Lineq.levels_packed for systems of DIFFERENT shapes and depths in ONE launch --
+        the loop-nest limits of a SCoP's statements. elims None: the list rhs_idx[b]-1 .. 1 of each system, as
+        LoopTran::transformIterSpace runs it. Returns (ok[nb], steps[nb], levels) with levels[b][k] the rows of system b once
+        elims[b][0 .. k] are eliminated, and levels_packed's verdicts."""
+        ok, steps, res, eoff = self._chain_ragged(True, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy)
+        e = eoff.tolist()
+        return ok, steps, [res[e[b]: e[b + 1]] for b in range(len(ok))]
+
+    @staticmethod
+    def ragged_last_route():
+        """xpg_lineq_ragged_last_route of the calling thread's last project_ragged / levels_ragged call, as a dict."""
+        out = np.zeros(7, dtype=np.int64)
+        rc = lib().xpg_lineq_ragged_last_route(vp(out), C.c_int(7))
+        if rc != 0:
+            raise ValueError("xpg_lineq_ragged_last_route: %d" % rc)
+        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "out_bytes"), (int(x) for x in out)))
+
     def reduce_ragged(self, mats_list, rhs_idx=None, is_intersect=True):
         """Lineq::reduce on systems of different shapes in one call: (ok[nb], [system b's surviving rows])."""
         from .six import _ragged_pack
