@@ -970,6 +970,42 @@ int xpg_lineq_bounds_last_route(long long * out, int n);
  * asks -- then [7] the cap_rows and [8] the cap_out_rows it settles on.  Fills min(n, 9) entries; XPG_ERR_SHAPE /
  * XPG_ERR_UNSUPPORTED as the call. */
 int xpg_test_lineq_bounds_plan(int nb, int rows, int cols, int rhs_idx, int cap_rows, int cap_out_rows, long long * out, int n);
+/* The fused calcBound for systems of MIXED shapes in ONE launch: the statements of a SCoP sit at different depths, so rows,
+ * cols and rhs_idx differ from statement to statement.  mats holds the systems, system b (rows[b] x cols[b]) at cell
+ * offsets[b]; rhs_idx[b] its constant column (NULL: the last column of each).  Every chain of every system runs in one launch
+ * (one upload, one synchronisation), whose LDS layout and capacities are those of the ENVELOPE -- the widest system's columns,
+ * the most rows -- while each system keeps its own row stride, so its results and verdicts are, bit for bit, those of
+ * xpg_lineq_bounds_batch_packed_rat32 called on its shape class with the same capacities.
+ *   cap_rows      rows an intermediate or a result may have before it is reduced; <= 0: 4 * LARGEST rows[b] + 16
+ *   cap_out_rows  rows of a result's slot; <= 0 (or above cap_rows): cap_rows
+ *   R             the sum of rhs_idx[b]; the bounds of variable j of system b are entry first[b] + j, first[b] the sum of the
+ *                 rhs_idx before b
+ *   out_cell_offsets [R + 1], out_rows [R]: entry r (out_rows[r] rows, its system's cols wide) starts at CELL
+ *                 out_cell_offsets[r] (the convention of xpg_lineq_levels_batch_ragged_rat32)
+ *   out_ok, out_chain, out_steps [nb]: as xpg_lineq_bounds_batch_packed_rat32, `need` judged against the call's cap_rows /
+ *                 cap_out_rows.  A system with out_ok[b] <= 0 contributes no cells; the others are packed all the same.
+ * outs (may be NULL) has room for outs_cap_cells cells, out_view (may be NULL) receives a pointer into the handle's pinned
+ * buffer, valid until the handle's next packed call; neither: a sizing call.  XPG_ERR_SHAPE where outs is too small (offsets,
+ * counts and verdicts are filled).  Decided before anything is launched: XPG_ERR_SHAPE -- nb < 0, rhs_idx[b] outside
+ * [1, cols[b]), rows[b] <= 0, cols[b] <= 1, a missing array; XPG_ERR_UNSUPPORTED -- the envelope's LDS layout over 160 KB,
+ * cap_rows > 32767.  nb == 0: returns 0, out_cell_offsets[0] = 0.  The intermediates' slots are the fused calcBound's
+ * (xpg_trim returns them).  There is no _dev form, as for the ragged projection. */
+int xpg_lineq_bounds_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                        const long long * offsets, const int32_t * rhs_idx, int cap_rows, int cap_out_rows,
+                                        xpg_rat32 * outs, long long outs_cap_cells, const xpg_rat32 ** out_view,
+                                        long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok, int32_t * out_chain,
+                                        int32_t * out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did.  out[0]
+ * launches (1; 0 where nothing was launched), [1] grid, [2] systems per workgroup, [3] LDS bytes per workgroup, [4] rows of the
+ * LDS result area, [5] bytes of intermediate slots (grid x 3 x cap_rows x widest cols x 8), [6] bytes of output slots
+ * (rhs_idx[b] x cap_out_rows x cols[b] x 8 per system), [7] elimination steps of the batch, the sum of
+ * (rhs_idx[b] - 1)(rhs_idx[b] + 2) / 2.  Fills min(n, 8) entries. */
+int xpg_lineq_bounds_ragged_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same eight figures from the shapes alone -- the function the launch itself
+ * asks, with its error codes -- then [8] the cap_rows, [9] the cap_out_rows, [10] the columns and [11] the rows of the
+ * envelope.  Fills min(n, 12) entries. */
+int xpg_test_lineq_bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows,
+                                      int cap_out_rows, long long * out, int n);
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank);
 int xpg_rat_rank_batch(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols,
                        int32_t * out_rank);

@@ -695,6 +695,7 @@ inline int levels_nests(const std::vector<RMatT *> & systems, const std::vector<
 // shape class (SCoPs have a handful), xpg_lineq_bounds_batch_packed_rat32: every elimination chain of a class in one launch.
 // A class one of whose systems needs more rows than the capacity tried is called again with the largest need the library
 // reports, at most three times; still short: XPG_ERR_UNSUPPORTED, never a silent ok = 0. Returns 0 or XPG_ERR_*.
+// (Systems of MIXED shapes in one call and one launch: calc_bound_each, below.)
 template <class RMatT>
 inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vector<int32_t> & rhs_idx,
                           std::vector<std::vector<RMatT> > & limits, std::vector<int32_t> & ok, xpg_ctx * c = 0)
@@ -746,6 +747,71 @@ inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vecto
         if (!answered) return XPG_ERR_UNSUPPORTED;
     }
     return 0;
+}
+
+// calc_bound_all for systems of MIXED shapes in ONE call: the same arguments, limits and ok, but every system -- whatever its
+// rows, columns and rhs_idx -- is packed once and goes up in one xpg_lineq_bounds_batch_ragged_rat32 call: one upload, one
+// launch, one synchronisation instead of one of each per shape class. The capacities are the call's (the library's default,
+// 4 * most rows + 16, first). Where a system reports -need the call is made again with the largest need reported -- above the
+// capacity tried: a step's unreduced rows, cap_rows; else an output slot, cap_out_rows -- at most three times; still short:
+// XPG_ERR_UNSUPPORTED, never a silent ok = 0. Returns 0 or XPG_ERR_*.
+template <class RMatT>
+inline int calc_bound_each(const std::vector<RMatT *> & systems, const std::vector<int32_t> & rhs_idx,
+                           std::vector<std::vector<RMatT> > & limits, std::vector<int32_t> & ok, xpg_ctx * c = 0)
+{
+    const int nb = (int)systems.size();
+    if ((int)rhs_idx.size() != nb) return XPG_ERR_SHAPE;
+    limits.assign((size_t)nb, std::vector<RMatT>());
+    ok.assign((size_t)nb, 0);
+    if (nb == 0) return 0;
+    xpg_ctx * h = c ? c : detail::shared_context();
+    std::vector<int32_t> rows((size_t)nb), cols((size_t)nb);
+    std::vector<long long> off((size_t)nb + 1, 0);
+    std::vector<int> first((size_t)nb + 1, 0);
+    int most = 0;
+    for (int b = 0; b < nb; b++) {
+        rows[(size_t)b] = (int32_t)systems[(size_t)b]->get_row_size(); cols[(size_t)b] = (int32_t)systems[(size_t)b]->get_col_size();
+        const int nv = rhs_idx[(size_t)b];
+        if (rows[(size_t)b] == 0 || cols[(size_t)b] == 0 || nv < 1 || nv >= cols[(size_t)b]) return XPG_ERR_SHAPE;
+        off[(size_t)b + 1] = off[(size_t)b] + (long long)rows[(size_t)b] * cols[(size_t)b];
+        first[(size_t)b + 1] = first[(size_t)b] + nv;
+        if (rows[(size_t)b] > most) most = rows[(size_t)b];
+    }
+    std::vector<xpg_rat32> flat((size_t)off[(size_t)nb]);
+    for (int b = 0; b < nb; b++)
+        std::memcpy((void *)(flat.data() + off[(size_t)b]), (const void *)systems[(size_t)b]->get_matrix(),
+                    sizeof(xpg_rat32) * (size_t)rows[(size_t)b] * cols[(size_t)b]);
+    const int nres = first[(size_t)nb];
+    int cap = 4 * most + 16, cap_out = cap;                         // the library's defaults, spelled out
+    for (int attempt = 0; attempt < 3; attempt++) {
+        std::vector<long long> ooff((size_t)nres + 1, 0);
+        std::vector<int32_t> orows((size_t)nres, 0), kok((size_t)nb, 0), kchain((size_t)nb, 0), ksteps((size_t)nb, 0);
+        const xpg_rat32 * view = 0;
+        const int rc = xpg_lineq_bounds_batch_ragged_rat32(h, nb, flat.data(), rows.data(), cols.data(), off.data(), rhs_idx.data(), cap, cap_out,
+                                                           (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), kchain.data(),
+                                                           ksteps.data());
+        if (rc != 0) return rc;
+        int need_cap = 0, need_out = 0;
+        for (int b = 0; b < nb; b++) {
+            const int need = -kok[(size_t)b];
+            if (need > cap) { if (need > need_cap) need_cap = need; }
+            else if (need > need_out) need_out = need;              // (need <= 0: the system was answered)
+        }
+        if (need_cap) { cap = need_cap; cap_out = cap; }            // (a result's slot takes cap, as in calc_bound_all)
+        else if (need_out) cap_out = need_out;
+        if (need_cap || need_out) continue;
+        for (int b = 0; b < nb; b++) {
+            const int nv = rhs_idx[(size_t)b];
+            ok[(size_t)b] = kok[(size_t)b];
+            limits[(size_t)b].resize((size_t)nv);
+            for (int j = 0; j < nv; j++) {
+                const int r = first[(size_t)b] + j;
+                detail::put_cells(limits[(size_t)b][(size_t)j], view ? view + ooff[(size_t)r] : view, (int)orows[(size_t)r], (int)cols[(size_t)b]);
+            }
+        }
+        return 0;
+    }
+    return XPG_ERR_UNSUPPORTED;
 }
 
 } // namespace xpoly_amd

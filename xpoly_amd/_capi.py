@@ -51,6 +51,7 @@ SYMBOLS = [
     "xpg_test_lineq_levels_plan",
     "xpg_lineq_project_batch_ragged_rat32", "xpg_lineq_levels_batch_ragged_rat32", "xpg_lineq_ragged_last_route",
     "xpg_test_lineq_ragged_plan",
+    "xpg_lineq_bounds_batch_ragged_rat32", "xpg_lineq_bounds_ragged_last_route", "xpg_test_lineq_bounds_ragged_plan",
 ]
 
 _lib = None

@@ -317,6 +317,36 @@ int xpg_test_lineq_bounds_plan(int nb, int rows, int cols, int rhs_idx, int cap_
     const long long f[9] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, p.steps, p.cap, p.cap_out };
     return copy_fields(out, n, f);
 }
+// ---- calcBound fused for systems of mixed shapes in one launch (lineq_host.hip.h) ---------------------------------------------
+int xpg_lineq_bounds_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
+                                        const long long * offsets, const int32_t * rhs_idx, int cap_rows, int cap_out_rows, xpg_rat32 * outs,
+                                        long long outs_cap_cells, const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows,
+                                        int32_t * out_ok, int32_t * out_chain, int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_bounds_ragged_packed(ctx, nb, (const R32 *)mats, rows, cols, offsets, rhs_idx, cap_rows, cap_out_rows, (R32 *)outs, outs_cap_cells,
+                                      (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_chain, out_steps);
+}
+// what the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did (lineq_host.hip.h BoundsRaggedRoute)
+int xpg_lineq_bounds_ragged_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const BoundsRaggedRoute & r = bounds_ragged_route();
+    const long long f[8] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.out_bytes, r.steps };
+    return copy_fields(out, n, f);
+}
+// host-only test view: the plan of a ragged calcBound call from its shapes alone (lineq_host.hip.h bounds_ragged_plan, the
+// function the launch asks -- the error codes are its own), with the envelope it settles on behind the route's eight figures
+int xpg_test_lineq_bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows,
+                                      int cap_out_rows, long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    BoundsRaggedPlan p;
+    if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
+    const long long f[12] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps, p.cap,
+                              p.cap_out, p.cols, p.rows };
+    return copy_fields(out, n, f);
+}
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank)
 {
     XPG_BIND(ctx); return rat_rank_batch_dev(ctx, nb, (const R32 *)d_mats, rows, cols, d_out_rank); }

@@ -882,6 +882,169 @@ inline int lineq_bounds_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, in
     return rc;
 }
 
+// ---- calcBound fused for systems of MIXED shapes: one launch of k_calc_bound_ragged -------------------------------------------
+// THE plan of a ragged calcBound call (the launch and xpg_test_lineq_bounds_ragged_plan both ask it), decided before anything
+// is launched: every system under bounds_plan's shape rules, then the ENVELOPE -- the widest system's cols, the most rows --
+// under bounds_plan's capacity rules (cap_rows <= 0: 4 * most rows + 16; three slots per seat), so that a batch whose shapes
+// all agree gets exactly the uniform plan. The output slots follow the systems, cap_out x OWN cols cells per variable; `steps`
+// is the sum over the systems. rhs_idx NULL: the last column of each system.
+struct BoundsRaggedPlan { int cols, rows, cap, cap_out, cap_lds; LineqGeom q; long long seats, slots, steps; size_t seat_bytes, out_bytes; };
+inline int bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows, int cap_out_rows,
+                              BoundsRaggedPlan & p)
+{
+    if (nb <= 0 || !rows || !cols) return XPG_ERR_SHAPE;
+    long long cells = 0;
+    p.cols = 0; p.rows = 0; p.slots = 0; p.steps = 0;
+    for (int b = 0; b < nb; b++) {
+        const int rhs = rhs_idx ? rhs_idx[b] : cols[b] - 1;
+        if (rows[b] <= 0 || cols[b] <= 1 || rhs < 1 || rhs >= cols[b]) return XPG_ERR_SHAPE;
+        if (cols[b] > p.cols) p.cols = cols[b];
+        if (rows[b] > p.rows) p.rows = rows[b];
+        cells += (long long)rhs * cols[b];
+        p.slots += rhs;
+        p.steps += (long long)(rhs - 1) * (rhs + 2) / 2;
+    }
+    if (p.rows > 32767) return XPG_ERR_UNSUPPORTED;                            // (cap >= rows: refused below in any case)
+    p.cap = cap_rows <= 0 ? 4 * p.rows + 16 : cap_rows;
+    if (p.cap < p.rows) p.cap = p.rows;
+    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
+    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
+    const FmeLds fl = fme_lds(p.cap, p.cap, p.cols);
+    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    if (p.slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    p.cap_lds = fl.cap_lds;
+    p.q = lineq_geom(nb, 64, fl.lds);
+    if (p.q.G != 1) return XPG_ERR_UNSUPPORTED;                                // (the kernel's seat is the workgroup: fme's whole wave)
+    p.seats = (long long)p.q.grid * p.q.G;
+    p.seat_bytes = (size_t)p.seats * 3 * (size_t)p.cap * p.cols * 8;
+    p.out_bytes = (size_t)cells * (size_t)p.cap_out * 8;
+    return 0;
+}
+// What the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did (xpg_lineq_bounds_ragged_last_route): launches
+// of k_calc_bound_ragged (1), its grid, systems per workgroup, LDS bytes per system, cap_lds, bytes of seat slots, bytes of
+// output slots, elimination steps of the whole batch.
+struct BoundsRaggedRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, out_bytes, steps; };
+inline BoundsRaggedRoute & bounds_ragged_route() { static thread_local BoundsRaggedRoute r = {0, 0, 0, 0, 0, 0, 0, 0}; return r; }
+// Host arrays with a PACKED result in CELLS, lineq_chain_ragged_packed step for step: out_cell_offsets [R + 1] and out_rows [R],
+// R the sum of the rhs, variable j of system b at first[b] + j (first[b] the sum of the rhs before b). ONE upload (descriptors
+// and the systems gathered into one block of the handle's pinned buffer), ONE launch, one synchronisation before the rows
+// travel: small slots come down with the counts and are packed here; else k_ragged_cells / k_rows_scan give the offsets under
+// that synchronisation and k_pack_ragged sends the live cells alone (both in their levels mode: the descriptor's list_at /
+// list_n carry first[b] / rhs). A system with out_ok <= 0 contributes no cells, the others are packed all the same.
+// XPG_ERR_SHAPE where `outs` holds fewer than out_cell_offsets[R] cells (offsets, counts and verdicts are filled); neither
+// outs nor view: a sizing call.
+inline int lineq_bounds_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * rows, const int32_t * cols, const long long * offsets,
+                                      const int32_t * rhs_idx, int cap_rows, int cap_out_rows, R32 * outs, long long outs_cap_cells,
+                                      const R32 ** view, long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok,
+                                      int32_t * out_chain, int32_t * out_steps)
+{
+    if (view) *view = 0;
+    bounds_ragged_route() = BoundsRaggedRoute{0, 0, 0, 0, 0, 0, 0, 0};
+    if (nb < 0 || !out_cell_offsets) return XPG_ERR_SHAPE;
+    if (nb == 0) { out_cell_offsets[0] = 0; return 0; }
+    BoundsRaggedPlan p;
+    if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
+    if (!ctx || !mats || !offsets || !out_rows || !out_ok || !out_chain || !out_steps || (outs && outs_cap_cells < 0)) return XPG_ERR_SHAPE;
+    for (int b = 0; b < nb; b++) if (offsets[b] < 0) return XPG_ERR_SHAPE;
+    const int nres = (int)p.slots;
+    // the block that goes up: [descriptors][systems, back to back]
+    const size_t b_desc = (size_t)nb * sizeof(RaggedSys);
+    size_t in_cells = 0;
+    for (int b = 0; b < nb; b++) in_cells += (size_t)rows[b] * cols[b];
+    const size_t b_up = b_desc + in_cells * 8, up_al = (b_up + 255) & ~(size_t)255;
+    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 4 + (size_t)nb * 12;     // cell offsets, then rows, ok, chain and steps
+    const size_t meta_al = (meta + 255) & ~(size_t)255, b_ints = (size_t)(nres + 3 * (size_t)nb) * 4;
+    const size_t bo = p.out_bytes;
+    const bool small_out = bo <= ((size_t)512 << 10);
+    DevBuf dup, dout, dints, dcells, doff;                           // dints: rows [nres], ok [nb], chain [nb], steps [nb]
+    XPG_TRY(dup.alloc(ctx, b_up)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dints.alloc(ctx, b_ints));
+    XPG_TRY(dcells.alloc(ctx, (size_t)nres * 4)); XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
+    Scratch & seats = ctx->scratch[SCRATCH_LINEQ_BOUNDS];
+    if (const int rc = scratch_reserve(ctx, seats, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_bounds_ragged seats)")) return rc;
+    int rc = hpack_reserve(ctx, meta_al + up_al + (small_out ? bo : 0));
+    if (rc) return rc;
+    char * hp = hpack_buf(ctx, false);
+    char * hup = hp + meta_al;
+    RaggedSys * hd = (RaggedSys *)hup;
+    long long in_at = 0, out_at = 0;
+    int first = 0;
+    for (int b = 0; b < nb; b++) {
+        const int rhs = rhs_idx ? rhs_idx[b] : cols[b] - 1;
+        const size_t c = (size_t)rows[b] * cols[b];
+        hd[b] = RaggedSys{in_at, out_at, rows[b], cols[b], rhs, first, rhs, 0};
+        memcpy(hup + b_desc + (size_t)in_at * 8, (const void *)(mats + offsets[b]), c * 8);
+        in_at += (long long)c;
+        out_at += (long long)rhs * p.cap_out * cols[b];
+        first += rhs;
+    }
+    XPG_TRY(hipMemcpyAsync(dup.p, hup, b_up, hipMemcpyHostToDevice, ctx->stream));
+    const RaggedSys * d_sys = (const RaggedSys *)dup.p;
+    const R32 * d_mats = (const R32 *)((char *)dup.p + b_desc);
+    int * d_rows = (int *)dints.p, * d_ok = d_rows + nres, * d_chain = d_ok + nb, * d_steps = d_chain + nb;
+    XPG_TRY(lds_limit((const void *)k_calc_bound_ragged, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_sys, d_mats, (R32 *)seats.buf, p.cap, p.cols,
+                       (R32 *)dout.p, p.cap_out, d_rows, d_ok, d_chain, d_steps, p.cap_lds);
+    XPG_TRY(hipGetLastError());
+    bounds_ragged_route() = BoundsRaggedRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps};
+    // the way down
+    long long * h_off = (long long *)hp;
+    int32_t * h_ints = (int32_t *)(hp + (size_t)(nres + 1) * 8);     // rows, ok, chain, steps as on the device
+    XPG_TRY(hipMemcpyAsync(h_ints, dints.p, b_ints, hipMemcpyDeviceToHost, ctx->stream));
+    const auto verdicts_out = [&]() {
+        memcpy(out_rows, h_ints, (size_t)nres * 4); memcpy(out_ok, h_ints + nres, (size_t)nb * 4);
+        memcpy(out_chain, h_ints + nres + nb, (size_t)nb * 4); memcpy(out_steps, h_ints + nres + 2 * (size_t)nb, (size_t)nb * 4);
+    };
+    if (small_out) {
+        char * hs = hup + up_al;
+        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        verdicts_out();
+        long long tot = 0;
+        for (int b = 0; b < nb; b++)
+            for (int j = 0, f = hd[b].list_at; j < hd[b].list_n; j++) { out_cell_offsets[f + j] = tot; tot += (long long)out_rows[f + j] * cols[b]; }
+        out_cell_offsets[nres] = tot;
+        if (outs && outs_cap_cells < tot) return XPG_ERR_SHAPE;
+        for (int b = 0; b < nb; b++)                                 // forward moves: a destination never lies above its source
+            for (int j = 0, f = hd[b].list_at; j < hd[b].list_n; j++) {
+                const char * src = hs + ((size_t)hd[b].out_off + (size_t)j * p.cap_out * cols[b]) * 8;
+                const size_t nbytes = (size_t)(out_cell_offsets[f + j + 1] - out_cell_offsets[f + j]) * 8;
+                if (outs) memcpy((char *)outs + (size_t)out_cell_offsets[f + j] * 8, src, nbytes);
+                if (view) memmove(hs + (size_t)out_cell_offsets[f + j] * 8, src, nbytes);
+            }
+        if (view && tot > 0) *view = (const R32 *)hs;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_ragged_cells, dim3((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024), dim3(256), 0, ctx->stream, nb, d_sys, 1,
+                       (const int *)d_rows, (int *)dcells.p);
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)dcells.p, (long long *)doff.p);
+    XPG_TRY(hipGetLastError());
+    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipStreamSynchronize(ctx->stream));
+    verdicts_out();
+    memcpy(out_cell_offsets, h_off, (size_t)(nres + 1) * 8);
+    const long long total = out_cell_offsets[nres];
+    if (outs && outs_cap_cells < total) return XPG_ERR_SHAPE;
+    if (total == 0 || (!outs && !view)) return 0;                    // (neither: a sizing call)
+    const size_t bp = (size_t)total * 8;
+    DevBuf dpk;
+    XPG_TRY(dpk.alloc(ctx, bp));
+    hipLaunchKernelGGL(k_pack_ragged, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, d_sys, 1, (const R32 *)dout.p, p.cap_out,
+                       (const int *)dcells.p, (const long long *)doff.p, (R32 *)dpk.p);
+    XPG_TRY(hipGetLastError());
+    if (view) {                                                      // into pinned memory; the caller's copy, if any, from there
+        if ((rc = hpack_reserve(ctx, bp))) return rc;
+        char * hv = hpack_buf(ctx, false);
+        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        if (outs) memcpy(outs, hv, bp);
+        *view = (const R32 *)hv;
+    } else {
+        XPG_TRY(hipMemcpyAsync(outs, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
+
 // Matrix<Rational>::rank on device arrays, enqueue only: d_rank [nb].
 inline int rat_rank_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int32_t * d_rank)
 {

@@ -911,6 +911,102 @@ __global__ __launch_bounds__(64) void k_calc_bound_batch(int nb, const R32 * mat
     }
 }
 
+// k_calc_bound_batch's walk for systems of MIXED shapes in one launch: the statements of a SCoP sit at different depths, so
+// rows, cols and rhs differ from system to system. The walk is the uniform kernel's, statement for statement -- the prefixes
+// P_j walked once, the tail per variable, the hold slot and the two sides, the verdict of the lowest failing chain, one call
+// site of w_fme_step for tail and prefix -- in a kernel of its own, so that the uniform kernel keeps its text and its registers
+// (profiles/lineq_bounds_ragged_isa.txt). The addressing is k_fme_chain_ragged's: block (64, 1), the seat is the workgroup, the
+// system index is uniform and its descriptor (RaggedSys; there is no list, so list_at carries the FIRST RESULT INDEX of the
+// system, the sum of the rhs before it, and list_n its rhs: k_ragged_cells / k_pack_ragged serve in their levels mode) comes in
+// as scalars. The LDS block, the seats and cap / cap_lds / cap_out belong to the LAUNCH (lineq_host.hip.h bounds_ragged_plan):
+// [result area (cap_lds x ecols)] [step input (cap x ecols)] [scratch], a seat THREE slots of cap x ecols cells (sides 0 and 1,
+// then the hold slot). INSIDE an area or a slot a system uses its OWN cols as row stride, so every cell, loop bound and result
+// bit is the uniform kernel's; cap rows x cols <= cap x ecols cells, so nothing a step may build (need <= cap, else a verdict
+// before any row is written past nfree <= rows <= cap) leaves its slot.
+//   Consecutive systems of one wavefront differ in rows, cols and rhs. What k_fme_chain_ragged's comment says of w_load,
+// w_fme_step, w_reduce / w_remove_iden and w_iden_rows' read behind the last row holds here unchanged, for they are the only
+// helpers called. The hold slot adds one thing to check: it is READ only where `held` is true, and `held` starts false with
+// every system and becomes true only after this system's own prefix step has put res.r rows x OWN cols there (built in place,
+// or w_store from LDS) -- pj_rows is that res.r, so the load reads exactly the cells written, never those of an earlier
+// system of another width. The sides are read (w_load from res.a) only in the step after the one that wrote them. fin_res /
+// fin_r / tok are reset per chain as in the uniform kernel.
+//   outs: result j of system b in its own slot of cap_out x cols cells at d.out_off + j * cap_out * cols; out_rows[first + j]
+// its count; out_ok / out_chain / out_steps [nb], k_calc_bound_batch's verdicts with `need` judged against the launch's cap /
+// cap_out; the counts of a failed system zeroed in the same way. rhs == 1: no step, the one result is the input, unreduced.
+__global__ __launch_bounds__(64) void k_calc_bound_ragged(int nb, const RaggedSys * __restrict__ sys, const R32 * mats, R32 * seats, int cap,
+                                                          int ecols, R32 * outs, int cap_out, int * out_rows, int * out_ok, int * out_chain,
+                                                          int * out_steps, int cap_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    R32 * const res_lds = (R32 *)lds_all;
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * ecols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * ecols), cap);
+    const int slot = cap * ecols;                                       // (cells; the LDS layout holds as many, so they fit an int)
+    R32 * const seat = seats + (size_t)blockIdx.x * 3 * slot;           // sides 0 and 1, then the hold slot
+    LQ_CLEAR
+    for (int b = (int)blockIdx.x; b < nb; b += (int)gridDim.x) {
+        const RaggedSys d = sys[b];
+        const int cols = d.cols, rhs = d.rhs;
+        const R32 * const in = mats + d.in_off;
+        int * const cnt = out_rows + d.list_at;
+        WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+        WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
+        bool held = false;                                              // P_j: the input, then the hold slot
+        int pj_rows = d.rows;
+        int okv = 1, chain = -1, steps = 0, side = 0;
+        bool walk = true;
+        for (int j = rhs - 1; j >= 0 && walk; j--) {
+            w_load(tmp, held ? seat + 2 * slot : in, pj_rows, cols);
+            bool fin_res = false;                                       // no step (j == 0, or P_j empty): P_j itself, unreduced
+            int fin_r = pj_rows;
+            int tok = 1, tstep = 0;
+            // t < j: step t of chain j's tail, u = j-1-t; t == j: the tail is stored, then the prefix step u = j (one call site
+            // of the step for both, as in k_calc_bound_batch)
+            for (int t = 0; t <= j; t++) {
+                const bool prefix = t == j;
+                if (prefix) {
+                    int kept = 0;
+                    if (tok == 1) {
+                        R32 * const dst = outs + d.out_off + (size_t)j * cap_out * cols;
+                        if (fin_r > cap_out) { tok = -fin_r; tstep = rhs - 1; }
+                        else { if (fin_res) w_store(res, dst); else w_store(tmp, dst); kept = fin_r; }
+                    }
+                    if (tok != 1) { okv = tok; chain = j; steps = tstep; }
+                    if (lane_id() == 0) cnt[j] = kept;
+                    wave_sync();
+                    if (j == 0 || pj_rows == 0) break;                  // (an empty prefix stays empty)
+                    // P_j again: the tail's first step normalised it in place
+                    w_load(tmp, held ? seat + 2 * slot : in, pj_rows, cols);
+                } else if (tok != 1 || fin_r == 0) continue;            // (empty from here on: every later step copies nothing)
+                const int u = prefix ? j : j - 1 - t;
+                const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (prefix ? 2 : side) * slot, cols, rhs, u, 0, cap, cap_lds, cap, s);
+                wave_sync();
+                if (st.over >= 0 || !st.ok) {
+                    const int v = st.over >= 0 ? -st.over : 0;
+                    if (prefix) { okv = v; chain = 0; steps = rhs - 1 - j; walk = false; }
+                    else { tok = v; tstep = rhs - 2 - u; }
+                } else if (prefix) {
+                    if (st.in_lds) w_store(res, seat + 2 * slot);       // else it was built there
+                    held = true; pj_rows = res.r;
+                    wave_sync();
+                } else {
+                    fin_res = true; fin_r = res.r;
+                    if (u > 0 && res.r > 0) {
+                        w_load(tmp, res.a, res.r, cols);                // from LDS, or from the side just written
+                        if (!st.in_lds) side ^= 1;
+                    }
+                }
+            }
+        }
+        if (lane_id() == 0) {                                           // (lane 0 wrote the counts: its stores keep their order)
+            if (okv != 1) for (int j = 0; j < rhs; j++) cnt[j] = 0;
+            out_ok[b] = okv; out_chain[b] = chain; out_steps[b] = steps;
+        }
+        wave_sync();
+        LQ_FLUSH
+    }
+}
+
 // ---- Gauss-Jordan family: rank / det / inv, one wave per matrix -----------------------------------
 __device__ inline R32 abs_r(R32 v) { return lt(v, R32(0, 1)) ? neg(v) : v; }          // matt.h:206-212
 

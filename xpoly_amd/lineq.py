@@ -386,6 +386,51 @@ class Lineq:
             raise ValueError("xpg_lineq_bounds_last_route: %d" % rc)
         return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "steps"), (int(x) for x in out)))
 
+    def bounds_ragged(self, mats_list, rhs_idx=None, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_bounds_batch_ragged_rat32: Lineq.bounds_packed for systems of DIFFERENT shapes, each with its own rhs_idx[b]
+        (None: its last column), in ONE launch -- the bounds of every variable of a SCoP's statements. Returns (ok[nb], chain[nb],
+        steps[nb], bounds) with bounds[b][j] the rows x cols[b] x 2 bounds of variable j of system b and bounds_packed's verdicts;
+        the capacities are the call's -- cap_rows defaults to 4 * (most rows) + 16. copy=False: views of the handle's pinned
+        buffer, valid until the next packed call on this handle."""
+        from .six import _ragged_pack
+        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
+        nb = len(parts)
+        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
+        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+        if rhs is not None and rhs.size != nb:
+            raise ValueError("one rhs_idx per system: %d systems, %d rhs_idx" % (nb, rhs.size))
+        first = np.zeros(nb + 1, dtype=np.int64)
+        first[1:] = np.cumsum(rhs if rhs is not None else cols - 1)
+        nres = max(int(first[nb]), 0)
+        ooff = np.zeros(nres + 1, dtype=np.int64); orows = np.zeros(max(nres, 1), dtype=np.int32)
+        ok = np.zeros(nb, dtype=np.int32); chain = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, chain, steps, []
+        view = C.c_void_p()
+        self.ctx.check(lib().xpg_lineq_bounds_batch_ragged_rat32(
+            self.ctx._h, C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0),
+            None, C.c_longlong(0), C.byref(view), vp(ooff), vp(orows), vp(ok), vp(chain), vp(steps)),
+            "xpg_lineq_bounds_batch_ragged_rat32")
+        total = int(ooff[nres])
+        if not copy and total:
+            buf = (C.c_int32 * (total * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
+        else:
+            packed = np.empty((total, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        o = ooff.tolist(); f = first.tolist(); w = cols.tolist()
+        return ok, chain, steps, [[packed[o[r]: o[r + 1]].reshape(-1, w[b], 2) for r in range(f[b], f[b + 1])] for b in range(nb)]
+
+    @staticmethod
+    def bounds_ragged_last_route():
+        """xpg_lineq_bounds_ragged_last_route of the calling thread's last bounds_ragged call, as a dict."""
+        out = np.zeros(8, dtype=np.int64)
+        rc = lib().xpg_lineq_bounds_ragged_last_route(vp(out), C.c_int(8))
+        if rc != 0:
+            raise ValueError("xpg_lineq_bounds_ragged_last_route: %d" % rc)
+        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "out_bytes", "steps"), (int(x) for x in out)))
+
     def rank(self, mats):
         a = _stack(mats)
         nb, rows, cols = a.shape[:3]
