@@ -139,10 +139,11 @@ int  xpg_lp_chain_aborts(xpg_lp * lp, unsigned * aborts, int * chain_off, unsign
 /* ... and how many of the launches that passed did their batch's first stage themselves (no pick / prep launches for it). */
 int  xpg_lp_chain_folds(xpg_lp * lp, unsigned * folds);
 /* Which loop and which kernel instances the handle runs the LP in its current shape with (evidence for bench.py's `shapes`
- * leg; no reference counterpart).  out[0..n-1], n <= 10: loop (0 pipelined, 3 blocked), pivots per blocked pass,
+ * leg; no reference counterpart).  out[0..n-1], n <= 11: loop (0 pipelined, 3 blocked), pivots per blocked pass,
  * chain form (0 launch-per-stage kernels, 1 one persistent launch on one XCD, 2 the same spread over the chip), columns of
  * the entering column's line kept in LDS (0 / 8 / 16), rows per workgroup of the pass (16 / 32), leading dimension, chain
- * workers, pick workers, prep workers, LDS bytes per chain worker. */
+ * workers, pick workers, prep workers, LDS bytes per chain worker, and for a Rational handle the loop its last iterations
+ * ran on (0 none yet, 1 one launch per pivot, 2 two launches per pivot: what xpg_test_r32_loop_plan names for its shape). */
 int  xpg_lp_loop_info(xpg_lp * lp, int32_t * out, int n);
 /* Test view: SIX::normalize (src/com/lpsol.h:1290-1394, convertEq2Ineq :1197-1278) made both ways for one input -- the cells
  * the HBM route makes on the device (out_dev_cells) and the cells the LDS route makes on the host (out_host_cells), each
@@ -158,6 +159,13 @@ int  xpg_test_normalize(xpg_ctx * ctx, int kind, const void * tgtf, const void *
  * tableau of W live columns gets. */
 int  xpg_test_sweep_tile(int strips, int rowblocks, int rev, int lid, int * bx, int * by);
 int  xpg_test_pick_ld(int W);
+/* The launch rules of the two HBM-resident Rational loops for a tableau of m rows and W columns, host-side view for tests (no
+ * device needed): forced = 0 (XPG_R32_LOOP unset), 1 (=fused), 2 (=pipe).  out[0..n-1], n <= 11: loop taken (1 the
+ * one-launch-per-pivot loop, 0 the two-launch loop); of the fused launch: pick workgroups N, stager workgroups NP, grid x,
+ * grid y, rows per pick lane ceil(m / (64 N)); of the two-launch loop's sweep launch: pick workgroups N, column blocks (the
+ * staging launch's grid), grid x, grid y, rows per pick lane ceil(m / (256 N)).  XPG_ERR_SHAPE for m or W <= 0 or another
+ * forced. */
+int  xpg_test_r32_loop_plan(int m, int W, int forced, int32_t * out, int n);
 /* The device's canonical rational forms on n host triples (tests: the sweep's fused a + k * e and the ratio test's
  * b / a must equal the reference's two operations, src/com/rational.cpp:273-397, for canonical operands -- lowest
  * terms, den > 0, below the appro threshold; anything else in the inputs returns XPG_ERR_SHAPE):

@@ -369,6 +369,14 @@ int xpg_test_sweep_tile(int strips, int rowblocks, int rev, int lid, int * bx, i
     return live ? 1 : 0;
 }
 int xpg_test_pick_ld(int W) { return W > 0 ? pick_ld(W) : XPG_ERR_SHAPE; }
+// r32_loop_plan (lp_host.hip.h) for a Rational tableau of m x W: forced = 0 no XPG_R32_LOOP, 1 "fused", 2 "pipe".
+int xpg_test_r32_loop_plan(int m, int W, int forced, int32_t * out, int n)
+{
+    if (!out || n < 0 || m <= 0 || W <= 0 || forced < R32_FORCE_NONE || forced > R32_FORCE_PIPE) return XPG_ERR_SHAPE;
+    const R32LoopPlan p = r32_loop_plan(m, W, forced);
+    const int32_t f[11] = { p.fused, p.fN, p.fNP, p.fgx, p.fgy, p.frows, p.pN, p.pNP, p.pgx, p.pgy, p.prows };
+    return copy_fields(out, n, f);
+}
 } // extern "C"
 namespace xpg { namespace {
 __global__ __launch_bounds__(256) void k_test_canon_ops(int n, const R32 * a, const R32 * k, const R32 * e, R32 * out_fma, R32 * out_div)
@@ -450,7 +458,7 @@ int xpg_lp_chain_aborts(xpg_lp * lp, unsigned * aborts, int * chain_off, unsigne
 int xpg_lp_loop_info(xpg_lp * lp, int32_t * out, int n)
 {
     if (!lp || !lp->impl || !out || n < 0) return XPG_ERR_SHAPE;
-    int32_t f[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int32_t f[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (lp->impl->kind == 0) ((Lp<F64> *)lp->impl)->loop_info(f);
     else ((Lp<R32> *)lp->impl)->loop_info(f);
     return copy_fields(out, n, f);

@@ -57,11 +57,40 @@ template <> inline void launch_pipe_sweep<F64>(xpg_ctx * ctx, const LpView<F64> 
                           (const double *)v.colbuf + (size_t)slot * colstride);
     if (timed) ctx->prof_n++;
 }
+// The launch rules of the two HBM-resident Rational loops -- decided in ONE place: launch_fused<R32> and
+// launch_pipe_sweep<R32> launch what it says, Lp::queue_iterations asks it which loop a tableau takes, xpg_test_r32_loop_plan
+// shows it to the CPU tests (tests/r32_loop_cases.py mirrors it).
+//   loop     the fused loop where it pays -- 350 000 .. 5 000 000 cells, see queue_iterations -- or where XPG_R32_LOOP=fused
+//            forces it; XPG_R32_LOOP=pipe forces the two-launch loop whatever the size
+//   fused    N one-wave pick workgroups (64 rows each, at most PICK_MAX_WGS), NP stager workgroups (256 columns each), grid
+//            (max(m, N + NP), 1 + NP); a pick lane walks rows p * 64 + tid, + 64 N, ...: ceil(m / (64 N)) of them at most
+//   pipe     N pick workgroups of 256 rows, grid (max(m, N), 1 + column blocks), ceil(m / (256 N)) rows per pick lane
+enum { R32_FORCE_NONE = 0, R32_FORCE_FUSED = 1, R32_FORCE_PIPE = 2 };
+struct R32LoopPlan {
+    int fused;                         // 1: the one-launch loop (lp_fused_r32.hip.h), 0: the two-launch loop (lp_pipe_r32.hip.h)
+    int fN, fNP, fgx, fgy, frows;      // the fused launch: pick workgroups, stagers, grid, rows per pick lane
+    int pN, pNP, pgx, pgy, prows;      // the two-launch loop's sweep launch: pick workgroups, column blocks (= the prep launch's grid), grid, rows per pick lane
+};
+inline R32LoopPlan r32_loop_plan(int m, int W, int forced)
+{
+    R32LoopPlan p;
+    const size_t cells = (size_t)m * (size_t)W;
+    p.fused = forced == R32_FORCE_PIPE ? 0 : (forced == R32_FORCE_FUSED || (cells >= 350000u && cells <= 5000000u)) ? 1 : 0;
+    p.fNP = (W + 255) / 256;
+    p.fN = (m + 63) / 64 < PICK_MAX_WGS ? (m + 63) / 64 : PICK_MAX_WGS;     // one-wave pick workgroups
+    p.fgx = m > p.fN + p.fNP ? m : p.fN + p.fNP; p.fgy = 1 + p.fNP;
+    p.frows = (m + 64 * p.fN - 1) / (64 * p.fN);
+    p.pNP = (W + 255) / 256;
+    p.pN = (m + 255) / 256 < PICK_MAX_WGS ? (m + 255) / 256 : PICK_MAX_WGS;
+    p.pgx = m > p.pN ? m : p.pN; p.pgy = 1 + p.pNP;
+    p.prows = (m + 256 * p.pN - 1) / (256 * p.pN);
+    return p;
+}
 template <> inline void launch_pipe_sweep<R32>(xpg_ctx * ctx, const LpView<R32> & v, int slot, int colstride, bool sample)
 {
     const bool timed = sample && prof_open(ctx);
-    const int N = (v.m + 255) / 256 < PICK_MAX_WGS ? (v.m + 255) / 256 : PICK_MAX_WGS;
-    hipLaunchKernelGGL(k_pipe_sweep_r32, dim3(v.m > N ? v.m : N, 1 + (v.W + 255) / 256), dim3(256), 0, ctx->stream, v, slot, colstride, N);
+    const R32LoopPlan pl = r32_loop_plan(v.m, v.W, R32_FORCE_NONE);
+    hipLaunchKernelGGL(k_pipe_sweep_r32, dim3(pl.pgx, pl.pgy), dim3(256), 0, ctx->stream, v, slot, colstride, pl.pN);
     if (timed) prof_close(ctx);
 }
 // Fused Rational loop (lp_fused_r32.hip.h): one launch per pivot; generic = the generic point before it (generic pick in
@@ -70,11 +99,10 @@ template <class S> inline void launch_fused(xpg_ctx *, const LpView<S> &, int, i
 template <class S> inline void launch_side_home(xpg_ctx *, const LpView<S> &) {}
 template <> inline void launch_fused<R32>(xpg_ctx * ctx, const LpView<R32> & v, int slot, int colstride, bool generic)
 {
-    const int NP = (v.W + 255) / 256;
+    const R32LoopPlan pl = r32_loop_plan(v.m, v.W, R32_FORCE_NONE);
     if (generic) hipLaunchKernelGGL(k_fused_generic, dim3(1), dim3(1024), 0, ctx->stream, v, slot, colstride);
     const bool timed = prof_open(ctx);
-    const int N = (v.m + 63) / 64 < PICK_MAX_WGS ? (v.m + 63) / 64 : PICK_MAX_WGS;     // one-wave pick workgroups
-    hipLaunchKernelGGL(k_pipe_fused_r32, dim3(v.m > N + NP ? v.m : N + NP, 1 + NP), dim3(256), 0, ctx->stream, v, slot, colstride, N, NP);
+    hipLaunchKernelGGL(k_pipe_fused_r32, dim3(pl.fgx, pl.fgy), dim3(256), 0, ctx->stream, v, slot, colstride, pl.fN, pl.fNP);
     if (timed) prof_close(ctx);
 }
 template <> inline void launch_side_home<R32>(xpg_ctx * ctx, const LpView<R32> & v)
@@ -243,6 +271,7 @@ template <class S> struct Lp : LpBase {
     LoopState * h_state = nullptr;    // pinned mirror for read_state
     bool fused_unavailable = false;   // fused Rational loop: its buffers could not be allocated
     bool fused_idles_often = false;   // ... this solve defers decisions often: a generic point before every launch
+    int r32_loop_ran = 0;             // the Rational loop the last queue_iterations call took: 1 one launch per pivot, 2 two launches (xpg_lp_loop_info)
     unsigned fused_idle_seen = 0;
     int blk_batch = 0;      // blocked loop: id of the next batch since reset_loop
     bool closes_often = false;   // blocked loop: >= 5 % of this solve's sweeps so far were of a batch closed early
@@ -464,6 +493,7 @@ template <class S> struct Lp : LpBase {
                              (ctx->loop_mode == 3 || (ctx->loop_auto && (size_t)v.m * v.W * 16 >= blocked_from_bytes()));
         o[0] = blocked ? 3 : 0;
         o[5] = v.ld;
+        o[10] = r32_loop_ran;
         if (!blocked) return;
         const BlkPlan pl = blk_plan(ctx, v.m, v.W, v.ld, ctx->block_len, opt_pricing == 0, chain_off, chain_spread, true);
         o[1] = ctx->block_len; o[2] = !pl.chain ? 0 : pl.local ? 1 : 2; o[3] = pl.line; o[4] = ctx->block_len == 32 ? pl.sweep_rows : 16;
@@ -484,19 +514,20 @@ template <class S> struct Lp : LpBase {
         blocked_now = blocked;
         if (blocked) { queue_blocked(k); return; }
         // (the rational scalar: XPG_R32_LOOP=pipe forces the two-launch loop, =fused the one-launch loop)
-        static const bool r32_pipe = [] { const char * s = xpg_env("XPG_R32_LOOP"); return s && !strcmp(s, "pipe"); }();
+        static const int r32_forced = [] {
+            const char * s = xpg_env("XPG_R32_LOOP");
+            return s && !strcmp(s, "pipe") ? R32_FORCE_PIPE : s && !strcmp(s, "fused") ? R32_FORCE_FUSED : R32_FORCE_NONE;
+        }();
         static const unsigned generic_every = [] { const char * s = xpg_hook("XPG_R32_GENERIC_EVERY"); const int n = s ? atoi(s) : 0; return (unsigned)(n > 0 ? n : 16); }();
         // The fused loop where it pays: its sweep copies the columns the in-place sweep skips (ping-pong tableau) and its
         // launch lasts as long as the pick -> staging chain inside it. Measured against the two-launch loop
         // (tools/lab/probe_rat_sizes.py, us per pivot fused / two-launch): 256 x 512 21.4 / 19.9, 384 x 785 21.0 / 21.0,
         // 512 x 1213 17.0 / 18.0, 768 x 1769 16.7 / 20.9, 1024 x 2048 19.7 / 24.7, 1280 x 2281 27.0 / 30.3, 1536 x 2637
-        // 32.0 / 31.8, 2048 x 3549 51.5 / 46.4. XPG_R32_LOOP=fused / pipe force one or the other.
-        static const bool r32_fused = [] { const char * s = xpg_env("XPG_R32_LOOP"); return s && !strcmp(s, "fused"); }();
-        const size_t cells = (size_t)v.m * (size_t)v.W;
-        const bool fused_pays = r32_fused || (cells >= 350000u && cells <= 5000000u);
-        if (!std::is_same<S, F64>::value && !r32_pipe && fused_pays && k > 0 && fused_buffers()) {
+        // 32.0 / 31.8, 2048 x 3549 51.5 / 46.4. XPG_R32_LOOP=fused / pipe force one or the other. (The rule itself: r32_loop_plan.)
+        if (!std::is_same<S, F64>::value && r32_loop_plan(v.m, v.W, r32_forced).fused && k > 0 && fused_buffers()) {
             // one launch per pivot (lp_fused_r32.hip.h); the first launch of a call and every generic_every-th one are
             // preceded by a generic point
+            r32_loop_ran = 1;
             for (unsigned t = 0; t < k; t++) {
                 const int slot = (int)(pipe_t++ & 1u);
                 launch_fused<S>(ctx, v, slot, colstride, fused_idles_often || t % generic_every == 0);
@@ -509,6 +540,7 @@ template <class S> struct Lp : LpBase {
             }
             return;                                     // (read_state, which follows every call, brings the tableau home)
         }
+        if (k > 0 && !std::is_same<S, F64>::value) r32_loop_ran = 2;
         if (k > 0 && !pipe_primed) {
             // the first pivot is chosen by a launch that has nothing to sweep (pd[1].row < 0): fp64 the sweep launch's
             // pick workgroup, Rational the prep launch's first workgroup

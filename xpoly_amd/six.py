@@ -317,6 +317,13 @@ class DeviceLP:
                     chain_line=o[3], sweep_rows=o[4], ld=o[5], chain_workers=o[6], pick_workers=o[7], prep_workers=o[8],
                     chain_lds_bytes=o[9])
 
+    def r32_loop_ran(self):
+        """The device-resident loop a Rational handle's last iterations ran on: None (none yet), "fused" (one launch per
+        pivot, lp_fused_r32.hip.h) or "pipe" (two launches, lp_pipe_r32.hip.h) -- the 11th figure of xpg_lp_loop_info."""
+        o = (C.c_int32 * 11)()
+        self.ctx.check(lib().xpg_lp_loop_info(self._h, o, C.c_int(11)), "xpg_lp_loop_info")
+        return {0: None, 1: "fused", 2: "pipe"}[o[10]]
+
     def shape(self):
         r, w, rhs = C.c_int(), C.c_int(), C.c_int()
         self.ctx.check(lib().xpg_lp_shape(self._h, C.byref(r), C.byref(w), C.byref(rhs)), "xpg_lp_shape")
