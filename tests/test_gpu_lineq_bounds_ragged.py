@@ -137,6 +137,34 @@ def test_every_class_equals_its_uniform_call(lq, batch, wants):
     assert all(got[0][b] == ok[b] and all(rows_equal(x, y) for x, y in zip(got[3][b], bounds[b])) for b in others)
 
 
+# (rows, nv, systems): a small nest, and the class whose steps' results lie on both sides of cap_lds (tests/test_gpu_lineq_bounds.py)
+TWINS = [(8, 5, 5), (9, 4, 48)]
+
+
+@pytest.mark.parametrize("rows,nv,nb", TWINS)
+def test_one_shape_gives_the_same_bits_through_the_uniform_and_the_ragged_kernel(lq, port, rows, nv, nb):
+    """k_calc_bound_batch and k_calc_bound_ragged run ONE walk (lineq_kernels.hip.h w_calc_bound_walk) through two views of a
+    system: a batch whose systems all share one shape gets the same plan from both calls and must come back bit for bit the
+    same -- rows, their counts, ok, chain and steps."""
+    mats = rc.class_batch(rows, nv, nb)
+    cap_lds = rc.plan_view([rows] * nb, [nv + 1] * nb, None, CAP)["cap_lds"]
+    needs, prefix = [], []
+    for m in mats:
+        n, p = bc.step_needs(port, m, nv)
+        needs += list(n.values()); prefix += p
+    assert max(needs) <= CAP
+    if rows == 9:                                            # results in LDS, on the seat's sides and built in its hold slot
+        assert any(n <= cap_lds for n in needs) and sum(n > cap_lds for n in needs) >= 4 and sum(n > cap_lds for n in prefix) >= 2
+    uok, uchain, usteps, ub = lq.bounds_packed(mats, nv, cap_rows=CAP)
+    assert lq.bounds_last_route()["cap_lds"] == cap_lds
+    rok, rchain, rsteps, rb = lq.bounds_ragged(list(mats), cap_rows=CAP)
+    assert lq.bounds_ragged_last_route()["cap_lds"] == cap_lds
+    assert np.array_equal(uok, rok) and np.array_equal(uchain, rchain) and np.array_equal(usteps, rsteps), (uok, rok, uchain, rchain, usteps, rsteps)
+    assert (uok == 1).any()
+    for b in range(nb):
+        assert len(rb[b]) == nv and all(ub[b][j].shape == rb[b][j].shape and np.array_equal(ub[b][j], rb[b][j]) for j in range(nv)), b
+
+
 # ---- 3. the route ----------------------------------------------------------------------------------------------------------------
 def test_one_launch_and_the_route_is_the_restated_plan(lq, batch):
     mats, _, _ = batch

@@ -1,7 +1,7 @@
 """GPU parity of the projection entry points (xpg_lineq_project_batch_*: a list of variables eliminated in ONE launch of
 k_fme_chain_batch) against the CPU checker's fme applied step after step (tests/lineq_project_cases.py stepped), and against
-the product's own single-step Lineq.fme chained in Python -- which runs k_fme_batch, the other copy of the step. Bit-exact:
-nothing is compared with a tolerance."""
+the product's own single-step Lineq.fme chained in Python -- k_fme_batch, which runs the same step (w_fme_step) once per launch.
+Bit-exact: nothing is compared with a tolerance."""
 import os
 import subprocess
 
@@ -99,7 +99,8 @@ def test_chains_stop_at_every_step_index(lq, wants):
 
 @pytest.mark.parametrize("rows,nv,elim", PARITY)
 def test_one_statement_of_the_step(lq, rows, nv, elim):
-    """The chain kernel's step against k_fme_batch's: the same batches through single-step fme calls chained in Python."""
+    """A chain in one launch against the step on its own: the same batches through single-step fme calls (k_fme_batch) chained
+    in Python."""
     mats = _batch(rows, nv, 48)
     for dark in (False, True):
         ok, steps, res = lq.project_packed(mats, nv, elim, dark, cap_rows=256)

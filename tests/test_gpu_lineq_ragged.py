@@ -125,6 +125,43 @@ def test_every_class_matches_its_uniform_call(lq, base):
             assert all(rows_equal(lres[b][k], ures[i][k]) for i, b in enumerate(idx) for k in range(len(el))), (dark, c)
 
 
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+# (rows, nv, list, systems, cap_rows): a small nest, and HOMES at the capacity that puts its steps' results on both sides of cap_lds
+TWINS = [(8, 5, [4, 3, 2, 1], 5, CAP), rc.HOMES + (None,)]
+
+
+@pytest.mark.parametrize("rows,nv,el,nb,cap", TWINS)
+def test_one_shape_gives_the_same_bits_through_the_uniform_and_the_ragged_kernels(lq, port, rows, nv, el, nb, cap):
+    """The uniform and the ragged kernels run ONE walk (lineq_kernels.hip.h w_chain_walk) through two views of a system: a batch
+    whose systems all share one shape gets the same plan from both calls and must come back bit for bit the same -- rows, their
+    counts, ok and steps -- as a projection and with every level kept."""
+    mats = rc.class_batch(rows, nv, nb)
+    want = [rc.stepped(port, mats[b], nv, el) for b in range(nb)]
+    needs = [n for w in want for n in w[3] if n is not None]
+    both_homes = cap is None
+    cap = cap or max(128, max(needs))
+    cap_lds = rc.plan_view([rows] * nb, [nv + 1] * nb, None, [el] * nb, True, cap, cap)["cap_lds"]
+    assert max(needs) <= cap and any(w[0] == 1 and w[2].shape[0] > 0 for w in want)
+    if both_homes:                                           # results of steps in LDS and in the seat's device slots
+        assert sum(n <= cap_lds for n in needs) >= 4 and sum(n > cap_lds for n in needs) >= 4, (cap_lds, sorted(needs))
+    for dark in (False, True):
+        uok, usteps, ures = lq.project_packed(mats, nv, el, dark, cap_rows=cap, cap_out_rows=cap)
+        assert lq.project_last_route()["cap_lds"] == cap_lds
+        rok, rsteps, rres = lq.project_ragged(list(mats), None, [el] * nb, dark, cap_rows=cap, cap_out_rows=cap)
+        assert lq.ragged_last_route()["cap_lds"] == cap_lds
+        assert np.array_equal(uok, rok) and np.array_equal(usteps, rsteps), (dark, uok, rok, usteps, rsteps)
+        assert all(_same_bits(ures[b], rres[b]) for b in range(nb)), dark
+        uok, usteps, ulev = lq.levels_packed(mats, nv, el, dark, cap_rows=cap, cap_out_rows=cap)
+        assert lq.levels_last_route()["cap_lds"] == cap_lds
+        rok, rsteps, rlev = lq.levels_ragged(list(mats), None, [el] * nb, dark, cap_rows=cap, cap_out_rows=cap)
+        assert lq.ragged_last_route()["cap_lds"] == cap_lds
+        assert np.array_equal(uok, rok) and np.array_equal(usteps, rsteps), (dark, uok, rok, usteps, rsteps)
+        assert all(len(rlev[b]) == len(el) and _same_bits(ulev[b][k], rlev[b][k]) for b in range(nb) for k in range(len(el))), dark
+
+
 # ---- 3. one launch, planned as restated ----------------------------------------------------------------------------------------
 def test_four_classes_take_one_launch_and_the_restated_plan(lq, base):
     mats, nvs, elims = base

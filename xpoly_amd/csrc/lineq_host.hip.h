@@ -575,12 +575,123 @@ inline int ragged_chain_plan(int nb, const int32_t * rows, const int32_t * cols,
 // output slots.
 struct RaggedRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, out_bytes; };
 inline RaggedRoute & ragged_route() { static thread_local RaggedRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
+// The block a ragged packed call (chain, levels, calcBound) sends up, and the buffers of its way down. ONE upload: [descriptors]
+// [lists: nlist entries of `elim`, none where nlist == 0][the systems, gathered back to back], built in the handle's pinned
+// buffer behind meta_al bytes kept for what comes down first (cell offsets [nres + 1], then the ints as on the device) and, with
+// small slots, in front of room for the slots themselves. list(b, at, n, per), asked once per system in order, gives the
+// descriptor's list_at and list_n and the number of result slots of system b (cap_out x OWN cols cells each, following the
+// systems' order: out_off). dints: rows [nres], then nv verdict arrays [nb].
+struct RaggedUp {
+    DevBuf dup, dout, dints, dcells, doff;
+    int nres, nv, cap_out; size_t up_al, meta_al, bo; bool small_out;
+    RaggedSys * hd; const RaggedSys * d_sys; const int * d_lists; const R32 * d_mats;
+};
+template <class List>
+inline int ragged_up(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * rows, const int32_t * cols, const long long * offsets,
+                     const int32_t * rhs_idx, const int32_t * elim, int nlist, List list, int nres, int nv, int cap_out, size_t out_bytes, RaggedUp & u)
+{
+    const size_t b_desc = (size_t)nb * sizeof(RaggedSys), b_list = ((size_t)nlist * 4 + 7) & ~(size_t)7;
+    size_t in_cells = 0;
+    for (int b = 0; b < nb; b++) in_cells += (size_t)rows[b] * cols[b];
+    const size_t b_up = b_desc + b_list + in_cells * 8;
+    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 4 + (size_t)nb * 4 * nv;
+    u.nres = nres; u.nv = nv; u.cap_out = cap_out; u.bo = out_bytes;
+    u.up_al = (b_up + 255) & ~(size_t)255; u.meta_al = (meta + 255) & ~(size_t)255;
+    u.small_out = u.bo <= ((size_t)512 << 10);
+    XPG_TRY(u.dup.alloc(ctx, b_up)); XPG_TRY(u.dout.alloc(ctx, u.bo)); XPG_TRY(u.dints.alloc(ctx, (size_t)(nres + nv * (size_t)nb) * 4));
+    XPG_TRY(u.dcells.alloc(ctx, (size_t)nres * 4)); XPG_TRY(u.doff.alloc(ctx, (size_t)(nres + 1) * 8));
+    if (const int rc = hpack_reserve(ctx, u.meta_al + u.up_al + (u.small_out ? u.bo : 0))) return rc;
+    char * hup = hpack_buf(ctx, false) + u.meta_al;
+    u.hd = (RaggedSys *)hup;
+    long long in_at = 0, out_at = 0;
+    for (int b = 0; b < nb; b++) {
+        int at, n, per;
+        list(b, at, n, per);
+        const size_t c = (size_t)rows[b] * cols[b];
+        u.hd[b] = RaggedSys{in_at, out_at, rows[b], cols[b], rhs_idx ? rhs_idx[b] : cols[b] - 1, at, n, 0};
+        memcpy(hup + b_desc + b_list + (size_t)in_at * 8, (const void *)(mats + offsets[b]), c * 8);
+        in_at += (long long)c;
+        out_at += (long long)per * cap_out * cols[b];
+    }
+    if (nlist) memcpy(hup + b_desc, elim, (size_t)nlist * 4);
+    XPG_TRY(hipMemcpyAsync(u.dup.p, hup, b_up, hipMemcpyHostToDevice, ctx->stream));
+    u.d_sys = (const RaggedSys *)u.dup.p;
+    u.d_lists = (const int *)((char *)u.dup.p + b_desc);
+    u.d_mats = (const R32 *)((char *)u.dup.p + b_desc + b_list);
+    return 0;
+}
+// The way down of a ragged packed call, after its kernel is enqueued: one synchronisation before the rows travel. With small
+// slots they come down with the counts and are packed here; else k_ragged_cells / k_rows_scan give the offsets under that
+// synchronisation and k_pack_ragged sends the live cells alone. per_entry: a system has list_n results, the first at list_at
+// (levels, calcBound: the kernels' levels mode); else one, result b. verdicts: the u.nv arrays [nb] that follow the counts.
+inline int ragged_rows_down(xpg_ctx * ctx, int nb, const int32_t * cols, RaggedUp & u, bool per_entry, R32 * outs, long long outs_cap_cells,
+                            const R32 ** view, long long * out_cell_offsets, int32_t * out_rows, int32_t * const * verdicts)
+{
+    const int nres = u.nres;
+    char * hp = hpack_buf(ctx, false);
+    long long * h_off = (long long *)hp;
+    int32_t * h_ints = (int32_t *)(hp + (size_t)(nres + 1) * 8);
+    XPG_TRY(hipMemcpyAsync(h_ints, u.dints.p, (size_t)(nres + u.nv * (size_t)nb) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    const auto verdicts_out = [&]() {
+        memcpy(out_rows, h_ints, (size_t)nres * 4);
+        for (int v = 0; v < u.nv; v++) memcpy(verdicts[v], h_ints + nres + (size_t)v * nb, (size_t)nb * 4);
+    };
+    if (u.small_out) {
+        char * hs = hp + u.meta_al + u.up_al;
+        XPG_TRY(hipMemcpyAsync(hs, u.dout.p, u.bo, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        verdicts_out();
+        long long tot = 0;
+        for (int b = 0; b < nb; b++)
+            for (int k = 0, first = per_entry ? u.hd[b].list_at : b; k < (per_entry ? u.hd[b].list_n : 1); k++) {
+                out_cell_offsets[first + k] = tot; tot += (long long)out_rows[first + k] * cols[b];
+            }
+        out_cell_offsets[nres] = tot;
+        if (outs && outs_cap_cells < tot) return XPG_ERR_SHAPE;
+        for (int b = 0; b < nb; b++)                                 // forward moves: a destination never lies above its source
+            for (int k = 0, first = per_entry ? u.hd[b].list_at : b; k < (per_entry ? u.hd[b].list_n : 1); k++) {
+                const char * src = hs + ((size_t)u.hd[b].out_off + (size_t)k * u.cap_out * cols[b]) * 8;
+                const size_t nbytes = (size_t)(out_cell_offsets[first + k + 1] - out_cell_offsets[first + k]) * 8;
+                if (outs) memcpy((char *)outs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
+                if (view) memmove(hs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
+            }
+        if (view && tot > 0) *view = (const R32 *)hs;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_ragged_cells, dim3((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024), dim3(256), 0, ctx->stream, nb, u.d_sys, per_entry ? 1 : 0,
+                       (const int *)u.dints.p, (int *)u.dcells.p);
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)u.dcells.p, (long long *)u.doff.p);
+    XPG_TRY(hipGetLastError());
+    XPG_TRY(hipMemcpyAsync(h_off, u.doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipStreamSynchronize(ctx->stream));
+    verdicts_out();
+    memcpy(out_cell_offsets, h_off, (size_t)(nres + 1) * 8);
+    const long long total = out_cell_offsets[nres];
+    if (outs && outs_cap_cells < total) return XPG_ERR_SHAPE;
+    if (total == 0 || (!outs && !view)) return 0;                    // (neither: a sizing call)
+    const size_t bp = (size_t)total * 8;
+    DevBuf dpk;
+    XPG_TRY(dpk.alloc(ctx, bp));
+    hipLaunchKernelGGL(k_pack_ragged, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, u.d_sys, per_entry ? 1 : 0, (const R32 *)u.dout.p,
+                       u.cap_out, (const int *)u.dcells.p, (const long long *)u.doff.p, (R32 *)dpk.p);
+    XPG_TRY(hipGetLastError());
+    if (view) {                                                      // into pinned memory; the caller's copy, if any, from there
+        if (const int rc = hpack_reserve(ctx, bp)) return rc;
+        char * hv = hpack_buf(ctx, false);
+        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+        if (outs) memcpy(outs, hv, bp);
+        *view = (const R32 *)hv;
+    } else {
+        XPG_TRY(hipMemcpyAsync(outs, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
+        XPG_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
 // Host arrays with a PACKED result in CELLS (the rows differ in width; the convention of xpg_lineq_fme_batch_ragged_rat32):
 // out_cell_offsets [slots + 1] and out_rows [slots], slots = nb (projection: result b) or elim_offsets[nb] (levels: level k of
-// system b at elim_offsets[b] + k). ONE upload -- descriptors, lists and the systems gathered into one block of the handle's
-// pinned buffer -- ONE launch, and one synchronisation before the rows travel: with small slots they come down with the counts
-// and are packed here; else k_ragged_cells / k_rows_scan give the offsets under that synchronisation and k_pack_ragged sends
-// the live cells alone. A system with out_ok <= 0 contributes no cells, the others are packed all the same. XPG_ERR_SHAPE
+// system b at elim_offsets[b] + k). ONE upload (ragged_up), ONE launch, and one synchronisation before the rows travel
+// (ragged_rows_down). A system with out_ok <= 0 contributes no cells, the others are packed all the same. XPG_ERR_SHAPE
 // where `outs` holds fewer than out_cell_offsets[slots] cells (offsets, counts and verdicts are filled); neither outs nor
 // view: a sizing call.
 inline int lineq_chain_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * rows, const int32_t * cols, const long long * offsets,
@@ -596,111 +707,25 @@ inline int lineq_chain_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, co
     if (const int rc = ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, levels, cap_rows, cap_out_rows, p)) return rc;
     if (!ctx || !mats || !offsets || !out_rows || !out_ok || !out_steps || (outs && outs_cap_cells < 0)) return XPG_ERR_SHAPE;
     for (int b = 0; b < nb; b++) if (offsets[b] < 0) return XPG_ERR_SHAPE;
-    const int nres = (int)p.slots, nlist = elim_offsets[nb];
-    // the block that goes up: [descriptors][lists][systems, back to back]
-    const size_t b_desc = (size_t)nb * sizeof(RaggedSys), b_list = ((size_t)nlist * 4 + 7) & ~(size_t)7;
-    size_t in_cells = 0;
-    for (int b = 0; b < nb; b++) in_cells += (size_t)rows[b] * cols[b];
-    const size_t b_up = b_desc + b_list + in_cells * 8, up_al = (b_up + 255) & ~(size_t)255;
-    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 4 + (size_t)nb * 8;      // cell offsets, then rows, ok and steps
-    const size_t meta_al = (meta + 255) & ~(size_t)255, b_ints = (size_t)(nres + 2 * (size_t)nb) * 4;
-    const size_t bo = p.out_bytes;
-    const bool small_out = bo <= ((size_t)512 << 10);
-    DevBuf dup, dout, dints, dcells, doff;                           // dints: rows [nres], ok [nb], steps [nb]
-    XPG_TRY(dup.alloc(ctx, b_up)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dints.alloc(ctx, b_ints));
-    XPG_TRY(dcells.alloc(ctx, (size_t)nres * 4)); XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
     Scratch & seats = ctx->scratch[SCRATCH_LINEQ_PROJECT];
     if (const int rc = scratch_reserve(ctx, seats, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_ragged seats)")) return rc;
-    int rc = hpack_reserve(ctx, meta_al + up_al + (small_out ? bo : 0));
-    if (rc) return rc;
-    char * hp = hpack_buf(ctx, false);
-    char * hup = hp + meta_al;
-    RaggedSys * hd = (RaggedSys *)hup;
-    long long in_at = 0, out_at = 0;
-    for (int b = 0; b < nb; b++) {
-        const int n = elim_offsets[b + 1] - elim_offsets[b];
-        const size_t c = (size_t)rows[b] * cols[b];
-        hd[b] = RaggedSys{in_at, out_at, rows[b], cols[b], rhs_idx ? rhs_idx[b] : cols[b] - 1, elim_offsets[b], n, 0};
-        memcpy(hup + b_desc + b_list + (size_t)in_at * 8, (const void *)(mats + offsets[b]), c * 8);
-        in_at += (long long)c;
-        out_at += (long long)(levels ? n : 1) * p.cap_out * cols[b];
-    }
-    memcpy(hup + b_desc, elim, (size_t)nlist * 4);
-    XPG_TRY(hipMemcpyAsync(dup.p, hup, b_up, hipMemcpyHostToDevice, ctx->stream));
-    const RaggedSys * d_sys = (const RaggedSys *)dup.p;
-    const int * d_lists = (const int *)((char *)dup.p + b_desc);
-    const R32 * d_mats = (const R32 *)((char *)dup.p + b_desc + b_list);
-    int * d_rows = (int *)dints.p, * d_ok = d_rows + nres, * d_steps = d_ok + nb;
+    RaggedUp up;
+    const auto list = [&](int b, int & at, int & n, int & per) { at = elim_offsets[b]; n = elim_offsets[b + 1] - at; per = levels ? n : 1; };
+    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, elim, elim_offsets[nb], list, (int)p.slots, 2, p.cap_out, p.out_bytes, up)) return rc;
+    int * d_rows = (int *)up.dints.p, * d_ok = d_rows + up.nres, * d_steps = d_ok + nb;
     if (levels) {
         XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<true>, ctx->device, p.q.lds));
-        hipLaunchKernelGGL(k_fme_chain_ragged<true>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_sys, d_lists, d_mats, darkshadow,
-                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
+        hipLaunchKernelGGL(k_fme_chain_ragged<true>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_lists, up.d_mats, darkshadow,
+                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
     } else {
         XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<false>, ctx->device, p.q.lds));
-        hipLaunchKernelGGL(k_fme_chain_ragged<false>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_sys, d_lists, d_mats, darkshadow,
-                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
+        hipLaunchKernelGGL(k_fme_chain_ragged<false>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_lists, up.d_mats, darkshadow,
+                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
     }
     XPG_TRY(hipGetLastError());
     ragged_route() = RaggedRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes};
-    // the way down
-    long long * h_off = (long long *)hp;
-    int32_t * h_ints = (int32_t *)(hp + (size_t)(nres + 1) * 8);     // rows, ok, steps as on the device
-    XPG_TRY(hipMemcpyAsync(h_ints, dints.p, b_ints, hipMemcpyDeviceToHost, ctx->stream));
-    const auto verdicts_out = [&]() {
-        memcpy(out_rows, h_ints, (size_t)nres * 4); memcpy(out_ok, h_ints + nres, (size_t)nb * 4);
-        memcpy(out_steps, h_ints + nres + nb, (size_t)nb * 4);
-    };
-    if (small_out) {
-        char * hs = hup + up_al;
-        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        verdicts_out();
-        long long tot = 0;
-        for (int b = 0; b < nb; b++)
-            for (int k = 0, first = levels ? hd[b].list_at : b; k < (levels ? hd[b].list_n : 1); k++) {
-                out_cell_offsets[first + k] = tot; tot += (long long)out_rows[first + k] * cols[b];
-            }
-        out_cell_offsets[nres] = tot;
-        if (outs && outs_cap_cells < tot) return XPG_ERR_SHAPE;
-        for (int b = 0; b < nb; b++)                                 // forward moves: a destination never lies above its source
-            for (int k = 0, first = levels ? hd[b].list_at : b; k < (levels ? hd[b].list_n : 1); k++) {
-                const char * src = hs + ((size_t)hd[b].out_off + (size_t)k * p.cap_out * cols[b]) * 8;
-                const size_t nbytes = (size_t)(out_cell_offsets[first + k + 1] - out_cell_offsets[first + k]) * 8;
-                if (outs) memcpy((char *)outs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
-                if (view) memmove(hs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
-            }
-        if (view && tot > 0) *view = (const R32 *)hs;
-        return 0;
-    }
-    hipLaunchKernelGGL(k_ragged_cells, dim3((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024), dim3(256), 0, ctx->stream, nb, d_sys, levels ? 1 : 0,
-                       (const int *)d_rows, (int *)dcells.p);
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)dcells.p, (long long *)doff.p);
-    XPG_TRY(hipGetLastError());
-    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    verdicts_out();
-    memcpy(out_cell_offsets, h_off, (size_t)(nres + 1) * 8);
-    const long long total = out_cell_offsets[nres];
-    if (outs && outs_cap_cells < total) return XPG_ERR_SHAPE;
-    if (total == 0 || (!outs && !view)) return 0;                    // (neither: a sizing call)
-    const size_t bp = (size_t)total * 8;
-    DevBuf dpk;
-    XPG_TRY(dpk.alloc(ctx, bp));
-    hipLaunchKernelGGL(k_pack_ragged, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, d_sys, levels ? 1 : 0, (const R32 *)dout.p,
-                       p.cap_out, (const int *)dcells.p, (const long long *)doff.p, (R32 *)dpk.p);
-    XPG_TRY(hipGetLastError());
-    if (view) {                                                      // into pinned memory; the caller's copy, if any, from there
-        if ((rc = hpack_reserve(ctx, bp))) return rc;
-        char * hv = hpack_buf(ctx, false);
-        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        if (outs) memcpy(outs, hv, bp);
-        *view = (const R32 *)hv;
-    } else {
-        XPG_TRY(hipMemcpyAsync(outs, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return 0;
+    int32_t * const verdicts[3] = {out_ok, out_steps, 0};
+    return ragged_rows_down(ctx, nb, cols, up, levels, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
 }
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for nb systems at once: for every variable j the
@@ -925,12 +950,10 @@ inline int bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols
 // output slots, elimination steps of the whole batch.
 struct BoundsRaggedRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, out_bytes, steps; };
 inline BoundsRaggedRoute & bounds_ragged_route() { static thread_local BoundsRaggedRoute r = {0, 0, 0, 0, 0, 0, 0, 0}; return r; }
-// Host arrays with a PACKED result in CELLS, lineq_chain_ragged_packed step for step: out_cell_offsets [R + 1] and out_rows [R],
-// R the sum of the rhs, variable j of system b at first[b] + j (first[b] the sum of the rhs before b). ONE upload (descriptors
-// and the systems gathered into one block of the handle's pinned buffer), ONE launch, one synchronisation before the rows
-// travel: small slots come down with the counts and are packed here; else k_ragged_cells / k_rows_scan give the offsets under
-// that synchronisation and k_pack_ragged sends the live cells alone (both in their levels mode: the descriptor's list_at /
-// list_n carry first[b] / rhs). A system with out_ok <= 0 contributes no cells, the others are packed all the same.
+// Host arrays with a PACKED result in CELLS, as lineq_chain_ragged_packed gives them: out_cell_offsets [R + 1] and out_rows [R],
+// R the sum of the rhs, variable j of system b at first[b] + j (first[b] the sum of the rhs before b). ONE upload (ragged_up:
+// descriptors and systems, no list -- the descriptor's list_at / list_n carry first[b] / rhs), ONE launch, one synchronisation
+// before the rows travel (ragged_rows_down). A system with out_ok <= 0 contributes no cells, the others are packed all the same.
 // XPG_ERR_SHAPE where `outs` holds fewer than out_cell_offsets[R] cells (offsets, counts and verdicts are filled); neither
 // outs nor view: a sizing call.
 inline int lineq_bounds_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * rows, const int32_t * cols, const long long * offsets,
@@ -946,103 +969,20 @@ inline int lineq_bounds_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, c
     if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
     if (!ctx || !mats || !offsets || !out_rows || !out_ok || !out_chain || !out_steps || (outs && outs_cap_cells < 0)) return XPG_ERR_SHAPE;
     for (int b = 0; b < nb; b++) if (offsets[b] < 0) return XPG_ERR_SHAPE;
-    const int nres = (int)p.slots;
-    // the block that goes up: [descriptors][systems, back to back]
-    const size_t b_desc = (size_t)nb * sizeof(RaggedSys);
-    size_t in_cells = 0;
-    for (int b = 0; b < nb; b++) in_cells += (size_t)rows[b] * cols[b];
-    const size_t b_up = b_desc + in_cells * 8, up_al = (b_up + 255) & ~(size_t)255;
-    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 4 + (size_t)nb * 12;     // cell offsets, then rows, ok, chain and steps
-    const size_t meta_al = (meta + 255) & ~(size_t)255, b_ints = (size_t)(nres + 3 * (size_t)nb) * 4;
-    const size_t bo = p.out_bytes;
-    const bool small_out = bo <= ((size_t)512 << 10);
-    DevBuf dup, dout, dints, dcells, doff;                           // dints: rows [nres], ok [nb], chain [nb], steps [nb]
-    XPG_TRY(dup.alloc(ctx, b_up)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dints.alloc(ctx, b_ints));
-    XPG_TRY(dcells.alloc(ctx, (size_t)nres * 4)); XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
     Scratch & seats = ctx->scratch[SCRATCH_LINEQ_BOUNDS];
     if (const int rc = scratch_reserve(ctx, seats, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_bounds_ragged seats)")) return rc;
-    int rc = hpack_reserve(ctx, meta_al + up_al + (small_out ? bo : 0));
-    if (rc) return rc;
-    char * hp = hpack_buf(ctx, false);
-    char * hup = hp + meta_al;
-    RaggedSys * hd = (RaggedSys *)hup;
-    long long in_at = 0, out_at = 0;
-    int first = 0;
-    for (int b = 0; b < nb; b++) {
-        const int rhs = rhs_idx ? rhs_idx[b] : cols[b] - 1;
-        const size_t c = (size_t)rows[b] * cols[b];
-        hd[b] = RaggedSys{in_at, out_at, rows[b], cols[b], rhs, first, rhs, 0};
-        memcpy(hup + b_desc + (size_t)in_at * 8, (const void *)(mats + offsets[b]), c * 8);
-        in_at += (long long)c;
-        out_at += (long long)rhs * p.cap_out * cols[b];
-        first += rhs;
-    }
-    XPG_TRY(hipMemcpyAsync(dup.p, hup, b_up, hipMemcpyHostToDevice, ctx->stream));
-    const RaggedSys * d_sys = (const RaggedSys *)dup.p;
-    const R32 * d_mats = (const R32 *)((char *)dup.p + b_desc);
-    int * d_rows = (int *)dints.p, * d_ok = d_rows + nres, * d_chain = d_ok + nb, * d_steps = d_chain + nb;
+    RaggedUp up;
+    int first = 0;                                                   // (asked once per system, in order)
+    const auto list = [&](int b, int & at, int & n, int & per) { at = first; n = per = rhs_idx ? rhs_idx[b] : cols[b] - 1; first += n; };
+    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, (const int32_t *)0, 0, list, (int)p.slots, 3, p.cap_out, p.out_bytes, up)) return rc;
+    int * d_rows = (int *)up.dints.p, * d_ok = d_rows + up.nres, * d_chain = d_ok + nb, * d_steps = d_chain + nb;
     XPG_TRY(lds_limit((const void *)k_calc_bound_ragged, ctx->device, p.q.lds));
-    hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_sys, d_mats, (R32 *)seats.buf, p.cap, p.cols,
-                       (R32 *)dout.p, p.cap_out, d_rows, d_ok, d_chain, d_steps, p.cap_lds);
+    hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_mats, (R32 *)seats.buf, p.cap, p.cols,
+                       (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_chain, d_steps, p.cap_lds);
     XPG_TRY(hipGetLastError());
     bounds_ragged_route() = BoundsRaggedRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps};
-    // the way down
-    long long * h_off = (long long *)hp;
-    int32_t * h_ints = (int32_t *)(hp + (size_t)(nres + 1) * 8);     // rows, ok, chain, steps as on the device
-    XPG_TRY(hipMemcpyAsync(h_ints, dints.p, b_ints, hipMemcpyDeviceToHost, ctx->stream));
-    const auto verdicts_out = [&]() {
-        memcpy(out_rows, h_ints, (size_t)nres * 4); memcpy(out_ok, h_ints + nres, (size_t)nb * 4);
-        memcpy(out_chain, h_ints + nres + nb, (size_t)nb * 4); memcpy(out_steps, h_ints + nres + 2 * (size_t)nb, (size_t)nb * 4);
-    };
-    if (small_out) {
-        char * hs = hup + up_al;
-        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        verdicts_out();
-        long long tot = 0;
-        for (int b = 0; b < nb; b++)
-            for (int j = 0, f = hd[b].list_at; j < hd[b].list_n; j++) { out_cell_offsets[f + j] = tot; tot += (long long)out_rows[f + j] * cols[b]; }
-        out_cell_offsets[nres] = tot;
-        if (outs && outs_cap_cells < tot) return XPG_ERR_SHAPE;
-        for (int b = 0; b < nb; b++)                                 // forward moves: a destination never lies above its source
-            for (int j = 0, f = hd[b].list_at; j < hd[b].list_n; j++) {
-                const char * src = hs + ((size_t)hd[b].out_off + (size_t)j * p.cap_out * cols[b]) * 8;
-                const size_t nbytes = (size_t)(out_cell_offsets[f + j + 1] - out_cell_offsets[f + j]) * 8;
-                if (outs) memcpy((char *)outs + (size_t)out_cell_offsets[f + j] * 8, src, nbytes);
-                if (view) memmove(hs + (size_t)out_cell_offsets[f + j] * 8, src, nbytes);
-            }
-        if (view && tot > 0) *view = (const R32 *)hs;
-        return 0;
-    }
-    hipLaunchKernelGGL(k_ragged_cells, dim3((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024), dim3(256), 0, ctx->stream, nb, d_sys, 1,
-                       (const int *)d_rows, (int *)dcells.p);
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)dcells.p, (long long *)doff.p);
-    XPG_TRY(hipGetLastError());
-    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipStreamSynchronize(ctx->stream));
-    verdicts_out();
-    memcpy(out_cell_offsets, h_off, (size_t)(nres + 1) * 8);
-    const long long total = out_cell_offsets[nres];
-    if (outs && outs_cap_cells < total) return XPG_ERR_SHAPE;
-    if (total == 0 || (!outs && !view)) return 0;                    // (neither: a sizing call)
-    const size_t bp = (size_t)total * 8;
-    DevBuf dpk;
-    XPG_TRY(dpk.alloc(ctx, bp));
-    hipLaunchKernelGGL(k_pack_ragged, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, d_sys, 1, (const R32 *)dout.p, p.cap_out,
-                       (const int *)dcells.p, (const long long *)doff.p, (R32 *)dpk.p);
-    XPG_TRY(hipGetLastError());
-    if (view) {                                                      // into pinned memory; the caller's copy, if any, from there
-        if ((rc = hpack_reserve(ctx, bp))) return rc;
-        char * hv = hpack_buf(ctx, false);
-        XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-        if (outs) memcpy(outs, hv, bp);
-        *view = (const R32 *)hv;
-    } else {
-        XPG_TRY(hipMemcpyAsync(outs, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
-        XPG_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return 0;
+    int32_t * const verdicts[3] = {out_ok, out_chain, out_steps};
+    return ragged_rows_down(ctx, nb, cols, up, true, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
 }
 
 // Matrix<Rational>::rank on device arrays, enqueue only: d_rank [nb].

@@ -387,11 +387,9 @@ __global__ __launch_bounds__(64) void k_reduce_batch(int nb, R32 * mats, int row
 
 // One elimination of Lineq::fme (linsys.cpp:656-774): variable u out of the tmp.r rows that w_load put into tmp (LDS), the
 // result built and reduced in res_lds where its nfree + P x N rows fit cap_lds, else directly in `go` (device memory with
-// room for cap rows; flat pointers). It is k_fme_batch's body, statement for statement, as k_fme_chain_batch runs it once
-// per entry of its elimination list and k_calc_bound_batch once per step of its walk. k_fme_batch keeps its own text: calling this function from it moved its SGPR spills
-// from 75 to 77 (profiles/lineq_project_isa.txt), so a change to either copy has to be made in both -- the tests hold
-// the two against each other bit for bit (tests/test_gpu_lineq_project.py). tmp is normalised in place; res.a / res.r
-// say where the result is and how many rows it has. capx >= the rows of either matrix (the cell loops' divisor).
+// room for cap rows; flat pointers). THE step of every kernel of the family: k_fme_batch runs it once per system, the chain
+// walk once per entry of a list, the calcBound walk once per step. tmp is normalised in place; res.a / res.r say where the
+// result is and how many rows it has. capx >= the rows of either matrix (the cell loops' divisor).
 struct FmeStep { bool ok; bool in_lds; int over; };        // over: -1, or the rows the result needs where cap holds fewer
 __device__ __forceinline__ FmeStep w_fme_step(WMat & tmp, WMat & res, R32 * const res_lds, R32 * const go, const int cols,
                                               const int rhs, const int u, const int darkshadow, const int cap,
@@ -527,112 +525,15 @@ __global__ __launch_bounds__(64) void k_fme_batch(int nb, const R32 * mats, int 
         const int rows = in_rows ? in_rows[b] : cap_in;
         const R32 * g = mats + (size_t)b * cap_in * cols;
         R32 * const go = outs + (size_t)b * cap * cols;
-        LQ_T0
-        w_load(tmp, g, rows, cols);
-        LQ_T(0)
-        res.r = 0; res.cn = tmp.cn;
-        // classify rows: 0 = no u (copy), 1 = positive, 2 = negative; 3 = inconsistent constant row
-        int * kind = s.map;
-        int * bad_at = &s.flags[1];
-        if (lane_id() == 0) *bad_at = INT_MAX;
+        { LQ_T0 w_load(tmp, g, rows, cols); LQ_T(0) }
+        const FmeStep st = w_fme_step(tmp, res, res_lds, go, cols, rhs, u, darkshadow, cap, cap_lds, cap > cap_in ? cap : cap_in, s);
+        LQ_T0                                                           // (the step stamps its own phases, 1 .. 5)
         wave_sync();
-        for (int i = lane_id(); i < rows; i += wave_lanes()) {
-            bool have = false;
-            for (int j = 0; j < rhs && !have; j++) have = ne(tmp.a[i * cols + j], R32(0, 1));
-            if (!have && w_cmp_value(tmp, rhs, i, R32(0, 1)) == CST_LT) atomicMin(bad_at, i);
-            const R32 c = tmp.a[i * cols + u];
-            kind[i] = ne(c, R32(0, 1)) ? (gt(c, R32(0, 1)) ? 1 : 2) : 0;
-        }
-        wave_sync();
-        const int stop = *bad_at == INT_MAX ? rows : *bad_at;      // rows before the first bad one are processed
-        LQ_T(1)
-        // the row lists: rows without u go first, in order (linsys.cpp:724-730); positive and negative rows of u
-        int nfree = 0, np = 0, nn = 0;
-        for (int base = 0; base < stop; base += wave_lanes()) {
-            const int i = base + lane_id();
-            const int kd = i < stop ? kind[i] : -1;
-            const unsigned long long bf = grp_ballot(kd == 0), bp = grp_ballot(kd == 1), bn = grp_ballot(kd == 2);
-            if (kd == 0) kind[i] = -(nfree + grp_rank(bf)) - 1;       // destination row, encoded negative
-            else if (kd == 1) s.pos[np + grp_rank(bp)] = (short)i;
-            else if (kd == 2) s.negs[nn + grp_rank(bn)] = (short)i;
-            nfree += __popcll(bf); np += __popcll(bp); nn += __popcll(bn);
-        }
-        wave_sync();
-        // where this system's result lives
-        const int need = nfree + (np + nn == 1 ? 1 : np * nn);
-        const bool in_lds = need <= cap_lds;
-        res.a = in_lds ? res_lds : go;
-        // normalise the rows that contain u (linsys.cpp:711-723): the rows are independent, so the factors are
-        // found one lane per row (kept in the still empty result matrix) and applied one lane per cell
-        R32 * fac = cap_lds ? res_lds : go;                       // (the host keeps cap_lds * cols >= cap_in when cap_lds > 0)
-        for (int i = lane_id(); i < stop; i += wave_lanes()) {
-            int mode = SCALE_KEEP;
-            if (kind[i] > 0) {
-                const R32 c = tmp.a[i * cols + u];
-                R32 f(1, 1);
-                if (kind[i] == 1) { if (ne(c, R32(1, 1))) f = q_div(tmp.cn, R32(1, 1), c); }
-                else if (ne(c, R32(-1, 1))) f = q_div(tmp.cn, R32(1, 1), neg(c));
-                mode = scale_mode(f);
-                fac[i] = f;
-            }
-            s.drop[i] = (unsigned char)mode;
-        }
-        wave_sync();
-        const FastDiv by_cols(cols, (cap > cap_in ? cap : cap_in) * cols + wave_lanes());
-        for (int t = lane_id(); t < stop * cols; t += wave_lanes()) {
-            const int i = by_cols.quot(t), mode = s.drop[i];
-            if (mode != SCALE_KEEP) tmp.a[t] = q_scaled(tmp.cn, tmp.a[t], fac[i], mode);
-        }
-        wave_sync();
-        if (darkshadow) {
-            for (int i = lane_id(); i < stop; i += wave_lanes())
-                if (kind[i] == 2) tmp.a[i * cols + rhs] = q_sub(tmp.cn, tmp.a[i * cols + rhs], R32(1, 1));
-            wave_sync();
-        }
-        LQ_T(2)
-        // rows without u are copied first
-        wave_sync();
-        for (int t = lane_id(); t < stop * cols; t += wave_lanes()) {
-            const int i = by_cols.quot(t), j = t - i * cols;
-            if (kind[i] < 0) res.a[(-kind[i] - 1) * cols + j] = tmp.a[t];
-        }
-        res.r = nfree;
-        LQ_T(3)
-        bool ok = true;
-        int status_rows = -1;
-        if (stop < rows) {                                              // inconsistent constant row
-            ok = false;
-        } else {
-            int extra = 0;
-            if (np + nn == 1) extra = 1;
-            else if (np + nn > 1) extra = np * nn;
-            if (res.r + extra > cap) { status_rows = res.r + extra; ok = false; }
-            else if (np + nn == 1) {
-                const int pi = np == 1 ? s.pos[0] : s.negs[0];
-                for (int j = lane_id(); j < cols; j += wave_lanes()) res.a[res.r * cols + j] = tmp.a[pi * cols + j];
-                res.r += 1;
-            } else if (np + nn > 1) {                                   // every (pos, neg) pair summed
-                const int base = res.r * cols, total = np * nn * cols;
-                const FastDiv by_nn(nn, np * nn);
-                for (int t = lane_id(); t < total; t += wave_lanes()) {
-                    const int pair = by_cols.quot(t), j = t - pair * cols;
-                    const int pq = by_nn.quot(pair);
-                    const int pi = s.pos[pq], ni = s.negs[pair - pq * nn];
-                    res.a[base + t] = q_add(tmp.cn, tmp.a[pi * cols + j], tmp.a[ni * cols + j]);
-                }
-                res.r += np * nn;
-            }
-            wave_sync();
-            LQ_T(4)
-            if (status_rows < 0 && res.r > 0) ok = w_reduce(res, rhs, true, s);
-            LQ_T(5)
-        }
-        wave_sync();
-        if (status_rows < 0 && in_lds) w_store(res, go);
+        if (st.over < 0 && st.in_lds) w_store(res, go);
         if (lane_id() == 0) {
-            out_rows[b] = status_rows < 0 ? res.r : -status_rows;       // negative: did not fit, needs that many rows
-            out_ok[b] = ok ? 1 : 0;
-            if (chain_ok && !ok) chain_ok[b] = status_rows < 0 ? 0 : -status_rows;
+            out_rows[b] = st.over < 0 ? res.r : -st.over;               // negative: did not fit, needs that many rows
+            out_ok[b] = st.ok ? 1 : 0;
+            if (chain_ok && !st.ok) chain_ok[b] = st.over < 0 ? 0 : -st.over;
         }
         wave_sync();
         LQ_T(6)
@@ -640,145 +541,175 @@ __global__ __launch_bounds__(64) void k_fme_batch(int nb, const R32 * mats, int 
     }
 }
 
-// A projection: the variables el.u[0 .. el.n) eliminated one after the other (DepPoly::eliminateAuxVar, eng/poly.cpp:643-651;
-// the scanning bounds, eng/poly.cpp:4807-4813), each step's result the next step's input, ALL steps of a system before the
-// wave takes its next system. The list travels as a kernel argument (no upload of its own); an index may repeat.
+// ---- the walks: many steps of one system before its wavefront takes the next system --------------------------------------------
+// A SEAT is the wavefront group of one workgroup slot (sys_first() of the uniform kernels, the workgroup of the ragged ones); it
+// serves the systems b, b + stride, ... one after the other. Its LDS is [result area (cap_lds x cols)] [step input (cap x cols)]
+// [scratch], fme_lds(cap, cap, cols). Intermediates belong to the SEAT, not to the system: a step whose nfree + P x N rows fit
+// cap_lds is built and reduced in LDS and loaded into the input area from there; a larger one is built and reduced in one of the
+// seat's slots of `seats` (cap rows each; the two SIDES alternate) and loaded from there. Seats are reused above the grid.
+//   A walk reads its system through a VIEW (the template parameter Sys) that holds the kernel's own arguments and computes an
+// address where it is used: rows(), cols(), rhs(), in() the input cells, u(k) entry k of the elimination list, out(k) / cnt(k)
+// result slot k of the system (cap_out rows of OWN cols cells) and its row count. UniformSys reads kernel arguments, the list
+// included (ElimList: no upload of its own); RaggedView a descriptor and a concatenated list in device memory.
+//   The uniform kernels take every shape from their arguments. The ragged kernels serve systems of MIXED shapes in one launch --
+// the statements of a SCoP sit at different depths, so rows, cols, rhs and the list differ from system to system. There the
+// LDS block, the seats and cap / cap_lds / cap_out belong to the LAUNCH, sized by the host from the envelope (the widest
+// system's `ecols`, the largest capacity: lineq_host.hip.h ragged_chain_plan, bounds_ragged_plan), each area and slot (cap x
+// ecols cells) at the same place for every system. INSIDE an area or slot a system uses its OWN cols as row stride, so its cells
+// -- and with them every loop bound, divisor and result bit -- are those of the uniform kernels; a narrower system leaves the
+// tail unused. cap_lds x ecols >= cap cells, so the row factors of a step fit the result area whatever cols is; a step with
+// need <= cap_lds rows is built in LDS (need x cols <= cap_lds x ecols cells), and nothing a step may build (need <= cap, else
+// a verdict before any row is written past nfree <= rows <= cap) leaves its slot. `need` is judged against the launch's caps.
+//   Consecutive systems of one seat may differ in cols, rows and list. Nothing of the previous system is read: w_load writes the
+// rows x cols cells every later loop is bounded by; w_fme_step writes bad_at, kind[0 .. rows), the row lists, drop[] and the
+// factors before it reads them (a factor only where its own drop[] entry, written in the same pass, says so); w_reduce and
+// w_remove_iden write map[] / removed[] / kind[] for [0, m.r) first. The one read past a live entry -- w_iden_rows' four hashes
+// per trip, up to three behind the last row -- is inside the scratch of cap + 1 entries and cannot change a result (a row's
+// own index is visited after any larger one), whatever an earlier system of another width left there. The scratch itself never
+// moves with cols. A side is read (w_load from res.a) only in the step after the one that wrote it. The wave_sync that ends a
+// system in the kernel orders lane 0's verdicts and every lane's LDS reads before the next system's w_load.
 enum { FME_CHAIN_MAX = 64 };
 struct ElimList { int n; int u[FME_CHAIN_MAX]; };
-// mats [nb][rows][cols]; LDS of a seat (the wave of one workgroup slot): [result area (cap_lds x cols)] [step input (cap x cols)]
-// [scratch], fme_lds(cap, cap, cols) as for calcBound's chains. Intermediates belong to the SEAT, not to the system: a step
-// whose nfree + P x N rows fit cap_lds is built and reduced in LDS and loaded into the input area from there; a larger one is
-// built and reduced in one of the seat's two cap-row slots of `seats` [seats][2][cap][cols] (the sides alternate) and loaded
-// from there. The last step's rows go to the system's own slot of outs [nb][cap_out][cols]; nothing is stored behind them.
-//   out_ok[b] 1, out_steps[b] el.n: out_rows[b] rows (0 after an empty intermediate: fme of an empty system is true and empty)
-//   out_ok[b] 0, out_steps[b] k:    step k found the system inconsistent; no rows
-//   out_ok[b] -need:                step out_steps[b] needs `need` > cap rows, or (out_steps[b] == el.n) the final result has
-//                                   `need` > cap_out rows; no rows
+struct RaggedSys { long long in_off, out_off; int rows, cols, rhs, list_at, list_n, pad; };
+
+// system b of a uniform batch: mats [nb][rows][cols], `per` result slots a system (outs [nb][per][cap_out][cols], out_rows [nb][per])
+struct UniformSys {
+    const R32 * mats; int rows_, cols_, rhs_, per; R32 * outs; int cap_out; int * out_rows; int b;
+    __device__ __forceinline__ int rows() const { return rows_; }
+    __device__ __forceinline__ int cols() const { return cols_; }
+    __device__ __forceinline__ int rhs() const { return rhs_; }
+    __device__ __forceinline__ const R32 * in() const { return mats + (size_t)b * rows_ * cols_; }
+    __device__ __forceinline__ R32 * out(int k) const { return outs + ((size_t)b * per + k) * cap_out * cols_; }
+    __device__ __forceinline__ int * cnt(int k) const { return out_rows + (size_t)b * per + k; }
+};
+struct UniformChain : UniformSys {
+    const ElimList & el;
+    __device__ __forceinline__ int n() const { return el.n; }
+    __device__ __forceinline__ int u(int k) const { return el.u[k]; }
+};
+// system b of a ragged batch: the slots start at cell d.out_off, the counts at out_rows[first] (one result: first = b; a result
+// per list entry or per variable: first = d.list_at, which for calcBound carries the sum of the rhs before b, list_n its rhs --
+// k_ragged_cells / k_pack_ragged serve in their levels mode)
+struct RaggedView {
+    const RaggedSys & d; const int * lists; const R32 * mats; R32 * outs; int cap_out; int * out_rows; int first;
+    __device__ __forceinline__ int rows() const { return d.rows; }
+    __device__ __forceinline__ int cols() const { return d.cols; }
+    __device__ __forceinline__ int rhs() const { return d.rhs; }
+    __device__ __forceinline__ int n() const { return d.list_n; }
+    __device__ __forceinline__ int u(int k) const { return lists[d.list_at + k]; }
+    __device__ __forceinline__ const R32 * in() const { return mats + d.in_off; }
+    __device__ __forceinline__ R32 * out(int k) const { return outs + d.out_off + (size_t)k * cap_out * d.cols; }
+    __device__ __forceinline__ int * cnt(int k) const { return out_rows + first + k; }
+};
+
+// A projection: the variables u(0 .. n) eliminated one after the other (DepPoly::eliminateAuxVar, eng/poly.cpp:643-651; the scanning
+// bounds, eng/poly.cpp:4807-4813), each step's result the next step's input; an index may repeat. `slot`: cells of a side.
+// KEEP_LEVELS false: the last step's rows go to out(0), their count to cnt(0); nothing is stored behind them.
+//   okv 1, steps n:  cnt(0) rows (0 after an empty intermediate: fme of an empty system is true and empty)
+//   okv 0, steps k:  step k found the system inconsistent; no rows
+//   okv -need:       step `steps` needs `need` > cap rows, or (steps == n) the final result has `need` > cap_out rows; no rows
+// KEEP_LEVELS true: loop-bound generation (LoopTran::transformIterSpace, eng/ldtran.cpp:178-196 and :241-257) eliminates rhs-1 .. 1
+// and records the system after each step -- level k, with u(0 .. k) eliminated, bounds a loop of its own. After step k succeeds
+// its rows go -- whole cells across the lanes, from LDS or from the side just written -- to out(k) and their count to cnt(k),
+// BEFORE they are loaded as step k+1's input (the next step normalises its input in place).
+//   okv 1, steps n:      every level is stored (after an empty intermediate every later level has 0 rows)
+//   okv 0, steps k:      step k found the system inconsistent
+//   okv -need, steps k:  need > cap: step k's unreduced result needs `need` rows; cap_out < need <= cap: level k's reduced result
+//                        has `need` rows and does not fit its slot. The two cannot be confused: a reduced result never has more
+//                        rows than its step built, and that was at most cap.
+//   A system with okv <= 0 has 0 rows at EVERY level, those before its failing step included: lane 0 zeroes the counts it has
+//   already written (its stores keep their order).
+struct ChainEnd { int okv, steps; };
+template <bool KEEP_LEVELS, class Sys>
+__device__ __forceinline__ ChainEnd w_chain_walk(const Sys & y, R32 * const res_lds, R32 * const tmp_lds, R32 * const seat, const size_t slot,
+                                                 const int darkshadow, const int cap, const int cap_out, const int cap_lds, WScratch & s)
+{
+    const int cols = y.cols(), n = y.n();
+    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+    WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
+    w_load(tmp, y.in(), y.rows(), cols);
+    int okv = 1, steps = n, kept = 0, side = 0, k = 0;
+    for (; k < n; k++) {
+        const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * slot, cols, y.rhs(), y.u(k), darkshadow, cap, cap_lds, cap, s);
+        wave_sync();
+        if (st.over >= 0) { okv = -st.over; steps = k; break; }
+        if (!st.ok) { okv = 0; steps = k; break; }
+        if (KEEP_LEVELS) {
+            if (res.r > cap_out) { okv = -res.r; steps = k; break; }
+            if (res.r == 0) break;                                      // empty from here on: this and every later level
+            w_store(res, y.out(k));
+            if (lane_id() == 0) *y.cnt(k) = res.r;
+            if (k + 1 == n) { k = n; break; }
+        } else {
+            if (res.r == 0) break;                                      // empty from here on: every later step copies nothing
+            if (k + 1 == n) {
+                if (res.r > cap_out) okv = -res.r;
+                else { w_store(res, y.out(0)); kept = res.r; }
+                break;
+            }
+        }
+        w_load(tmp, res.a, res.r, cols);                                // from LDS, or from the side just written
+        if (!st.in_lds) side ^= 1;
+    }
+    if (lane_id() == 0) {
+        if (KEEP_LEVELS) { for (int j = okv == 1 ? k : 0; j < n; j++) *y.cnt(j) = 0; }   // the levels not reached; all after a failure
+        else *y.cnt(0) = kept;
+    }
+    ChainEnd e; e.okv = okv; e.steps = steps;
+    return e;
+}
+
+// mats [nb][rows][cols], seats [seats][2][cap][cols], outs [nb][cap_out][cols], out_rows [nb]
 __global__ __launch_bounds__(64) void k_fme_chain_batch(int nb, const R32 * mats, int rows, int cols, int rhs, ElimList el,
                                                         int darkshadow, R32 * seats, int cap, R32 * outs, int cap_out,
                                                         int * out_rows, int * out_ok, int * out_steps, int cap_lds, int sys_lds)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
-    R32 * const res_lds = (R32 *)lds;
-    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
-    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
-    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
-    R32 * const seat = seats + (size_t)sys_first() * 2 * cap * cols;
+    R32 * const res_lds = (R32 *)(lds_all + (size_t)threadIdx.y * sys_lds);
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * cols), cap);
+    const size_t slot = (size_t)cap * cols;
+    R32 * const seat = seats + (size_t)sys_first() * 2 * slot;
     LQ_CLEAR
     for (int b = sys_first(); b < nb; b += sys_stride()) {
-        w_load(tmp, mats + (size_t)b * rows * cols, rows, cols);
-        int okv = 1, steps = el.n, kept = 0, side = 0;
-        for (int k = 0; k < el.n; k++) {
-            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * cap * cols, cols, rhs, el.u[k], darkshadow, cap,
-                                          cap_lds, cap, s);
-            wave_sync();
-            if (st.over >= 0) { okv = -st.over; steps = k; break; }
-            if (!st.ok) { okv = 0; steps = k; break; }
-            if (res.r == 0) break;                                      // empty from here on: every later step copies nothing
-            if (k + 1 == el.n) {
-                if (res.r > cap_out) okv = -res.r;
-                else { w_store(res, outs + (size_t)b * cap_out * cols); kept = res.r; }
-                break;
-            }
-            w_load(tmp, res.a, res.r, cols);                            // from LDS, or from the side just written
-            if (!st.in_lds) side ^= 1;
-        }
-        if (lane_id() == 0) { out_rows[b] = kept; out_ok[b] = okv; out_steps[b] = steps; }
+        const UniformChain y = {{mats, rows, cols, rhs, 1, outs, cap_out, out_rows, b}, el};
+        const ChainEnd e = w_chain_walk<false>(y, res_lds, tmp_lds, seat, slot, darkshadow, cap, cap_out, cap_lds, s);
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_steps[b] = e.steps; }
         wave_sync();
         LQ_FLUSH
     }
 }
 
-// A projection that KEEPS EVERY LEVEL: loop-bound generation (LoopTran::transformIterSpace, eng/ldtran.cpp:178-196 and :241-257)
-// eliminates rhs-1 .. 1 and records the system after each step -- level k, with el.u[0 .. k] eliminated, bounds a loop of its
-// own. The walk is k_fme_chain_batch's (a wavefront per system, every step through w_fme_step, intermediates in the LDS result
-// area or in the seat's two alternating slots of `seats` [seats][2][cap][cols], seats reused above the grid) with a loop of
-// its own, so that the chain kernel keeps its text and its registers (profiles/lineq_levels_isa.txt). New is the store: after
-// step k succeeds its rows go -- whole cells across the lanes, from LDS or from the side just written -- to slot (b, k) of
-// outs [nb][el.n][cap_out][cols] and their count to out_rows [nb][el.n], BEFORE they are loaded as step k+1's input (the next
-// step normalises its input in place). Nothing is stored behind a level's rows.
-//   out_ok[b] 1, out_steps[b] el.n: every level is stored (after an empty intermediate every later level has 0 rows: fme of
-//                                   an empty system is true and empty)
-//   out_ok[b] 0, out_steps[b] k:    step k found the system inconsistent
-//   out_ok[b] -need, out_steps[b] k: need > cap: step k's unreduced result needs `need` rows; cap_out < need <= cap: level
-//                                   k's reduced result has `need` rows and does not fit its slot. The two cannot be confused:
-//                                   a reduced result never has more rows than its step built, and that was at most cap.
-// A system with out_ok[b] <= 0 has 0 rows at EVERY level, those before its failing step included: lane 0 zeroes the counts it
-// has already written (its stores keep their order), as k_calc_bound_batch does.
+// the same, every level kept: outs [nb][el.n][cap_out][cols], out_rows [nb][el.n]
 __global__ __launch_bounds__(64) void k_fme_levels_batch(int nb, const R32 * mats, int rows, int cols, int rhs, ElimList el,
                                                          int darkshadow, R32 * seats, int cap, R32 * outs, int cap_out,
                                                          int * out_rows, int * out_ok, int * out_steps, int cap_lds, int sys_lds)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
-    R32 * const res_lds = (R32 *)lds;
-    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
-    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
-    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
-    R32 * const seat = seats + (size_t)sys_first() * 2 * cap * cols;
+    R32 * const res_lds = (R32 *)(lds_all + (size_t)threadIdx.y * sys_lds);
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * cols), cap);
+    const size_t slot = (size_t)cap * cols;
+    R32 * const seat = seats + (size_t)sys_first() * 2 * slot;
     LQ_CLEAR
     for (int b = sys_first(); b < nb; b += sys_stride()) {
-        w_load(tmp, mats + (size_t)b * rows * cols, rows, cols);
-        int * const cnt = out_rows + (size_t)b * el.n;
-        int okv = 1, steps = el.n, side = 0, k = 0;
-        for (; k < el.n; k++) {
-            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * cap * cols, cols, rhs, el.u[k], darkshadow, cap,
-                                          cap_lds, cap, s);
-            wave_sync();
-            if (st.over >= 0) { okv = -st.over; steps = k; break; }
-            if (!st.ok) { okv = 0; steps = k; break; }
-            if (res.r > cap_out) { okv = -res.r; steps = k; break; }
-            if (res.r == 0) break;                                      // empty from here on: this and every later level
-            w_store(res, outs + ((size_t)b * el.n + k) * cap_out * cols);
-            if (lane_id() == 0) cnt[k] = res.r;
-            if (k + 1 < el.n) {
-                w_load(tmp, res.a, res.r, cols);                        // from LDS, or from the side just written
-                if (!st.in_lds) side ^= 1;
-            }
-        }
-        if (lane_id() == 0) {
-            for (int j = okv == 1 ? k : 0; j < el.n; j++) cnt[j] = 0;   // the levels not reached; all of them after a failure
-            out_ok[b] = okv; out_steps[b] = steps;
-        }
+        const UniformChain y = {{mats, rows, cols, rhs, el.n, outs, cap_out, out_rows, b}, el};
+        const ChainEnd e = w_chain_walk<true>(y, res_lds, tmp_lds, seat, slot, darkshadow, cap, cap_out, cap_lds, s);
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_steps[b] = e.steps; }
         wave_sync();
         LQ_FLUSH
     }
 }
 
-// The two walks above for systems of MIXED shapes and lists in one launch: the statements of a SCoP sit at different depths, so
-// rows, cols, rhs and the list rhs-1 .. 1 differ from system to system. A system is read from its descriptor in device memory
-// instead of from kernel arguments, its list from one concatenated array (no ElimList argument). The walk is unchanged -- a
-// wavefront per system, every step through w_fme_step, intermediates in the LDS result area or in the seat's two alternating
-// slots, seats reused above the grid -- and keeps a loop of its own, so that the two uniform kernels keep their text and their
-// registers (profiles/lineq_ragged_isa.txt).
-//   The LDS block, the seats and cap / cap_lds / cap_out belong to the LAUNCH: sized by the host from the envelope (the widest
-// system's `ecols`, the largest capacity: lineq_host.hip.h ragged_chain_plan), [result area (cap_lds x ecols)] [step input (cap
-// x ecols)] [scratch], each area at the same place for every system. INSIDE an area a system uses its OWN cols as row stride,
-// so its cells -- and with them every loop bound, divisor and result bit -- are those of the uniform kernels; a narrower system
-// leaves the tail of an area unused. cap_lds x ecols >= cap cells, so the row factors of a step fit the result area whatever
-// cols is; a step with need <= cap_lds rows is built in LDS (need x cols <= cap_lds x ecols cells).
-//   Consecutive systems of one wavefront may differ in cols, rows and list. Nothing of the previous system is read: w_load
-// writes the rows x cols cells every later loop is bounded by; w_fme_step writes bad_at, kind[0 .. rows), the row lists, drop[]
-// and the factors before it reads them (a factor only where its own drop[] entry, written in the same pass, says so); w_reduce
-// and w_remove_iden write map[] / removed[] / kind[] for [0, m.r) first. The one read past a live entry -- w_iden_rows' four
-// hashes per trip, up to three behind the last row -- is inside the scratch of cap + 1 entries and cannot change a result
-// (a row's own index is visited after any larger one), whatever an earlier system of another width left there. The scratch
-// itself never moves with cols. The wave_sync that ends a system orders lane 0's verdicts and every lane's LDS reads before the
-// next system's w_load, as in the uniform kernels.
-//   outs: the slot(s) of system b start at cell d.out_off, cap_out x d.cols cells each. KEEP_LEVELS false: one slot, the last
-// step's rows, out_rows[b] (k_fme_chain_batch's verdicts). KEEP_LEVELS true: slot k receives level k and out_rows[d.list_at + k]
-// its count (k_fme_levels_batch's verdicts, the counts of a failed system zeroed in the same way). `need` is judged against
-// the launch's cap / cap_out.
-struct RaggedSys { long long in_off, out_off; int rows, cols, rhs, list_at, list_n, pad; };
+// Both for systems of mixed shapes: a whole wavefront per system (block (64, 1), what lineq_geom gives fme), the seat is the
+// workgroup, the system index is uniform and its descriptor comes in as scalars. Indexing a descriptor by threadIdx.y instead
+// costs 128 / 138 VGPRs (profiles/lineq_ragged_isa.txt), which is why the uniform kernels are not this one.
 template <bool KEEP_LEVELS>
 __global__ __launch_bounds__(64) void k_fme_chain_ragged(int nb, const RaggedSys * __restrict__ sys, const int * __restrict__ lists,
                                                          const R32 * mats, int darkshadow, R32 * seats, int cap, int ecols, R32 * outs,
                                                          int cap_out, int * out_rows, int * out_ok, int * out_steps, int cap_lds)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    // a whole wavefront per system (block (64, 1), what lineq_geom gives fme): the seat is the workgroup, the system index is
-    // uniform and its descriptor comes in as scalars
     R32 * const res_lds = (R32 *)lds_all;
     R32 * const tmp_lds = res_lds + (size_t)cap_lds * ecols;
     WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * ecols), cap);
@@ -787,40 +718,9 @@ __global__ __launch_bounds__(64) void k_fme_chain_ragged(int nb, const RaggedSys
     LQ_CLEAR
     for (int b = (int)blockIdx.x; b < nb; b += (int)gridDim.x) {
         const RaggedSys d = sys[b];
-        const int cols = d.cols, n = d.list_n;
-        const int * const el = lists + d.list_at;
-        WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
-        WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
-        w_load(tmp, mats + d.in_off, d.rows, cols);
-        int * const cnt = out_rows + (KEEP_LEVELS ? d.list_at : b);
-        int okv = 1, steps = n, kept = 0, side = 0, k = 0;
-        for (; k < n; k++) {
-            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (size_t)side * slot, cols, d.rhs, el[k], darkshadow, cap, cap_lds, cap, s);
-            wave_sync();
-            if (st.over >= 0) { okv = -st.over; steps = k; break; }
-            if (!st.ok) { okv = 0; steps = k; break; }
-            if (KEEP_LEVELS) {
-                if (res.r > cap_out) { okv = -res.r; steps = k; break; }
-                if (res.r == 0) break;                                  // empty from here on: this and every later level
-                w_store(res, outs + d.out_off + (size_t)k * cap_out * cols);
-                if (lane_id() == 0) cnt[k] = res.r;
-                if (k + 1 == n) { k = n; break; }
-            } else {
-                if (res.r == 0) break;                                  // empty from here on: every later step copies nothing
-                if (k + 1 == n) {
-                    if (res.r > cap_out) okv = -res.r;
-                    else { w_store(res, outs + d.out_off); kept = res.r; }
-                    break;
-                }
-            }
-            w_load(tmp, res.a, res.r, cols);                            // from LDS, or from the side just written
-            if (!st.in_lds) side ^= 1;
-        }
-        if (lane_id() == 0) {
-            if (KEEP_LEVELS) { for (int j = okv == 1 ? k : 0; j < n; j++) cnt[j] = 0; }   // the levels not reached; all after a failure
-            else cnt[0] = kept;
-            out_ok[b] = okv; out_steps[b] = steps;
-        }
+        const RaggedView y = {d, lists, mats, outs, cap_out, out_rows, KEEP_LEVELS ? d.list_at : b};
+        const ChainEnd e = w_chain_walk<KEEP_LEVELS>(y, res_lds, tmp_lds, seat, slot, darkshadow, cap, cap_out, cap_lds, s);
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_steps[b] = e.steps; }
         wave_sync();
         LQ_FLUSH
     }
@@ -831,108 +731,101 @@ __global__ __launch_bounds__(64) void k_fme_chain_ragged(int nb, const RaggedSys
 // chain starts with a prefix of rhs-1 .. 1: with P_j the system with the variables above j eliminated (P_{rhs-1} the input,
 // P_{j-1} = fme(P_j, j)), chain j is P_j followed by the tail j-1 .. 0. The prefixes are walked once, j = rhs-1 down to 0:
 // (rhs-1) + rhs(rhs-1)/2 steps per system instead of rhs(rhs-1). fme is a pure function of its input matrix and u, so every
-// result has the bits the chain run on its own has. LDS of a seat as in k_fme_chain_batch; `seats` is [seats][3][cap][cols]:
-// two alternating sides for the intermediates that do not fit cap_lds rows, and a HOLD slot for the current prefix P_j (a
-// step normalises its input in place, so P_j is loaded twice: for its tail and for the step that makes P_{j-1}).
-// outs [nb][rhs][cap_out][cols], out_rows [nb][rhs]; nothing is stored behind a result's rows.
-//   out_ok[b] 1, out_chain[b] -1, out_steps[b] 0: every chain ran (a chain with an empty intermediate ends empty and ok)
+// result has the bits the chain run on its own has. A seat has THREE slots of `slot` cells here: the two sides, and a HOLD slot
+// for the current prefix P_j (a step normalises its input in place, so P_j is loaded twice: for its tail and for the step that
+// makes P_{j-1}). The hold slot is READ only where `held` is true, and `held` starts false with every system and becomes true
+// only after this system's own prefix step has put res.r rows x OWN cols there (built in place, or w_store from LDS) -- pj_rows
+// is that res.r, so the load reads exactly the cells written, never those of an earlier system. fin_res / fin_r / tok are reset
+// per chain. Result j goes to out(j), its count to cnt(j); nothing is stored behind a result's rows. rhs == 1: no step, the one
+// result is the input, unreduced.
+//   okv 1, chain -1, steps 0: every chain ran (a chain with an empty intermediate ends empty and ok)
 //   else the verdict of the LOWEST failing chain, the one the reference meets first (it runs j = 0 first and returns):
-//   out_ok[b] 0 (inconsistent) or -need (step out_steps[b] of chain out_chain[b] needs `need` > cap rows, or, with
-//   out_steps[b] == rhs - 1, that chain's final result has `need` > cap_out rows); all rhs counts of the system are 0.
+//   okv 0 (inconsistent) or -need (step `steps` of chain `chain` needs `need` > cap rows, or, with steps == rhs - 1, that
+//   chain's final result has `need` > cap_out rows); all rhs counts of the system are 0.
 // A prefix step is a step of chain 0 (index rhs-1-u) and of every chain below u: its failure ends the walk. A failing tail is
 // recorded and the walk goes on -- a lower chain may fail in another way, and overwrites the record.
+struct BoundEnd { int okv, chain, steps; };
+template <class Sys>
+__device__ __forceinline__ BoundEnd w_calc_bound_walk(const Sys & y, R32 * const res_lds, R32 * const tmp_lds, R32 * const seat, const int slot,
+                                                      const int cap, const int cap_out, const int cap_lds, WScratch & s)
+{
+    const int cols = y.cols(), rhs = y.rhs();
+    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
+    WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
+    bool held = false;                                                  // P_j: the input, then the hold slot
+    int pj_rows = y.rows();
+    int okv = 1, chain = -1, steps = 0, side = 0;
+    bool walk = true;
+    for (int j = rhs - 1; j >= 0 && walk; j--) {
+        w_load(tmp, held ? seat + 2 * slot : y.in(), pj_rows, cols);
+        bool fin_res = false;                                           // no step (j == 0, or P_j empty): P_j itself, unreduced
+        int fin_r = pj_rows;
+        int tok = 1, tstep = 0;
+        // t < j: step t of chain j's tail, u = j-1-t (index rhs-2-u of the chain's list); t == j: the tail is stored, then
+        // the prefix step u = j. One call site of the step for both (two: 138 VGPRs against 132, profiles/calc_bound_isa.txt).
+        for (int t = 0; t <= j; t++) {
+            const bool prefix = t == j;
+            if (prefix) {
+                int kept = 0;
+                if (tok == 1) {
+                    if (fin_r > cap_out) { tok = -fin_r; tstep = rhs - 1; }
+                    else { if (fin_res) w_store(res, y.out(j)); else w_store(tmp, y.out(j)); kept = fin_r; }
+                }
+                if (tok != 1) { okv = tok; chain = j; steps = tstep; }
+                if (lane_id() == 0) *y.cnt(j) = kept;
+                wave_sync();
+                if (j == 0 || pj_rows == 0) break;                      // (an empty prefix stays empty)
+                // P_j again: the tail's first step normalised it in place
+                w_load(tmp, held ? seat + 2 * slot : y.in(), pj_rows, cols);
+            } else if (tok != 1 || fin_r == 0) continue;                // (empty from here on: every later step copies nothing)
+            const int u = prefix ? j : j - 1 - t;
+            const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (prefix ? 2 : side) * slot, cols, rhs, u, 0, cap, cap_lds, cap, s);
+            wave_sync();
+            if (st.over >= 0 || !st.ok) {
+                const int v = st.over >= 0 ? -st.over : 0;
+                if (prefix) { okv = v; chain = 0; steps = rhs - 1 - j; walk = false; }
+                else { tok = v; tstep = rhs - 2 - u; }
+            } else if (prefix) {
+                if (st.in_lds) w_store(res, seat + 2 * slot);           // else it was built there
+                held = true; pj_rows = res.r;
+                wave_sync();
+            } else {
+                fin_res = true; fin_r = res.r;
+                if (u > 0 && res.r > 0) {
+                    w_load(tmp, res.a, res.r, cols);                    // from LDS, or from the side just written
+                    if (!st.in_lds) side ^= 1;
+                }
+            }
+        }
+    }
+    if (lane_id() == 0 && okv != 1)                                     // (lane 0 wrote the counts: its stores keep their order)
+        for (int j = 0; j < rhs; j++) *y.cnt(j) = 0;
+    BoundEnd e; e.okv = okv; e.chain = chain; e.steps = steps;
+    return e;
+}
+
+// mats [nb][rows][cols], seats [seats][3][cap][cols], outs [nb][rhs][cap_out][cols], out_rows [nb][rhs]
 __global__ __launch_bounds__(64) void k_calc_bound_batch(int nb, const R32 * mats, int rows, int cols, int rhs, R32 * seats, int cap,
                                                          R32 * outs, int cap_out, int * out_rows, int * out_ok, int * out_chain,
                                                          int * out_steps, int cap_lds, int sys_lds)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    unsigned char * lds = lds_all + (size_t)threadIdx.y * sys_lds;
-    R32 * const res_lds = (R32 *)lds;
-    WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
-    WMat tmp; tmp.a = res_lds + (size_t)cap_lds * cols; tmp.ld = cols;
-    WScratch s = carve_scratch((unsigned char *)(tmp.a + (size_t)cap * cols), cap);
+    R32 * const res_lds = (R32 *)(lds_all + (size_t)threadIdx.y * sys_lds);
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * cols), cap);
     const int slot = cap * cols;                                        // (cells; the LDS layout holds as many, so they fit an int)
     R32 * const seat = seats + (size_t)sys_first() * 3 * slot;          // sides 0 and 1, then the hold slot
     LQ_CLEAR
     for (int b = sys_first(); b < nb; b += sys_stride()) {
-        bool held = false;                                              // P_j: the input, then the hold slot
-        int pj_rows = rows;
-        int okv = 1, chain = -1, steps = 0, side = 0;
-        bool walk = true;
-        for (int j = rhs - 1; j >= 0 && walk; j--) {
-            w_load(tmp, held ? seat + 2 * slot : mats + (size_t)b * rows * cols, pj_rows, cols);
-            bool fin_res = false;                                       // no step (j == 0, or P_j empty): P_j itself, unreduced
-            int fin_r = pj_rows;
-            int tok = 1, tstep = 0;
-            // t < j: step t of chain j's tail, u = j-1-t (index rhs-2-u of the chain's list); t == j: the tail is stored, then
-            // the prefix step u = j. One call site of the step for both (two: 138 VGPRs against 132, profiles/calc_bound_isa.txt).
-            for (int t = 0; t <= j; t++) {
-                const bool prefix = t == j;
-                if (prefix) {
-                    int kept = 0;
-                    if (tok == 1) {
-                        R32 * const dst = outs + ((size_t)b * rhs + j) * cap_out * cols;
-                        if (fin_r > cap_out) { tok = -fin_r; tstep = rhs - 1; }
-                        else { if (fin_res) w_store(res, dst); else w_store(tmp, dst); kept = fin_r; }
-                    }
-                    if (tok != 1) { okv = tok; chain = j; steps = tstep; }
-                    if (lane_id() == 0) out_rows[(size_t)b * rhs + j] = kept;
-                    wave_sync();
-                    if (j == 0 || pj_rows == 0) break;                  // (an empty prefix stays empty)
-                    // P_j again: the tail's first step normalised it in place
-                    w_load(tmp, held ? seat + 2 * slot : mats + (size_t)b * rows * cols, pj_rows, cols);
-                } else if (tok != 1 || fin_r == 0) continue;            // (empty from here on: every later step copies nothing)
-                const int u = prefix ? j : j - 1 - t;
-                const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (prefix ? 2 : side) * slot, cols, rhs, u, 0, cap, cap_lds, cap, s);
-                wave_sync();
-                if (st.over >= 0 || !st.ok) {
-                    const int v = st.over >= 0 ? -st.over : 0;
-                    if (prefix) { okv = v; chain = 0; steps = rhs - 1 - j; walk = false; }
-                    else { tok = v; tstep = rhs - 2 - u; }
-                } else if (prefix) {
-                    if (st.in_lds) w_store(res, seat + 2 * slot);       // else it was built there
-                    held = true; pj_rows = res.r;
-                    wave_sync();
-                } else {
-                    fin_res = true; fin_r = res.r;
-                    if (u > 0 && res.r > 0) {
-                        w_load(tmp, res.a, res.r, cols);                // from LDS, or from the side just written
-                        if (!st.in_lds) side ^= 1;
-                    }
-                }
-            }
-        }
-        if (lane_id() == 0) {                                           // (lane 0 wrote the counts: its stores keep their order)
-            if (okv != 1) for (int j = 0; j < rhs; j++) out_rows[(size_t)b * rhs + j] = 0;
-            out_ok[b] = okv; out_chain[b] = chain; out_steps[b] = steps;
-        }
+        const UniformSys y = {mats, rows, cols, rhs, rhs, outs, cap_out, out_rows, b};
+        const BoundEnd e = w_calc_bound_walk(y, res_lds, tmp_lds, seat, slot, cap, cap_out, cap_lds, s);
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_chain[b] = e.chain; out_steps[b] = e.steps; }
         wave_sync();
         LQ_FLUSH
     }
 }
 
-// k_calc_bound_batch's walk for systems of MIXED shapes in one launch: the statements of a SCoP sit at different depths, so
-// rows, cols and rhs differ from system to system. The walk is the uniform kernel's, statement for statement -- the prefixes
-// P_j walked once, the tail per variable, the hold slot and the two sides, the verdict of the lowest failing chain, one call
-// site of w_fme_step for tail and prefix -- in a kernel of its own, so that the uniform kernel keeps its text and its registers
-// (profiles/lineq_bounds_ragged_isa.txt). The addressing is k_fme_chain_ragged's: block (64, 1), the seat is the workgroup, the
-// system index is uniform and its descriptor (RaggedSys; there is no list, so list_at carries the FIRST RESULT INDEX of the
-// system, the sum of the rhs before it, and list_n its rhs: k_ragged_cells / k_pack_ragged serve in their levels mode) comes in
-// as scalars. The LDS block, the seats and cap / cap_lds / cap_out belong to the LAUNCH (lineq_host.hip.h bounds_ragged_plan):
-// [result area (cap_lds x ecols)] [step input (cap x ecols)] [scratch], a seat THREE slots of cap x ecols cells (sides 0 and 1,
-// then the hold slot). INSIDE an area or a slot a system uses its OWN cols as row stride, so every cell, loop bound and result
-// bit is the uniform kernel's; cap rows x cols <= cap x ecols cells, so nothing a step may build (need <= cap, else a verdict
-// before any row is written past nfree <= rows <= cap) leaves its slot.
-//   Consecutive systems of one wavefront differ in rows, cols and rhs. What k_fme_chain_ragged's comment says of w_load,
-// w_fme_step, w_reduce / w_remove_iden and w_iden_rows' read behind the last row holds here unchanged, for they are the only
-// helpers called. The hold slot adds one thing to check: it is READ only where `held` is true, and `held` starts false with
-// every system and becomes true only after this system's own prefix step has put res.r rows x OWN cols there (built in place,
-// or w_store from LDS) -- pj_rows is that res.r, so the load reads exactly the cells written, never those of an earlier
-// system of another width. The sides are read (w_load from res.a) only in the step after the one that wrote them. fin_res /
-// fin_r / tok are reset per chain as in the uniform kernel.
-//   outs: result j of system b in its own slot of cap_out x cols cells at d.out_off + j * cap_out * cols; out_rows[first + j]
-// its count; out_ok / out_chain / out_steps [nb], k_calc_bound_batch's verdicts with `need` judged against the launch's cap /
-// cap_out; the counts of a failed system zeroed in the same way. rhs == 1: no step, the one result is the input, unreduced.
+// the same for systems of mixed shapes, addressed as k_fme_chain_ragged addresses them (there is no list)
 __global__ __launch_bounds__(64) void k_calc_bound_ragged(int nb, const RaggedSys * __restrict__ sys, const R32 * mats, R32 * seats, int cap,
                                                           int ecols, R32 * outs, int cap_out, int * out_rows, int * out_ok, int * out_chain,
                                                           int * out_steps, int cap_lds)
@@ -946,62 +839,9 @@ __global__ __launch_bounds__(64) void k_calc_bound_ragged(int nb, const RaggedSy
     LQ_CLEAR
     for (int b = (int)blockIdx.x; b < nb; b += (int)gridDim.x) {
         const RaggedSys d = sys[b];
-        const int cols = d.cols, rhs = d.rhs;
-        const R32 * const in = mats + d.in_off;
-        int * const cnt = out_rows + d.list_at;
-        WMat res; res.a = res_lds; res.ld = cols; res.c = cols;
-        WMat tmp; tmp.a = tmp_lds; tmp.ld = cols;
-        bool held = false;                                              // P_j: the input, then the hold slot
-        int pj_rows = d.rows;
-        int okv = 1, chain = -1, steps = 0, side = 0;
-        bool walk = true;
-        for (int j = rhs - 1; j >= 0 && walk; j--) {
-            w_load(tmp, held ? seat + 2 * slot : in, pj_rows, cols);
-            bool fin_res = false;                                       // no step (j == 0, or P_j empty): P_j itself, unreduced
-            int fin_r = pj_rows;
-            int tok = 1, tstep = 0;
-            // t < j: step t of chain j's tail, u = j-1-t; t == j: the tail is stored, then the prefix step u = j (one call site
-            // of the step for both, as in k_calc_bound_batch)
-            for (int t = 0; t <= j; t++) {
-                const bool prefix = t == j;
-                if (prefix) {
-                    int kept = 0;
-                    if (tok == 1) {
-                        R32 * const dst = outs + d.out_off + (size_t)j * cap_out * cols;
-                        if (fin_r > cap_out) { tok = -fin_r; tstep = rhs - 1; }
-                        else { if (fin_res) w_store(res, dst); else w_store(tmp, dst); kept = fin_r; }
-                    }
-                    if (tok != 1) { okv = tok; chain = j; steps = tstep; }
-                    if (lane_id() == 0) cnt[j] = kept;
-                    wave_sync();
-                    if (j == 0 || pj_rows == 0) break;                  // (an empty prefix stays empty)
-                    // P_j again: the tail's first step normalised it in place
-                    w_load(tmp, held ? seat + 2 * slot : in, pj_rows, cols);
-                } else if (tok != 1 || fin_r == 0) continue;            // (empty from here on: every later step copies nothing)
-                const int u = prefix ? j : j - 1 - t;
-                const FmeStep st = w_fme_step(tmp, res, res_lds, seat + (prefix ? 2 : side) * slot, cols, rhs, u, 0, cap, cap_lds, cap, s);
-                wave_sync();
-                if (st.over >= 0 || !st.ok) {
-                    const int v = st.over >= 0 ? -st.over : 0;
-                    if (prefix) { okv = v; chain = 0; steps = rhs - 1 - j; walk = false; }
-                    else { tok = v; tstep = rhs - 2 - u; }
-                } else if (prefix) {
-                    if (st.in_lds) w_store(res, seat + 2 * slot);       // else it was built there
-                    held = true; pj_rows = res.r;
-                    wave_sync();
-                } else {
-                    fin_res = true; fin_r = res.r;
-                    if (u > 0 && res.r > 0) {
-                        w_load(tmp, res.a, res.r, cols);                // from LDS, or from the side just written
-                        if (!st.in_lds) side ^= 1;
-                    }
-                }
-            }
-        }
-        if (lane_id() == 0) {                                           // (lane 0 wrote the counts: its stores keep their order)
-            if (okv != 1) for (int j = 0; j < rhs; j++) cnt[j] = 0;
-            out_ok[b] = okv; out_chain[b] = chain; out_steps[b] = steps;
-        }
+        const RaggedView y = {d, (const int *)0, mats, outs, cap_out, out_rows, d.list_at};
+        const BoundEnd e = w_calc_bound_walk(y, res_lds, tmp_lds, seat, slot, cap, cap_out, cap_lds, s);
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_chain[b] = e.chain; out_steps[b] = e.steps; }
         wave_sync();
         LQ_FLUSH
     }
