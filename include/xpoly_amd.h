@@ -693,7 +693,10 @@ int xpg_dep_is_empty_batch_ex_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mat
  *   XPG_DEP_SYMBOLS_AS_VARS  OPT-IN, NOT PARITY: the evident intent of src/eng/poly.cpp:530-573 -- after move2var the symbols
  *                            are variables of unknown sign, so has_solution(int, unique) is asked about the widened system:
  *                            rhs_idx = cols - 1, vc widened by all-zero (= free) rows and columns for the symbols.  Checked
- *                            against the CPU restatement's move2var + reduce + has_solution on that widened system. */
+ *                            against the CPU restatement's move2var + reduce + has_solution on that widened system.
+ * (The one other answer of this library that is not the reference's: a list of polyhedra one of whose members fails calcBound
+ * -- xpg_lineq_hull_batch_ragged_rat32's out_member, below: the group has no rows, where the reference's release build goes on
+ * with stale bounds.  That, too, answers a violated precondition, not a result.) */
 enum { XPG_DEP_PARITY = 0, XPG_DEP_SYMBOLS_AS_VARS = 1 };
 int xpg_dep_is_empty_batch_mode_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx,
                                       const xpg_rat32 * vc, int mode, int32_t * out_empty, long long * out_nodes);
@@ -1014,6 +1017,73 @@ int xpg_lineq_bounds_ragged_last_route(long long * out, int n);
  * envelope.  Fills min(n, 12) entries. */
 int xpg_test_lineq_bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows,
                                       int cap_out_rows, long long * out, int n);
+/* Lineq::ConvexHullUnionAndIntersect (src/com/linsys.cpp:283-336) for MANY lists of polyhedra in one call.  The members are laid
+ * out exactly as xpg_lineq_bounds_batch_ragged_rat32 takes its systems; group_offsets [n_groups + 1] partitions them: group g is
+ * the list of members group_offsets[g] .. group_offsets[g + 1] - 1, in list order.  Members of one group must share cols and
+ * rhs_idx (the reference's "homotype" assertion); their row counts may differ, groups may differ in everything.  Per group:
+ * calcBound on every member (ONE launch of the ragged calcBound kernel over all members), every variable's bounds -- members in
+ * list order, inside a member the variables 0 .. rhs_idx-1, empty bounds skipped -- appended to a matrix that begins with one
+ * zero row (the reference's res.reinit(1, cols)), and Lineq::reduce(res, rhs_idx, is_intersect) over the lot: a second launch on
+ * the same stream, one wavefront per group, no host synchronisation between the two.  One upload, one synchronisation.
+ * is_intersect == 0: the widest bounds (the union's bounding hull); else the tightest.  Result rows come in gather order.
+ *   cap_rows, cap_out_rows   the members' calcBound capacities, as xpg_lineq_bounds_batch_ragged_rat32
+ *   cap_hull_rows            rows a group may gather, lead row included; <= 0: the largest 1 + 2 * rhs_idx * members of any
+ *                            group, at most 32767; > 32767: XPG_ERR_UNSUPPORTED (reduce indexes rows as 16-bit)
+ *   out_cell_offsets [n_groups + 1], out_rows [n_groups]: group g's out_rows[g] rows, its cols wide, start at CELL
+ *                            out_cell_offsets[g]
+ *   out_ok, out_member, out_chain, out_steps [n_groups]:
+ *     out_ok 1, out_member -1     every member's calcBound succeeded and reduce returned true: the rows are reduce's
+ *     out_ok 0, out_member -1     reduce returned false.  is_intersect: 0 rows (the reference's res.clean()); else the rows as
+ *                                 reduce leaves them, after removeIdenRow, uncompacted -- what xpg_lineq_reduce_batch_rat32
+ *                                 returns for an inconsistent system
+ *     out_member m >= 0           member m of the group (the LOWEST such) did not succeed: out_ok (0 or -need), out_chain and
+ *                                 out_steps are that member's calcBound verdict, the group has 0 rows, reduce is not run.
+ *                                 STATED DEVIATION, NOT PARITY: the reference's release build compiles the ASSERT on calcBound
+ *                                 out and goes on with the bounds left over from the previous member.  This answers a violated
+ *                                 precondition, not a result.
+ *     out_ok -need, out_member -1 the group gathers need > cap_hull_rows rows: 0 rows; the other groups are answered all the same
+ *     a group without members     0 rows, out_ok 1
+ * outs / outs_cap_cells / out_view / a sizing call (neither) / XPG_ERR_SHAPE with offsets, counts and verdicts filled: as
+ * xpg_lineq_bounds_batch_ragged_rat32.  Decided before anything is launched: XPG_ERR_SHAPE -- members of a group that differ in
+ * cols or rhs_idx, group_offsets not starting at 0, not monotone or not ending at n_members, and what the ragged calcBound
+ * refuses; XPG_ERR_UNSUPPORTED -- cap_hull_rows > 32767, the group kernel's LDS (32 KB of rows and the scratch of cap_hull_rows)
+ * over 160 KB, and what the ragged calcBound refuses.  n_groups == 0 (and n_members == 0): 0, out_cell_offsets[0] = 0.
+ * A group's matrix is gathered in LDS where its gathered capacity min(cap_hull_rows, 1 + members * rhs_idx * cap_out_rows) rows
+ * of its own cols fit the LDS rows of the call, else in a device slot of its workgroup.  There is no _dev form. */
+int xpg_lineq_hull_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, const int32_t * group_offsets, int n_members, const xpg_rat32 * mats,
+                                      const int32_t * rows, const int32_t * cols, const long long * offsets, const int32_t * rhs_idx,
+                                      int is_intersect, int cap_rows, int cap_out_rows, int cap_hull_rows, xpg_rat32 * outs,
+                                      long long outs_cap_cells, const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows,
+                                      int32_t * out_ok, int32_t * out_member, int32_t * out_chain, int32_t * out_steps);
+/* The projected union of PolyTran::step_4 (src/eng/poly.cpp:4802-4823) for many groups: every member is projected by its own
+ * elimination list (elim / elim_offsets / darkshadow per member, as xpg_lineq_project_batch_ragged_rat32: one launch of the
+ * ragged chain kernel), the results of a group's members are concatenated in list order -- no lead row -- and ONE
+ * Lineq::reduce(ub, rhs_idx, is_intersect) runs per group (step_4 passes 0).  Everything else as
+ * xpg_lineq_hull_batch_ragged_rat32: a member's verdict is the chain's (out_ok, out_steps; out_chain is -1), cap_hull_rows <= 0 is
+ * the largest 2 * rhs_idx * members of any group, a group's gathered capacity is min(cap_hull_rows, members * cap_out_rows). */
+int xpg_lineq_project_union_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, const int32_t * group_offsets, int n_members, const xpg_rat32 * mats,
+                                               const int32_t * rows, const int32_t * cols, const long long * offsets, const int32_t * rhs_idx,
+                                               const int32_t * elim, const int32_t * elim_offsets, int darkshadow, int is_intersect,
+                                               int cap_rows, int cap_out_rows, int cap_hull_rows, xpg_rat32 * outs, long long outs_cap_cells,
+                                               const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok,
+                                               int32_t * out_member, int32_t * out_chain, int32_t * out_steps);
+/* Evidence, no reference counterpart: what the calling thread's last hull or projected-union call did (one record serves both).
+ * out[0] launches of the producer (1; 0 where nothing was launched), [1] launches of the group kernel (1), [2] its grid, [3] its
+ * LDS bytes per workgroup, [4] groups whose home is LDS, [5] groups whose home is a device slot (groups without members are in
+ * neither), [6] bytes of the producer's intermediate slots, [7] bytes of the workgroups' device slots (0 where no group needs
+ * one), [8] bytes of the output slots -- the producer's, and one more slot per group with a lead row; a group's result goes to
+ * the front of its own members' slots, nothing grows with n_groups * cap_hull_rows -- [9] rows gathered over all groups (lead
+ * rows included).  Fills min(n, 10) entries. */
+int xpg_lineq_hull_last_route(long long * out, int n);
+int xpg_lineq_project_union_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the plan of a hull call (elim_offsets NULL) or of a projected union from the
+ * shapes alone -- the function the launch itself asks, with its error codes.  out[0 .. 8] as the route, then [9] cap_rows, [10]
+ * cap_out_rows, [11] cap_hull_rows as settled, [12] rows of the LDS matrix area at [13] the envelope's columns.  homes [n_groups]
+ * (may be NULL): 0 LDS, 1 device slot, -1 no members; gcaps [n_groups] (may be NULL): each group's gathered capacity.  Fills
+ * min(n, 14) entries. */
+int xpg_test_lineq_hull_plan(int n_groups, const int32_t * group_offsets, int n_members, const int32_t * rows, const int32_t * cols,
+                             const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets, int cap_rows, int cap_out_rows,
+                             int cap_hull_rows, long long * out, int n, int32_t * homes, int32_t * gcaps);
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank);
 int xpg_rat_rank_batch(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols,
                        int32_t * out_rank);

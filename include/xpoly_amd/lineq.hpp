@@ -10,7 +10,7 @@
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
 // should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
-// levels_all, project_each, levels_nests, calc_bound_all -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
+// levels_all, project_each, levels_nests, calc_bound_all, calc_bound_each, hull_all, project_union_each -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
 #define XPOLY_AMD_LINEQ_HPP
@@ -24,6 +24,14 @@
 #include "six.hpp"
 
 namespace xpoly_amd {
+
+namespace detail {
+// (defined below the collectors: the one call behind Lineq::ConvexHullUnionAndIntersect, hull_all and project_union_each)
+template <class RMatT>
+int hull_groups(const std::vector<std::vector<RMatT *> > & groups, const std::vector<int32_t> & rhs_idx,
+                const std::vector<std::vector<std::vector<int32_t> > > * elims, bool darkshadow, bool is_intersect, std::vector<RMatT> & results,
+                std::vector<int32_t> & ok, std::vector<int32_t> * member, xpg_ctx * c);
+}
 
 template <class RMatT> class Lineq {
     xpg_ctx * m_ctx;
@@ -296,6 +304,33 @@ public:
         if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { put_rows(*dst[(size_t)pos], a, r, c); })) return false;
         if (A) *A = *dst.back();
         return true;
+    }
+    // Lineq::ConvexHullUnionAndIntersect, linsys.cpp:283-336, with the reference's signature: calcBound on every polyhedron of
+    // `chlst` (all of one dimension), every variable's bounds appended behind one zero row, and reduce(res, rhs_idx,
+    // is_intersect) over the lot -- the widest bounds (the union's bounding hull) or the tightest; an inconsistent intersection
+    // and an empty list clean `res`. ONE library call (xpg_lineq_hull_batch_ragged_rat32 with one group: two launches, one
+    // synchronisation); many lists at once: hull_all, below. STATED DEVIATION: where calcBound fails on a member the reference's
+    // release build goes on with the bounds of the member before; here `res` is cleaned (a violated precondition, not a result).
+    //   void ConvexHullUnionAndIntersect(RMat & res, ListT & chlst, unsigned rhs_idx, bool is_intersect)   -- a list with
+    //                                             get_head / get_next / get_elem_count (the reference's List<RMat*>)
+    //   void ConvexHullUnionAndIntersect(RMat & res, std::vector<RMat *> & chlst, unsigned rhs_idx, bool is_intersect)
+    void ConvexHullUnionAndIntersect(RMatT & res, std::vector<RMatT *> & chlst, unsigned rhs_idx, bool is_intersect)
+    {
+        if (chlst.empty()) { res.clean(); return; }                 // linsys.cpp:289-292
+        std::vector<std::vector<RMatT *> > groups(1, chlst);
+        std::vector<RMatT> out;
+        std::vector<int32_t> ok, member;
+        if (detail::hull_groups(groups, std::vector<int32_t>(1, (int32_t)rhs_idx), (const std::vector<std::vector<std::vector<int32_t> > > *)0, false,
+                                is_intersect, out, ok, &member, ctx()) != 0 || member[0] >= 0 || ok[0] < 0 || out[0].size() == 0) { res.clean(); return; }
+        res = out[0];
+    }
+    template <class ListT, class = decltype(std::declval<ListT &>().get_head()), class = decltype(std::declval<ListT &>().get_next()),
+              class = decltype(std::declval<ListT &>().get_elem_count())>
+    void ConvexHullUnionAndIntersect(RMatT & res, ListT & chlst, unsigned rhs_idx, bool is_intersect)
+    {
+        std::vector<RMatT *> v;
+        for (RMatT * p = chlst.get_head(); p != 0; p = chlst.get_next()) v.push_back(p);
+        ConvexHullUnionAndIntersect(res, v, rhs_idx, is_intersect);
     }
 };
 
@@ -812,6 +847,115 @@ inline int calc_bound_each(const std::vector<RMatT *> & systems, const std::vect
         return 0;
     }
     return XPG_ERR_UNSUPPORTED;
+}
+
+namespace detail {
+// The one call behind the hull collectors: the members of every group packed once, xpg_lineq_hull_batch_ragged_rat32 (elims
+// NULL) or xpg_lineq_project_union_batch_ragged_rat32. Where a group reports -need the call is made again with the largest need
+// reported -- of a member (above the cap_rows tried: a step's unreduced rows; else a result's slot, cap_out_rows) or of a group
+// (member -1: cap_hull_rows) -- at most three times; still short: XPG_ERR_UNSUPPORTED.
+template <class RMatT>
+inline int hull_groups(const std::vector<std::vector<RMatT *> > & groups, const std::vector<int32_t> & rhs_idx,
+                       const std::vector<std::vector<std::vector<int32_t> > > * elims, bool darkshadow, bool is_intersect, std::vector<RMatT> & results,
+                       std::vector<int32_t> & ok, std::vector<int32_t> * member, xpg_ctx * c)
+{
+    const int ng = (int)groups.size();
+    if ((int)rhs_idx.size() != ng || (elims && (int)elims->size() != ng)) return XPG_ERR_SHAPE;
+    results.assign((size_t)ng, RMatT());
+    ok.assign((size_t)ng, 0);
+    if (member) member->assign((size_t)ng, -1);
+    if (ng == 0) return 0;
+    xpg_ctx * h = c ? c : shared_context();
+    std::vector<int32_t> goff((size_t)ng + 1, 0), rows, cols, rhs, elim, eoff(1, 0);
+    std::vector<long long> off(1, 0);
+    int most = 0;
+    for (int g = 0; g < ng; g++) {
+        const std::vector<RMatT *> & grp = groups[(size_t)g];
+        if (elims && (*elims)[(size_t)g].size() != grp.size()) return XPG_ERR_SHAPE;
+        for (size_t i = 0; i < grp.size(); i++) {
+            const int r = grp[i]->size() == 0 ? 0 : (int)grp[i]->get_row_size(), cc = (int)grp[i]->get_col_size();
+            if (r == 0 || cc == 0) return XPG_ERR_SHAPE;
+            rows.push_back(r); cols.push_back(cc); rhs.push_back(rhs_idx[(size_t)g]);
+            off.push_back(off.back() + (long long)r * cc);
+            if (r > most) most = r;
+            if (elims) {
+                const std::vector<int32_t> & e = (*elims)[(size_t)g][i];
+                elim.insert(elim.end(), e.begin(), e.end());
+                eoff.push_back((int32_t)elim.size());
+            }
+        }
+        goff[(size_t)g + 1] = goff[(size_t)g] + (int32_t)grp.size();
+    }
+    const int nb = goff[(size_t)ng];
+    std::vector<xpg_rat32> flat((size_t)off.back() + 1);
+    for (int g = 0, b = 0; g < ng; g++)
+        for (size_t i = 0; i < groups[(size_t)g].size(); i++, b++)
+            std::memcpy((void *)(flat.data() + off[(size_t)b]), (const void *)groups[(size_t)g][i]->get_matrix(),
+                        sizeof(xpg_rat32) * (size_t)rows[(size_t)b] * cols[(size_t)b]);
+    if (elim.empty()) elim.push_back(0);
+    int cap = elims ? most * most / 4 + most + 1 : 4 * most + 16, cap_out = cap, cap_hull = 0;   // the library's defaults, spelled out
+    for (int attempt = 0; attempt < 3; attempt++) {
+        std::vector<long long> ooff((size_t)ng + 1, 0);
+        std::vector<int32_t> orows((size_t)ng, 0), kok((size_t)ng, 0), kmem((size_t)ng, 0), kchain((size_t)ng, 0), ksteps((size_t)ng, 0);
+        const xpg_rat32 * view = 0;
+        const int rc = elims
+            ? xpg_lineq_project_union_batch_ragged_rat32(h, ng, goff.data(), nb, flat.data(), rows.data(), cols.data(), off.data(), rhs.data(),
+                                                         elim.data(), eoff.data(), darkshadow ? 1 : 0, is_intersect ? 1 : 0, cap, cap_out, cap_hull,
+                                                         (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), kmem.data(), kchain.data(),
+                                                         ksteps.data())
+            : xpg_lineq_hull_batch_ragged_rat32(h, ng, goff.data(), nb, flat.data(), rows.data(), cols.data(), off.data(), rhs.data(),
+                                                is_intersect ? 1 : 0, cap, cap_out, cap_hull, (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(),
+                                                kok.data(), kmem.data(), kchain.data(), ksteps.data());
+        if (rc != 0) return rc;
+        int need_cap = 0, need_out = 0, need_hull = 0;
+        for (int g = 0; g < ng; g++) {
+            const int need = -kok[(size_t)g];
+            if (need <= 0) continue;                                // the group was answered
+            if (kmem[(size_t)g] < 0) { if (need > need_hull) need_hull = need; }
+            else if (need > cap) { if (need > need_cap) need_cap = need; }
+            else if (need > need_out) need_out = need;
+        }
+        if (need_cap) { cap = need_cap; cap_out = cap; }
+        else if (need_out) cap_out = need_out;
+        if (need_hull) cap_hull = need_hull;
+        if (need_cap || need_out || need_hull) continue;
+        for (int g = 0; g < ng; g++) {
+            ok[(size_t)g] = kok[(size_t)g];
+            if (member) (*member)[(size_t)g] = kmem[(size_t)g];
+            if (orows[(size_t)g] > 0) put_cells(results[(size_t)g], view + ooff[(size_t)g], (int)orows[(size_t)g], (int)cols[(size_t)goff[(size_t)g]]);
+            else results[(size_t)g].clean();
+        }
+        return 0;
+    }
+    return XPG_ERR_UNSUPPORTED;
+}
+} // namespace detail
+
+// Lineq::ConvexHullUnionAndIntersect (linsys.cpp:283-336) for MANY lists of polyhedra in ONE call -- the hull of the statements
+// that share a loop, of the access regions per array: groups[g] is a list of polyhedra that share their columns, rhs_idx[g] its
+// constant column. calcBound on every member of every group in one launch, ONE reduce per group in a second, one upload and one
+// synchronisation (xpg_lineq_hull_batch_ragged_rat32). results[g] receives the hull (cleaned where it has no rows), ok[g] 1; 0
+// where reduce found the group inconsistent (is_intersect: results[g] cleaned) or calcBound found a member inconsistent -- then
+// (*member)[g] (may be NULL) is that member's index, else -1, and results[g] is cleaned: the stated deviation from the reference,
+// which goes on with stale bounds. A call found short of rows is made again with the largest need reported, at most three
+// times; still short: XPG_ERR_UNSUPPORTED. Returns 0 or XPG_ERR_*.
+template <class RMatT>
+inline int hull_all(const std::vector<std::vector<RMatT *> > & groups, const std::vector<int32_t> & rhs_idx, bool is_intersect,
+                    std::vector<RMatT> & results, std::vector<int32_t> & ok, xpg_ctx * c = 0, std::vector<int32_t> * member = 0)
+{
+    return detail::hull_groups(groups, rhs_idx, (const std::vector<std::vector<std::vector<int32_t> > > *)0, false, is_intersect, results, ok, member, c);
+}
+
+// The projected union of PolyTran::step_4 (src/eng/poly.cpp:4802-4823) for many groups in ONE call: member i of group g is
+// projected by its own list elims[g][i] (one launch of the ragged chain kernel), the results of a group are concatenated in list
+// order and ONE reduce(ub, rhs_idx[g], is_intersect) runs per group (step_4 passes false). Arguments, verdicts and retries as
+// hull_all (xpg_lineq_project_union_batch_ragged_rat32).
+template <class RMatT>
+inline int project_union_each(const std::vector<std::vector<RMatT *> > & groups, const std::vector<std::vector<std::vector<int32_t> > > & elims,
+                              const std::vector<int32_t> & rhs_idx, bool is_intersect, std::vector<RMatT> & results, std::vector<int32_t> & ok,
+                              xpg_ctx * c = 0, bool darkshadow = false, std::vector<int32_t> * member = 0)
+{
+    return detail::hull_groups(groups, rhs_idx, &elims, darkshadow, is_intersect, results, ok, member, c);
 }
 
 } // namespace xpoly_amd

@@ -52,6 +52,8 @@ SYMBOLS = [
     "xpg_lineq_project_batch_ragged_rat32", "xpg_lineq_levels_batch_ragged_rat32", "xpg_lineq_ragged_last_route",
     "xpg_test_lineq_ragged_plan",
     "xpg_lineq_bounds_batch_ragged_rat32", "xpg_lineq_bounds_ragged_last_route", "xpg_test_lineq_bounds_ragged_plan",
+    "xpg_lineq_hull_batch_ragged_rat32", "xpg_lineq_project_union_batch_ragged_rat32", "xpg_lineq_hull_last_route",
+    "xpg_lineq_project_union_last_route", "xpg_test_lineq_hull_plan",
 ]
 
 _lib = None

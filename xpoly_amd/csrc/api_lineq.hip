@@ -4,6 +4,7 @@
 #include "ctx.hip.h"
 #include "lineq_host.hip.h"
 #include "ragged_host.hip.h"
+#include "lineq_hull_host.hip.h"
 
 using namespace xpg;
 
@@ -345,6 +346,58 @@ int xpg_test_lineq_bounds_ragged_plan(int nb, const int32_t * rows, const int32_
     if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
     const long long f[12] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps, p.cap,
                               p.cap_out, p.cols, p.rows };
+    return copy_fields(out, n, f);
+}
+// ---- hulls of lists of polyhedra: a producer launch, then ONE reduce per group (lineq_hull_host.hip.h) --------------------------
+int xpg_lineq_hull_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, const int32_t * group_offsets, int n_members, const xpg_rat32 * mats,
+                                      const int32_t * rows, const int32_t * cols, const long long * offsets, const int32_t * rhs_idx,
+                                      int is_intersect, int cap_rows, int cap_out_rows, int cap_hull_rows, xpg_rat32 * outs,
+                                      long long outs_cap_cells, const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows,
+                                      int32_t * out_ok, int32_t * out_member, int32_t * out_chain, int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    return lineq_hull_ragged_packed(ctx, n_groups, group_offsets, n_members, (const R32 *)mats, rows, cols, offsets, rhs_idx, (const int32_t *)0,
+                                    (const int32_t *)0, 0, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, (R32 *)outs, outs_cap_cells,
+                                    (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_member, out_chain, out_steps);
+}
+int xpg_lineq_project_union_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, const int32_t * group_offsets, int n_members, const xpg_rat32 * mats,
+                                               const int32_t * rows, const int32_t * cols, const long long * offsets, const int32_t * rhs_idx,
+                                               const int32_t * elim, const int32_t * elim_offsets, int darkshadow, int is_intersect,
+                                               int cap_rows, int cap_out_rows, int cap_hull_rows, xpg_rat32 * outs, long long outs_cap_cells,
+                                               const xpg_rat32 ** out_view, long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok,
+                                               int32_t * out_member, int32_t * out_chain, int32_t * out_steps)
+{
+    XPG_BIND(ctx);
+    if (out_view) *out_view = 0;
+    if (!elim_offsets && (n_groups != 0 || n_members != 0)) { hull_route() = HullRoute{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; return XPG_ERR_SHAPE; }
+    return lineq_hull_ragged_packed(ctx, n_groups, group_offsets, n_members, (const R32 *)mats, rows, cols, offsets, rhs_idx, elim, elim_offsets,
+                                    darkshadow, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, (R32 *)outs, outs_cap_cells,
+                                    (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_member, out_chain, out_steps);
+}
+// what the calling thread's last hull / projected-union call did (lineq_hull_host.hip.h HullRoute); one record serves both
+static int hull_last_route(long long * out, int n)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    const HullRoute & r = hull_route();
+    const long long f[10] = { r.prod_launches, r.launches, r.grid, r.lds, r.n_lds, r.n_dev, r.seat_bytes, r.slot_bytes, r.out_bytes, r.gathered };
+    return copy_fields(out, n, f);
+}
+int xpg_lineq_hull_last_route(long long * out, int n) { return hull_last_route(out, n); }
+int xpg_lineq_project_union_last_route(long long * out, int n) { return hull_last_route(out, n); }
+// host-only test view: the plan of a hull call (elim_offsets NULL) or of a projected union from the shapes alone
+// (lineq_hull_host.hip.h hull_plan, the function the launch asks -- the error codes are its own): the route's first nine
+// figures, then the capacities, the rows of the LDS matrix area and the envelope's columns; homes / gcaps [n_groups] (may be NULL)
+int xpg_test_lineq_hull_plan(int n_groups, const int32_t * group_offsets, int n_members, const int32_t * rows, const int32_t * cols,
+                             const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets, int cap_rows, int cap_out_rows,
+                             int cap_hull_rows, long long * out, int n, int32_t * homes, int32_t * gcaps)
+{
+    if (!out || n < 0) return XPG_ERR_SHAPE;
+    HullPlan p;
+    if (const int rc = hull_plan(n_groups, group_offsets, n_members, rows, cols, rhs_idx, elim, elim_offsets, cap_rows, cap_out_rows, cap_hull_rows, p,
+                                 homes, gcaps)) return rc;
+    const long long on = n_members > 0 ? 1 : 0;
+    const long long f[14] = { on, on, p.grid, (long long)p.lds, p.n_lds, p.n_dev, (long long)p.seat_bytes, (long long)p.slot_bytes,
+                              (long long)p.out_bytes, p.cap, p.cap_out, p.cap_hull, p.lds_rows, p.ecols };
     return copy_fields(out, n, f);
 }
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank)

@@ -847,6 +847,109 @@ __global__ __launch_bounds__(64) void k_calc_bound_ragged(int nb, const RaggedSy
     }
 }
 
+// ---- hulls: ONE reduce over the concatenated results of a GROUP of systems ---------------------------------------------------------
+// Lineq::ConvexHullUnionAndIntersect (linsys.cpp:283-336: calcBound on every member of a list, every variable's bounds appended
+// to a matrix that begins with one zero row, reduce over the lot) and the projected union of PolyTran::step_4 (eng/poly.cpp:
+// 4802-4823: an fme chain per statement, the results concatenated, one reduce). The per-member half is a PRODUCER launch
+// (k_calc_bound_ragged, k_fme_chain_ragged<false>); this kernel is the second launch on the same stream behind it -- no host
+// synchronisation between them -- and gives one wavefront (one workgroup) per GROUP.
+//   A group's descriptor is a RaggedSys read as: in_off the group's first member, rows its members, cols / rhs what they share,
+//   list_n the producer slots per member (calcBound: rhs, the variables 0 .. rhs-1; the chain: 1), list_at the first of its
+//   slots' counts in prod_rows, pad 1 where a zero row goes in front, out_off the cell where its members' slots begin in `outs`.
+//   Members of a group follow each other in the batch and share cols, so the group's slots are list_n x rows slots of cap_out x
+//   cols cells back to back from out_off: slot k holds prod_rows[list_at + k] live rows. Behind them the host keeps one more
+//   slot where pad is set, so that lead + the live rows -- the most a result can have -- fit the group's own region.
+// The wave gathers the live rows in slot order (members in list order, inside a member the variables 0 .. rhs-1; an empty result
+// contributes nothing) behind the lead row into ONE matrix with the group's own cols as row stride: in LDS where the group's
+// gathered CAPACITY gcap = min(cap_hull, lead + slots x cap_out) has gcap x cols <= lds_cells (a rule of the shapes alone: the
+// host's plan states every group's home), else in the workgroup's device slot (cap_hull x ecols cells; WScratch stays in LDS,
+// as w_fme_step does for a result past cap_lds). Then w_reduce, unchanged, and the surviving rows go to the FRONT of the group's
+// region in `outs` -- every live row has been read by then -- with their count in g_rows.
+//   g_ok 1, g_member -1:      every member's job succeeded and reduce returned true; the rows are reduce's
+//   g_ok 0, g_member -1:      reduce returned false: is_intersect: 0 rows (res.clean()); else the rows as reduce leaves them,
+//                             after removeIdenRow, uncompacted (what k_reduce_batch stores for an inconsistent system)
+//   g_member m >= 0:          member m of the group is the LOWEST whose own verdict is <= 0; g_ok / g_chain / g_steps are that
+//                             member's, the group has 0 rows, nothing is gathered or reduced
+//   g_ok -need, g_member -1:  the group gathers need > cap_hull rows; 0 rows
+//   no members:               0 rows, g_ok 1
+// g_gath: the rows gathered (lead included; 0 where nothing was). Nothing of an earlier group of the seat is read: the row map is
+// written for [lead, need) before it is read, the matrix for [0, need x cols), and w_reduce writes what it reads (see the walks).
+__global__ __launch_bounds__(64) void k_group_reduce(int ng, const RaggedSys * __restrict__ grp, R32 * outs, int cap_out,
+                                                     const int * __restrict__ prod_rows, const int * __restrict__ mem_ok,
+                                                     const int * __restrict__ mem_chain, const int * __restrict__ mem_steps, int is_intersect,
+                                                     int cap_hull, int ecols, int lds_cells, R32 * slots, int * g_rows, int * g_ok,
+                                                     int * g_member, int * g_chain, int * g_steps, int * g_gath)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    R32 * const mat_lds = (R32 *)lds_all;
+    WScratch s = carve_scratch((unsigned char *)(mat_lds + lds_cells), cap_hull);
+    R32 * const slot = slots + (size_t)blockIdx.x * cap_hull * ecols;
+    const int lane = lane_id();
+    for (int g = (int)blockIdx.x; g < ng; g += (int)gridDim.x) {
+        const RaggedSys d = grp[g];
+        const int members = d.rows, cols = d.cols, m0 = (int)d.in_off, lead = d.pad, n_slots = members * d.list_n;
+        // the lowest member whose job did not succeed (a lane meets its members in ascending order)
+        int badm = INT_MAX;
+        for (int k = lane; k < members && badm == INT_MAX; k += 64) if (mem_ok[m0 + k] <= 0) badm = k;
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_xor(badm, o); badm = y < badm ? y : badm; }
+        int need = 0;
+        if (badm == INT_MAX && members > 0) {
+            for (int k = lane; k < n_slots; k += 64) need += prod_rows[d.list_at + k];
+            for (int o = 1; o < 64; o <<= 1) need += __shfl_xor(need, o);
+            need += lead;
+        }
+        if (badm != INT_MAX || members == 0 || need > cap_hull) {
+            if (lane == 0) {
+                const bool failed = badm != INT_MAX;
+                g_rows[g] = 0;
+                g_ok[g] = failed ? mem_ok[m0 + badm] : (members == 0 ? 1 : -need);
+                g_member[g] = failed ? badm : -1;
+                g_chain[g] = failed && mem_chain ? mem_chain[m0 + badm] : -1;
+                g_steps[g] = failed ? mem_steps[m0 + badm] : 0;
+                g_gath[g] = 0;
+            }
+            continue;
+        }
+        const long long room = (long long)lead + (long long)n_slots * cap_out;
+        const long long gcap = room < cap_hull ? room : cap_hull;
+        WMat m; m.a = gcap * cols <= lds_cells ? mat_lds : slot; m.ld = cols; m.c = cols; m.r = need;
+        // row i of the matrix is row map[i] of the group's region (slot k, row r: k x cap_out + r)
+        int * const map = s.map;
+        int at = lead;
+        for (int base = 0; base < n_slots; base += 64) {
+            const int k = base + lane;
+            const int c = k < n_slots ? prod_rows[d.list_at + k] : 0;
+            int incl = c;
+            for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o); if (lane >= o) incl += y; }
+            const int start = at + incl - c;
+            for (int r = 0; r < c; r++) map[start + r] = k * cap_out + r;
+            at += __shfl(incl, 63);
+        }
+        if (lead) for (int j = lane; j < cols; j += 64) m.a[j] = R32(0, 1);
+        wave_sync();
+        R32 * const region = outs + d.out_off;
+        const int total = need * cols;
+        bool bad = false;
+        {
+            const FastDiv by_cols(cols, total + 64);
+            for (int t = lead * cols + lane; t < total; t += 64) {
+                const int i = by_cols.quot(t), j = t - i * cols;
+                const R32 v = region[(size_t)map[i] * cols + j];
+                bad |= !canonical(v);
+                m.a[t] = v;
+            }
+        }
+        m.cn = grp_ballot(bad) == 0;
+        wave_sync();
+        const bool ok = w_reduce(m, d.rhs, is_intersect != 0, s);
+        wave_sync();
+        if (!ok && is_intersect) m.r = 0;
+        w_store(m, region);
+        if (lane == 0) { g_rows[g] = m.r; g_ok[g] = ok ? 1 : 0; g_member[g] = -1; g_chain[g] = -1; g_steps[g] = 0; g_gath[g] = need; }
+        wave_sync();
+    }
+}
+
 // ---- Gauss-Jordan family: rank / det / inv, one wave per matrix -----------------------------------
 __device__ inline R32 abs_r(R32 v) { return lt(v, R32(0, 1)) ? neg(v) : v; }          // matt.h:206-212
 

@@ -431,6 +431,91 @@ class Lineq:
             raise ValueError("xpg_lineq_bounds_ragged_last_route: %d" % rc)
         return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "out_bytes", "steps"), (int(x) for x in out)))
 
+    def _hull_ragged(self, groups, rhs_idx, elims, darkshadow, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, copy):
+        """xpg_lineq_{hull,project_union}_batch_ragged_rat32 (elims None: the hull). groups: a list of lists of systems."""
+        from .six import _ragged_pack
+        ng = len(groups)
+        goff = np.zeros(ng + 1, dtype=np.int32)
+        goff[1:] = np.cumsum([len(g) for g in groups])
+        members = [m for g in groups for m in g]
+        nb = len(members)
+        ok = np.zeros(ng, dtype=np.int32); member = np.zeros(ng, dtype=np.int32); chain = np.zeros(ng, dtype=np.int32)
+        steps = np.zeros(ng, dtype=np.int32)
+        if ng == 0:
+            return ok, member, chain, steps, []
+        if nb:
+            flat, off, parts = _ragged_pack(members, RAT, 2)
+            rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
+        else:
+            flat, off, rows, cols = None, None, None, None
+        rhs = None
+        if rhs_idx is not None:                             # one per group, or one per member
+            rhs = np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+            if rhs.size == ng and rhs.size != nb:
+                rhs = np.ascontiguousarray(np.repeat(rhs, np.diff(goff)))
+            if rhs.size != nb:
+                raise ValueError("one rhs_idx per group or per member: %d groups, %d members, %d rhs_idx" % (ng, nb, rhs.size))
+        ooff = np.zeros(ng + 1, dtype=np.int64); orows = np.zeros(ng, dtype=np.int32)
+        view = C.c_void_p()
+        caps = (C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), C.c_int(cap_hull_rows or 0))
+        tail = (None, C.c_longlong(0), C.byref(view), vp(ooff), vp(orows), vp(ok), vp(member), vp(chain), vp(steps))
+        if elims is None:
+            name = "xpg_lineq_hull_batch_ragged_rat32"
+            code = getattr(lib(), name)(self.ctx._h, C.c_int(ng), vp(goff), C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs),
+                                        C.c_int(int(is_intersect)), *caps, *tail)
+        else:
+            name = "xpg_lineq_project_union_batch_ragged_rat32"
+            lists = [np.asarray(e, dtype=np.int32).reshape(-1) for g in elims for e in g]
+            if len(lists) != nb:
+                raise ValueError("one list per member: %d members, %d lists" % (nb, len(lists)))
+            eoff = np.zeros(nb + 1, dtype=np.int32)
+            eoff[1:] = np.cumsum([e.size for e in lists])
+            el = np.ascontiguousarray(np.concatenate(lists)) if nb and int(eoff[nb]) else np.zeros(1, dtype=np.int32)
+            code = getattr(lib(), name)(self.ctx._h, C.c_int(ng), vp(goff), C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs),
+                                        vp(el), vp(eoff), C.c_int(int(darkshadow)), C.c_int(int(is_intersect)), *caps, *tail)
+        self.ctx.check(code, name)
+        total = int(ooff[ng])
+        if not copy and total:
+            buf = (C.c_int32 * (total * 2)).from_address(view.value)
+            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
+        else:
+            packed = np.empty((total, 2), dtype=np.int32)
+            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
+                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
+        o = ooff.tolist(); g0 = goff.tolist()
+        width = [int(cols[g0[g]]) if g0[g + 1] > g0[g] else 0 for g in range(ng)]
+        return ok, member, chain, steps, [packed[o[g]: o[g + 1]].reshape(-1, width[g], 2) if width[g] else np.zeros((0, 0, 2), dtype=np.int32)
+                                          for g in range(ng)]
+
+    def hull_ragged(self, groups, rhs_idx=None, is_intersect=False, cap_rows=None, cap_out_rows=None, cap_hull_rows=None, copy=True):
+        """xpg_lineq_hull_batch_ragged_rat32: Lineq::ConvexHullUnionAndIntersect (linsys.cpp:283-336) for MANY lists of polyhedra
+        in one call -- groups[g] is a list of systems that share cols and rhs_idx (one rhs_idx per group or per member; None:
+        the last column). calcBound on every member in one launch, then ONE reduce per group over the members' bounds behind a
+        zero row, in a second launch. Returns (ok[ng], member[ng], chain[ng], steps[ng], [rows of group g]): ok 1; 0 with member
+        -1 where reduce found the group inconsistent (is_intersect: no rows); member m >= 0 with that member's calcBound verdict
+        where a member failed (no rows: a stated deviation from the reference, which goes on with stale bounds); -need with
+        member -1 where the group gathers need > cap_hull_rows rows. copy=False: views of the handle's pinned buffer."""
+        return self._hull_ragged(groups, rhs_idx, None, False, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, copy)
+
+    def project_union_ragged(self, groups, rhs_idx, elims, is_intersect=False, darkshadow=False, cap_rows=None, cap_out_rows=None,
+                             cap_hull_rows=None, copy=True):
+        """xpg_lineq_project_union_batch_ragged_rat32: PolyTran::step_4's shape -- every member of groups[g] projected by its own
+        list elims[g][i] in one launch, the results of a group concatenated in list order and ONE reduce per group. Returns what
+        hull_ragged returns; a member's verdict is the chain's (chain is -1)."""
+        return self._hull_ragged(groups, rhs_idx, elims, darkshadow, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, copy)
+
+    HULL_ROUTE_KEYS = ("producer_launches", "launches", "grid", "lds", "groups_lds", "groups_device", "seat_bytes", "slot_bytes",
+                       "out_bytes", "gathered_rows")
+
+    @staticmethod
+    def hull_ragged_last_route():
+        """xpg_lineq_hull_last_route of the calling thread's last hull_ragged / project_union_ragged call, as a dict."""
+        out = np.zeros(10, dtype=np.int64)
+        rc = lib().xpg_lineq_hull_last_route(vp(out), C.c_int(10))
+        if rc != 0:
+            raise ValueError("xpg_lineq_hull_last_route: %d" % rc)
+        return dict(zip(Lineq.HULL_ROUTE_KEYS, (int(x) for x in out)))
+
     def rank(self, mats):
         a = _stack(mats)
         nb, rows, cols = a.shape[:3]
