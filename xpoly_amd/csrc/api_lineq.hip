@@ -173,7 +173,7 @@ int xpg_lineq_project_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 
                                          long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
 {
     XPG_BIND(ctx);
-    return lineq_project_batch_packed(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+    return lineq_chain_batch_packed(ctx, false, nb, (const R32 *)mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
                                       (R32 *)outs, outs_cap_rows, (const R32 **)out_view, row_offsets, out_ok, out_steps);
 }
 int xpg_lineq_project_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
@@ -181,26 +181,17 @@ int xpg_lineq_project_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d
                                       xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps)
 {
     XPG_BIND(ctx);
-    return lineq_project_batch_dev(ctx, nb, (const R32 *)d_mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+    return lineq_chain_batch_dev(ctx, false, nb, (const R32 *)d_mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
                                    (R32 *)d_outs, d_out_rows, d_out_ok, d_out_steps);
 }
-// what the calling thread's last xpg_lineq_project_batch_* call did (lineq_host.hip.h ProjectRoute)
-int xpg_lineq_project_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const ProjectRoute & r = project_route();
-    const long long f[6] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes };
-    return copy_fields(out, n, f);
-}
+// what the calling thread's last xpg_lineq_project_batch_* call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_project_last_route(long long * out, int n) { return route_out(ROUTE_PROJECT, out, n); }
 // host-only test view: the plan of a projection call from its shape alone (lineq_host.hip.h project_plan), with the
 // capacities it settles on behind the route's six figures
 int xpg_test_lineq_project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_rows, long long * out, int n)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    ProjectPlan p;
-    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, p)) return rc;
-    const long long f[8] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, p.cap, p.cap_out };
-    return copy_fields(out, n, f);
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_PROJECT, project_plan(nb, rows, cols, cap_rows, cap_out_rows, p), p, out, n);
 }
 // host-only test view: what the projection entry points answer to an elimination list before they look at anything else
 // (lineq_host.hip.h project_check, the function they ask): 0, XPG_ERR_SHAPE or XPG_ERR_UNSUPPORTED
@@ -212,7 +203,7 @@ int xpg_lineq_levels_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
                                         long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
 {
     XPG_BIND(ctx);
-    return lineq_levels_batch_packed(ctx, nb, (const R32 *)mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+    return lineq_chain_batch_packed(ctx, true, nb, (const R32 *)mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
                                      (R32 *)outs, outs_cap_rows, (const R32 **)out_view, row_offsets, out_ok, out_steps);
 }
 int xpg_lineq_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int rhs_idx,
@@ -220,27 +211,17 @@ int xpg_lineq_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_
                                      xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps)
 {
     XPG_BIND(ctx);
-    return lineq_levels_batch_dev(ctx, nb, (const R32 *)d_mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
+    return lineq_chain_batch_dev(ctx, true, nb, (const R32 *)d_mats, rows, cols, rhs_idx, elim, n_elim, darkshadow, cap_rows, cap_out_rows,
                                   (R32 *)d_outs, d_out_rows, d_out_ok, d_out_steps);
 }
-// what the calling thread's last xpg_lineq_levels_batch_* call did (lineq_host.hip.h LevelsRoute)
-int xpg_lineq_levels_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const LevelsRoute & r = levels_route();
-    const long long f[7] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.level_bytes };
-    return copy_fields(out, n, f);
-}
+// what the calling thread's last xpg_lineq_levels_batch_* call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_levels_last_route(long long * out, int n) { return route_out(ROUTE_LEVELS, out, n); }
 // host-only test view: the plan of a levels call from its shape alone (lineq_host.hip.h levels_plan), with the capacities it
 // settles on behind the route's seven figures
 int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, long long * out, int n)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    LevelsPlan l;
-    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
-    const long long f[9] = { 1, l.p.q.grid, l.p.q.G, l.p.q.sys_lds, l.p.cap_lds, (long long)l.p.seat_bytes, (long long)l.level_bytes, l.p.cap,
-                             l.p.cap_out };
-    return copy_fields(out, n, f);
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_LEVELS, levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, p), p, out, n);
 }
 // ---- projection / levels of systems of mixed shapes and lists in one launch (lineq_host.hip.h) --------------------------------
 int xpg_lineq_project_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
@@ -263,25 +244,16 @@ int xpg_lineq_levels_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
     return lineq_chain_ragged_packed(ctx, nb, (const R32 *)mats, rows, cols, offsets, rhs_idx, elim, elim_offsets, true, darkshadow, cap_rows,
                                      cap_out_rows, (R32 *)outs, outs_cap_cells, (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_steps);
 }
-// what the calling thread's last ragged projection / levels call did (lineq_host.hip.h RaggedRoute)
-int xpg_lineq_ragged_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const RaggedRoute & r = ragged_route();
-    const long long f[7] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.out_bytes };
-    return copy_fields(out, n, f);
-}
+// what the calling thread's last ragged projection / levels call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_ragged_last_route(long long * out, int n) { return route_out(ROUTE_RAGGED, out, n); }
 // host-only test view: the plan of a ragged call from its shapes and lists alone (lineq_host.hip.h ragged_chain_plan, the
 // function the launch asks -- the error codes are its own), with the envelope it settles on behind the route's seven figures
 int xpg_test_lineq_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, const int32_t * elim,
                                const int32_t * elim_offsets, int levels, int cap_rows, int cap_out_rows, long long * out, int n)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    RaggedChainPlan p;
-    if (const int rc = ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, levels != 0, cap_rows, cap_out_rows, p)) return rc;
-    const long long f[11] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.cap, p.cap_out,
-                              p.cols, p.rows };
-    return copy_fields(out, n, f);
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE
+                         : plan_out(ROUTE_RAGGED, ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, levels != 0, cap_rows, cap_out_rows, p), p, out, n);
 }
 // ---- calcBound fused: the bounds of every variable of every system in one launch (lineq_host.hip.h) ---------------------------
 int xpg_lineq_bounds_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, int rows, int cols, int rhs_idx, int cap_rows,
@@ -300,23 +272,14 @@ int xpg_lineq_bounds_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_
     return lineq_bounds_batch_dev(ctx, nb, (const R32 *)d_mats, rows, cols, rhs_idx, cap_rows, cap_out_rows, (R32 *)d_outs, d_out_rows,
                                   d_out_ok, d_out_chain, d_out_steps);
 }
-// what the calling thread's last xpg_lineq_bounds_batch_* call did (lineq_host.hip.h BoundsRoute)
-int xpg_lineq_bounds_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const BoundsRoute & r = bounds_route();
-    const long long f[7] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.steps };
-    return copy_fields(out, n, f);
-}
+// what the calling thread's last xpg_lineq_bounds_batch_* call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_bounds_last_route(long long * out, int n) { return route_out(ROUTE_BOUNDS, out, n); }
 // host-only test view: the plan of a fused calcBound call from its shape alone (lineq_host.hip.h bounds_plan), with the
 // capacities it settles on behind the route's seven figures
 int xpg_test_lineq_bounds_plan(int nb, int rows, int cols, int rhs_idx, int cap_rows, int cap_out_rows, long long * out, int n)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    BoundsPlan p;
-    if (const int rc = bounds_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
-    const long long f[9] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, p.steps, p.cap, p.cap_out };
-    return copy_fields(out, n, f);
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_BOUNDS, bounds_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p), p, out, n);
 }
 // ---- calcBound fused for systems of mixed shapes in one launch (lineq_host.hip.h) ---------------------------------------------
 int xpg_lineq_bounds_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
@@ -328,25 +291,15 @@ int xpg_lineq_bounds_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 *
     return lineq_bounds_ragged_packed(ctx, nb, (const R32 *)mats, rows, cols, offsets, rhs_idx, cap_rows, cap_out_rows, (R32 *)outs, outs_cap_cells,
                                       (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_chain, out_steps);
 }
-// what the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did (lineq_host.hip.h BoundsRaggedRoute)
-int xpg_lineq_bounds_ragged_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const BoundsRaggedRoute & r = bounds_ragged_route();
-    const long long f[8] = { r.launches, r.grid, r.groups, r.sys_lds, r.cap_lds, r.seat_bytes, r.out_bytes, r.steps };
-    return copy_fields(out, n, f);
-}
+// what the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_bounds_ragged_last_route(long long * out, int n) { return route_out(ROUTE_BOUNDS_RAGGED, out, n); }
 // host-only test view: the plan of a ragged calcBound call from its shapes alone (lineq_host.hip.h bounds_ragged_plan, the
 // function the launch asks -- the error codes are its own), with the envelope it settles on behind the route's eight figures
 int xpg_test_lineq_bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows,
                                       int cap_out_rows, long long * out, int n)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    BoundsRaggedPlan p;
-    if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
-    const long long f[12] = { 1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps, p.cap,
-                              p.cap_out, p.cols, p.rows };
-    return copy_fields(out, n, f);
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_BOUNDS_RAGGED, bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p), p, out, n);
 }
 // ---- hulls of lists of polyhedra: a producer launch, then ONE reduce per group (lineq_hull_host.hip.h) --------------------------
 int xpg_lineq_hull_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, const int32_t * group_offsets, int n_members, const xpg_rat32 * mats,
@@ -369,21 +322,15 @@ int xpg_lineq_project_union_batch_ragged_rat32(xpg_ctx * ctx, int n_groups, cons
 {
     XPG_BIND(ctx);
     if (out_view) *out_view = 0;
-    if (!elim_offsets && (n_groups != 0 || n_members != 0)) { hull_route() = HullRoute{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; return XPG_ERR_SHAPE; }
+    if (!elim_offsets && (n_groups != 0 || n_members != 0)) { route_clear(ROUTE_HULL); return XPG_ERR_SHAPE; }
     return lineq_hull_ragged_packed(ctx, n_groups, group_offsets, n_members, (const R32 *)mats, rows, cols, offsets, rhs_idx, elim, elim_offsets,
                                     darkshadow, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, (R32 *)outs, outs_cap_cells,
                                     (const R32 **)out_view, out_cell_offsets, out_rows, out_ok, out_member, out_chain, out_steps);
 }
-// what the calling thread's last hull / projected-union call did (lineq_hull_host.hip.h HullRoute); one record serves both
-static int hull_last_route(long long * out, int n)
-{
-    if (!out || n < 0) return XPG_ERR_SHAPE;
-    const HullRoute & r = hull_route();
-    const long long f[10] = { r.prod_launches, r.launches, r.grid, r.lds, r.n_lds, r.n_dev, r.seat_bytes, r.slot_bytes, r.out_bytes, r.gathered };
-    return copy_fields(out, n, f);
-}
-int xpg_lineq_hull_last_route(long long * out, int n) { return hull_last_route(out, n); }
-int xpg_lineq_project_union_last_route(long long * out, int n) { return hull_last_route(out, n); }
+// what the calling thread's last hull / projected-union call did (lineq_host.hip.h: the table beside LineqRoute); one record
+// serves both
+int xpg_lineq_hull_last_route(long long * out, int n) { return route_out(ROUTE_HULL, out, n); }
+int xpg_lineq_project_union_last_route(long long * out, int n) { return route_out(ROUTE_HULL, out, n); }
 // host-only test view: the plan of a hull call (elim_offsets NULL) or of a projected union from the shapes alone
 // (lineq_hull_host.hip.h hull_plan, the function the launch asks -- the error codes are its own): the route's first nine
 // figures, then the capacities, the rows of the LDS matrix area and the envelope's columns; homes / gcaps [n_groups] (may be NULL)
@@ -391,14 +338,10 @@ int xpg_test_lineq_hull_plan(int n_groups, const int32_t * group_offsets, int n_
                              const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets, int cap_rows, int cap_out_rows,
                              int cap_hull_rows, long long * out, int n, int32_t * homes, int32_t * gcaps)
 {
-    if (!out || n < 0) return XPG_ERR_SHAPE;
     HullPlan p;
-    if (const int rc = hull_plan(n_groups, group_offsets, n_members, rows, cols, rhs_idx, elim, elim_offsets, cap_rows, cap_out_rows, cap_hull_rows, p,
-                                 homes, gcaps)) return rc;
-    const long long on = n_members > 0 ? 1 : 0;
-    const long long f[14] = { on, on, p.grid, (long long)p.lds, p.n_lds, p.n_dev, (long long)p.seat_bytes, (long long)p.slot_bytes,
-                              (long long)p.out_bytes, p.cap, p.cap_out, p.cap_hull, p.lds_rows, p.ecols };
-    return copy_fields(out, n, f);
+    return !out || n < 0 ? XPG_ERR_SHAPE
+                         : hull_plan_out(hull_plan(n_groups, group_offsets, n_members, rows, cols, rhs_idx, elim, elim_offsets, cap_rows, cap_out_rows,
+                                                   cap_hull_rows, p, homes, gcaps), p, out, n);
 }
 int xpg_rat_rank_batch_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_mats, int rows, int cols, int32_t * d_out_rank)
 {

@@ -47,14 +47,46 @@ inline int hpack_reserve(xpg_ctx * ctx, size_t bytes, bool internal = false)
 }
 inline char * hpack_buf(xpg_ctx * ctx, bool internal) { return (char *)(internal ? ctx->hred : ctx->hpack); }
 
+// THE way up of a packed call on nb systems of ONE shape (reduce, fme, projection, levels, fused calcBound), and the buffers of
+// its way down. The systems go up once: small batches (<= 4 MB) through the handle's pinned buffer -- one memcpy, then a true
+// asynchronous copy --, large ones straight from the caller's pages (the runtime's own staging is faster than a single-threaded
+// memcpy of tens of MB). The pinned buffer (hpack, or hred when `internal`: hpack_reserve) is laid out as [meta_al: row offsets
+// [nres + 1], then the ints as on the device][in_stage: the staged input][room: the result slots where they are small (<= 512 KB)
+// and come down whole; in_place: the input's size, k_pack_rows writes there]. dints: rows [nres], then nv verdict arrays [nb].
+// dout: the nres result slots, bo bytes (none in_place: the kernel works in di).
+struct PackedUp {
+    DevBuf di, dout, dints, doff;
+    int nb, nres, nv; size_t bo, meta_al, in_stage; bool small_out, internal;
+    int32_t * d_rows() const { return (int32_t *)dints.p; }
+    int32_t * d_verdict(int v) const { return (int32_t *)dints.p + nres + (size_t)v * nb; }
+    size_t ints_bytes() const { return ((size_t)nres + (size_t)nv * nb) * 4; }
+    char * h_room(xpg_ctx * ctx) const { return hpack_buf(ctx, internal) + meta_al + in_stage; }
+};
+inline int packed_up(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int nres, int nv, size_t bo, bool in_place, bool internal,
+                     PackedUp & u)
+{
+    const size_t bi = (size_t)nb * rows * cols * 8;
+    const bool small_in = bi <= ((size_t)4 << 20);
+    u.nb = nb; u.nres = nres; u.nv = nv; u.bo = bo; u.internal = internal;
+    u.meta_al = ((size_t)(nres + 1) * 8 + u.ints_bytes() + 255) & ~(size_t)255;
+    u.in_stage = small_in ? bi : 0;
+    u.small_out = !in_place && bo <= ((size_t)512 << 10);
+    XPG_TRY(u.di.alloc(ctx, bi)); XPG_TRY(u.dints.alloc(ctx, u.ints_bytes())); XPG_TRY(u.doff.alloc(ctx, (size_t)(nres + 1) * 8));
+    if (!in_place) XPG_TRY(u.dout.alloc(ctx, bo));
+    if (const int rc = hpack_reserve(ctx, u.meta_al + u.in_stage + (in_place ? bi : u.small_out ? bo : 0), internal)) return rc;
+    const void * src = mats;
+    if (small_in) { src = hpack_buf(ctx, internal) + u.meta_al; memcpy((void *)src, mats, bi); }
+    XPG_TRY(hipMemcpyAsync(u.di.p, src, bi, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
 // Lineq::reduce / removeIdenRow for nb host systems with a PACKED result (round 6): row_offsets[nb + 1] (in rows) and the
-// surviving rows of every system back to back. The systems go up once (small batches through the handle's pinned buffer,
-// large ones straight from the caller's pages), are reduced in place in HBM, and k_pack_rows_out writes the survivors
-// STRAIGHT INTO the handle's pinned host buffer (hipHostMalloc memory is mapped on the device: coalesced 16-byte stores
-// over the link), so the row counts, the verdicts, the offsets and the rows are all there after ONE synchronisation -- no
-// device slots come back, nothing is allocated per call beyond the handle's cached blocks. `out` (may be NULL) receives a
-// copy of the rows, *view (may be NULL) the pinned buffer itself (valid until the handle's next packed call), out_rows
-// (may be NULL) the per-system counts. `internal`: staged through hred instead (hpack_reserve), for the in-place form below.
+// surviving rows of every system back to back. The systems go up once (packed_up), are reduced in place in HBM, and k_pack_rows
+// writes the survivors STRAIGHT INTO the handle's pinned host buffer (hipHostMalloc memory is mapped on the device: coalesced
+// 16-byte stores over the link), so the row counts, the verdicts, the offsets and the rows are all there after ONE
+// synchronisation -- no device slots come back, nothing is allocated per call beyond the handle's cached blocks. `out` (may be
+// NULL) receives a copy of the rows, *view (may be NULL) the pinned buffer itself (valid until the handle's next packed call),
+// out_rows (may be NULL) the per-system counts. `internal`: staged through hred instead (hpack_reserve), for the in-place form below.
 inline int lineq_reduce_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, int mode, int is_intersect,
                                      R32 * out, long long out_cap_rows, const R32 ** view, long long * row_offsets,
                                      int32_t * out_rows, int32_t * out_ok, bool internal = false)
@@ -64,33 +96,17 @@ inline int lineq_reduce_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, in
         (out && out_cap_rows < 0))
         return XPG_ERR_SHAPE;
     if (nb == 0) { row_offsets[0] = 0; return 0; }
-    const size_t bi = (size_t)nb * rows * cols * 8;
-    const size_t meta = (size_t)(nb + 1) * 8 + (size_t)nb * 8;       // offsets, then ok and rows
-    const size_t meta_al = (meta + 255) & ~(size_t)255;
-    const bool small_in = bi <= ((size_t)4 << 20);
-    DevBuf di, dr, dk, doff;
-    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
-    XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + bi, internal);
-    if (rc) return rc;
-    char * hp = hpack_buf(ctx, internal);
-    char * hrows_out = hp + meta_al + (small_in ? bi : 0);           // where the survivors land
-    if (small_in) {
-        memcpy(hp + meta_al, mats, bi);
-        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = lineq_reduce_batch_dev(ctx, nb, (R32 *)di.p, rows, cols, rhs, mode, is_intersect, (int32_t *)dr.p, (int32_t *)dk.p);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nb, (const int *)dr.p, (long long *)doff.p);
-    hipLaunchKernelGGL(k_pack_rows, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, (const R32 *)di.p, rows, cols,
-                       (const int *)dr.p, (const long long *)doff.p, (R32 *)hrows_out);
+    PackedUp u;
+    if (const int rc = packed_up(ctx, nb, mats, rows, cols, nb, 1, 0, true, internal, u)) return rc;
+    char * hp = hpack_buf(ctx, internal), * hrows_out = u.h_room(ctx);   // where the survivors land
+    if (const int rc = lineq_reduce_batch_dev(ctx, nb, (R32 *)u.di.p, rows, cols, rhs, mode, is_intersect, u.d_rows(), u.d_verdict(0))) return rc;
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nb, (const int *)u.d_rows(), (long long *)u.doff.p);
+    hipLaunchKernelGGL(k_pack_rows, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, (const R32 *)u.di.p, rows, cols,
+                       (const int *)u.d_rows(), (const long long *)u.doff.p, (R32 *)hrows_out);
     XPG_TRY(hipGetLastError());
-    long long * h_off = (long long *)hp; int32_t * h_ok = (int32_t *)(hp + (size_t)(nb + 1) * 8); int32_t * h_rows = h_ok + nb;
-    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(h_rows, dr.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (mode == 1) XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    long long * h_off = (long long *)hp; int32_t * h_rows = (int32_t *)(hp + (size_t)(nb + 1) * 8), * h_ok = h_rows + nb;
+    XPG_TRY(hipMemcpyAsync(h_off, u.doff.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(h_rows, u.dints.p, u.ints_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     memcpy(row_offsets, h_off, (size_t)(nb + 1) * 8);
     if (out_rows) memcpy(out_rows, h_rows, (size_t)nb * 4);
@@ -181,42 +197,39 @@ inline int lineq_fme_batch(xpg_ctx * ctx, int nb, const R32 * mats, int rows, in
     return 0;
 }
 
-// The way down of a packed-result call (fme, projection), after its kernel is enqueued: dout [nb][cap][cols] holds each
-// system's live rows at the front of its slot, dr their counts, dk the verdicts, ds (may be NULL) the steps. The handle's
-// pinned buffer (hpack, or hred when `internal`) was reserved by the caller as [meta_al: offsets, ok, rows, steps][in_stage:
-// the staged input][the slots, when small_out]. small_out: the slots come down with the counts and are packed on the host --
-// one synchronisation, no scan / pack launches (a handful of systems: the drop-in adapter eliminates one per call). Else
-// k_rows_scan, one synchronisation for the offsets, k_pack_rows, and only live rows cross the link. short_msg != NULL: a
-// negative count (a result that needs -count rows) ends the call with XPG_ERR_UNSUPPORTED, the count in row_offsets[0].
-// out_ok == NULL: the results are not one per verdict (calcBound's nb * rhs results) -- dk is not read, the caller brings its
-// verdicts down itself, enqueued before this call so that its synchronisation covers them.
+// The way down of a uniform packed call (fme, projection, levels, fused calcBound), after its kernel is enqueued: u.dout
+// [nres][cap][cols] holds each result's live rows at the front of its slot, u.dints their counts and, behind them, the u.nv
+// verdict arrays [nb] that `verdicts` names in the same order -- ONE copy brings all the ints down. small_out: the slots come down
+// with them and are packed on the host -- one synchronisation, no scan / pack launches (a handful of systems: the drop-in adapter
+// eliminates one per call). Else k_rows_scan, one synchronisation for the offsets, k_pack_rows, and only live rows cross the link.
+// short_msg != NULL: a negative count (a result that needs -count rows) ends the call with XPG_ERR_UNSUPPORTED, the count in
+// row_offsets[0] and the verdicts not written. A buffer too small (XPG_ERR_SHAPE) still gets its offsets and verdicts.
+inline void no_lap(const char *) {}
 template <class Lap>
-inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & dout, DevBuf & dr, DevBuf & dk, DevBuf * ds, DevBuf & doff,
-                            size_t meta_al, size_t in_stage, bool small_out, bool internal, const char * short_msg, R32 * out,
-                            long long out_cap_rows, const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps, Lap lap)
+inline int packed_rows_down(xpg_ctx * ctx, PackedUp & u, int cols, int cap, const char * short_msg, R32 * out, long long out_cap_rows,
+                            const R32 ** view, long long * row_offsets, int32_t * const * verdicts, Lap lap)
 {
-    char * hp = hpack_buf(ctx, internal);
-    const size_t bo = (size_t)nb * cap * cols * 8;
-    long long * h_off = (long long *)hp; int32_t * h_ok = (int32_t *)(hp + (size_t)(nb + 1) * 8); int32_t * h_rows = h_ok + nb;
-    int32_t * h_steps = h_rows + nb;
-    if (out_ok) XPG_TRY(hipMemcpyAsync(h_ok, dk.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XPG_TRY(hipMemcpyAsync(h_rows, dr.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ds) XPG_TRY(hipMemcpyAsync(h_steps, ds->p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (small_out) {
-        char * hs = hp + meta_al + in_stage;
-        XPG_TRY(hipMemcpyAsync(hs, dout.p, bo, hipMemcpyDeviceToHost, ctx->stream));
+    const int nres = u.nres;
+    long long * h_off = (long long *)hpack_buf(ctx, u.internal);
+    int32_t * h_rows = (int32_t *)(h_off + nres + 1);
+    XPG_TRY(hipMemcpyAsync(h_rows, u.dints.p, u.ints_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    const auto verdicts_out = [&]() {
+        for (int v = 0; v < u.nv; v++) memcpy(verdicts[v], h_rows + nres + (size_t)v * u.nb, (size_t)u.nb * 4);
+    };
+    if (u.small_out) {
+        char * hs = u.h_room(ctx);
+        XPG_TRY(hipMemcpyAsync(hs, u.dout.p, u.bo, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
         long long tot = 0;
-        for (int b = 0; b < nb; b++) {
+        for (int b = 0; b < nres; b++) {
             if (short_msg && h_rows[b] < 0) { ctx->err = short_msg; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
             row_offsets[b] = tot; tot += h_rows[b];
         }
-        row_offsets[nb] = tot;
-        if (out_ok) memcpy(out_ok, h_ok, (size_t)nb * 4);
-        if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
+        row_offsets[nres] = tot;
+        verdicts_out();
         if (out && out_cap_rows < tot) return XPG_ERR_SHAPE;
         const size_t rowb = (size_t)cols * 8;
-        for (int b = 0; b < nb; b++) {                             // forward moves: a destination never lies above its source
+        for (int b = 0; b < nres; b++) {                           // forward moves: a destination never lies above its source
             const size_t nbytes = (size_t)(row_offsets[b + 1] - row_offsets[b]) * rowb;
             if (out) memcpy((char *)out + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
             if (view) memmove(hs + (size_t)row_offsets[b] * rowb, hs + (size_t)b * cap * rowb, nbytes);
@@ -224,30 +237,29 @@ inline int packed_rows_down(xpg_ctx * ctx, int nb, int cols, int cap, DevBuf & d
         if (view) *view = (const R32 *)hs;
         return 0;
     }
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nb, (const int *)dr.p, (long long *)doff.p);
-    XPG_TRY(hipMemcpyAsync(h_off, doff.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)u.d_rows(), (long long *)u.doff.p);
+    XPG_TRY(hipMemcpyAsync(h_off, u.doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     if (short_msg)
-        for (int b = 0; b < nb; b++)
+        for (int b = 0; b < nres; b++)
             if (h_rows[b] < 0) { ctx->err = short_msg; row_offsets[0] = h_rows[b]; return XPG_ERR_UNSUPPORTED; }
-    memcpy(row_offsets, h_off, (size_t)(nb + 1) * 8);
-    if (out_ok) memcpy(out_ok, h_ok, (size_t)nb * 4);
-    if (ds) memcpy(out_steps, h_steps, (size_t)nb * 4);
-    const long long total = row_offsets[nb];
+    memcpy(row_offsets, h_off, (size_t)(nres + 1) * 8);
+    verdicts_out();
+    const long long total = row_offsets[nres];
     if (out && out_cap_rows < total) return XPG_ERR_SHAPE;
     if (total == 0 || (!out && !view)) return 0;                   // (neither: a sizing call)
     const size_t bp = (size_t)total * cols * 8;
     lap("scan+meta");
     DevBuf dpk;
     XPG_TRY(dpk.alloc(ctx, bp));
-    hipLaunchKernelGGL(k_pack_rows, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, (const R32 *)dout.p, cap, cols,
-                       (const int *)dr.p, (const long long *)doff.p, (R32 *)dpk.p);
+    hipLaunchKernelGGL(k_pack_rows, dim3(nres < 4096 ? nres : 4096), dim3(256), 0, ctx->stream, nres, (const R32 *)u.dout.p, cap, cols,
+                       (const int *)u.d_rows(), (const long long *)u.doff.p, (R32 *)dpk.p);
     XPG_TRY(hipGetLastError());
     lap("pack");
     if (view) {                                                    // into pinned memory; the caller's copy, if any, from there
-        const int rc = hpack_reserve(ctx, bp, internal);
+        const int rc = hpack_reserve(ctx, bp, u.internal);
         if (rc) return rc;
-        char * hv = hpack_buf(ctx, internal);
+        char * hv = hpack_buf(ctx, u.internal);
         XPG_TRY(hipMemcpyAsync(hv, dpk.p, bp, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
         if (out) memcpy(out, hv, bp);
@@ -276,327 +288,285 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
     if (nb == 0) { row_offsets[0] = 0; return 0; }
     if (cap <= 0) cap = rows * rows / 4 + rows + 1;                  // every (positive, negative) pair + the rows without u
     if (cap < rows) cap = rows;
-    const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nb * cap * cols * 8;
-    const size_t meta = (size_t)(nb + 1) * 8 + (size_t)nb * 8;       // offsets, then ok and rows
-    DevBuf di, dout, dr, dk, doff;
-    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
-    XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
     static const bool dbg = xpg_hook("XPG_LINEQ_DEBUG") != 0;
     const auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char * what) { if (dbg) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "  fme_packed %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count()); } };
-    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
-    const size_t meta_al = (meta + 255) & ~(size_t)255;
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0), internal);
-    if (rc) return rc;
-    char * hp = hpack_buf(ctx, internal);
-    // small inputs through the pinned buffer (one memcpy, then a true asynchronous copy); large ones straight from
-    // the caller's pages (the runtime's own staging is faster than a single-threaded memcpy of tens of MB)
-    if (small_in) {
-        memcpy(hp + meta_al, mats, bi);
-        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
-    }
+    PackedUp up;
+    if (const int rc = packed_up(ctx, nb, mats, rows, cols, nb, 1, (size_t)nb * cap * cols * 8, false, internal, up)) return rc;
     lap("h2d");
-    rc = lineq_fme_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, u, darkshadow, (R32 *)dout.p, cap, (int32_t *)dr.p, (int32_t *)dk.p);
-    if (rc) return rc;
+    if (const int rc = lineq_fme_batch_dev(ctx, nb, (const R32 *)up.di.p, rows, cols, rhs, u, darkshadow, (R32 *)up.dout.p, cap, up.d_rows(),
+                                           up.d_verdict(0))) return rc;
     lap("kernel");
-    return packed_rows_down(ctx, nb, cols, cap, dout, dr, dk, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, internal,
-                            "fme: a result needs more rows than cap_rows", out, out_cap_rows, view, row_offsets, out_ok, (int32_t *)0, lap);
+    return packed_rows_down(ctx, up, cols, cap, "fme: a result needs more rows than cap_rows", out, out_cap_rows, view, row_offsets, &out_ok, lap);
 }
 
-// ---- projection: a list of variables eliminated in ONE launch (k_fme_chain_batch) -------------------------------------------
-// THE plan of a projection call (the launch and xpg_test_lineq_project_plan both ask it): capacities, LDS layout, geometry and
-// the seats' intermediates, from the shape alone. cap_rows <= 0: fme's default for `rows`; cap_out_rows <= 0 (or above cap):
-// cap. The LDS layout is fme_lds(cap, cap, cols), the rule calcBound's chains run under -- measured for k_fme_batch, not again
-// for the chain kernel. Returns 0, XPG_ERR_SHAPE or XPG_ERR_UNSUPPORTED (LDS over 160 KB, cap > 32767).
-struct ProjectPlan { int cap, cap_out, cap_lds; LineqGeom q; long long seats; size_t seat_bytes; };
-inline int project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_rows, ProjectPlan & p)
+// ---- THE plan of a fused call of this family (projection, levels, calcBound; one shape or mixed; the hull's producer) ------------
+// One struct, and ONE rule for the capacities and the envelope (lineq_plan_rule); the five named rules below it -- project_plan,
+// levels_plan, bounds_plan, ragged_chain_plan, bounds_ragged_plan -- are their own argument checks and per-system sums followed by
+// one call of it. The launch and the xpg_test_lineq_*_plan view of a family ask the same named rule.
+//   rows, cols   the envelope: the most rows and the widest system of the batch (one shape: its own)
+//   slots        results of the call (cap_out rows of the system's OWN cols each), out_bytes their bytes
+//   steps        elimination steps of the batch (calcBound), of one system (the uniform calcBound)
+struct LineqPlan {
+    int launches, rows, cols, cap, cap_out, cap_lds; LineqGeom q; long long seats, slots, steps; size_t seat_bytes, out_bytes;
+};
+// What tells the families apart in the rule: cap_rows <= 0 is fme's worst case rows^2 / 4 + rows + 1 (every positive-negative pair
+// and the rows without the variable) or the packed calcBound's 4 * rows + 16; cap_out_rows <= 0 is cap, or min(cap, 4 * rows + 16)
+// where the output slots follow nb * n_elim and not the grid (levels: at the projection's worst case the slots of 1024 nests of
+// 60 rows and depth 6 would be gigabytes); a seat has two cap-row slots or three (calcBound: two sides and the held prefix); and
+// the ragged kernels' seat is the workgroup (fme's whole wave), so they refuse a geometry with several systems per workgroup.
+struct PlanKind { bool fme_cap, levels_out; int seat_slots; bool seat_is_workgroup; };
+inline PlanKind kind_chain(bool levels, bool ragged) { const PlanKind k = {true, levels, 2, ragged}; return k; }
+inline PlanKind kind_bounds(bool ragged) { const PlanKind k = {false, false, 3, ragged}; return k; }
+// The rule. cap_out_rows above cap: cap. The LDS layout is fme_lds(cap, cap, cols), the rule calcBound's chains run under --
+// measured for k_fme_batch, not again for the chain kernels. Returns 0 or XPG_ERR_UNSUPPORTED: rows or cap
+// above 32767 (rows are indexed as short; the guard on rows keeps rows * rows an int), LDS over 160 KB, a seat that is no workgroup.
+inline int lineq_plan_rule(int nb, int rows, int cols, int cap_rows, int cap_out_rows, const PlanKind & k, LineqPlan & p)
+{
+    p.launches = 1; p.rows = rows; p.cols = cols;
+    if (rows > 32767) return XPG_ERR_UNSUPPORTED;
+    const int few = 4 * rows + 16;
+    p.cap = cap_rows > 0 ? cap_rows : (k.fme_cap ? rows * rows / 4 + rows + 1 : few);
+    if (p.cap < rows) p.cap = rows;
+    p.cap_out = cap_out_rows > p.cap ? p.cap : cap_out_rows;
+    if (cap_out_rows <= 0) p.cap_out = k.levels_out && few < p.cap ? few : p.cap;
+    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
+    const FmeLds fl = fme_lds(p.cap, p.cap, cols);
+    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    p.cap_lds = fl.cap_lds;
+    p.q = lineq_geom(nb, 64, fl.lds);
+    if (k.seat_is_workgroup && p.q.G != 1) return XPG_ERR_UNSUPPORTED;
+    p.seats = (long long)p.q.grid * p.q.G;
+    p.seat_bytes = (size_t)p.seats * k.seat_slots * (size_t)p.cap * cols * 8;
+    return 0;
+}
+inline void plan_slots(LineqPlan & p, long long slots, long long cells, long long steps)
+{
+    p.slots = slots; p.steps = steps; p.out_bytes = (size_t)cells * (size_t)p.cap_out * 8;
+}
+// A projection of nb systems of one shape (k_fme_chain_batch): one result per system.
+inline int project_plan(int nb, int rows, int cols, int cap_rows, int cap_out_rows, LineqPlan & p)
 {
     if (nb <= 0 || rows <= 0 || cols <= 1) return XPG_ERR_SHAPE;
-    p.cap = cap_rows <= 0 ? rows * rows / 4 + rows + 1 : cap_rows;
-    if (p.cap < rows) p.cap = rows;
-    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
-    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
-    const FmeLds fl = fme_lds(p.cap, p.cap, cols);
-    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
-    p.cap_lds = fl.cap_lds;
-    p.q = lineq_geom(nb, 64, fl.lds);
-    p.seats = (long long)p.q.grid * p.q.G;
-    p.seat_bytes = (size_t)p.seats * 2 * (size_t)p.cap * cols * 8;
+    if (const int rc = lineq_plan_rule(nb, rows, cols, cap_rows, cap_out_rows, kind_chain(false, false), p)) return rc;
+    plan_slots(p, nb, (long long)nb * cols, 0);
     return 0;
 }
-// What the calling thread's last xpg_lineq_project_batch_* call did (xpg_lineq_project_last_route): launches of the chain
-// kernel (1), its grid, groups per workgroup, LDS bytes per system, cap_lds, bytes of seat slots the launch was given.
-struct ProjectRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes; };
-inline ProjectRoute & project_route() { static thread_local ProjectRoute r = {0, 0, 0, 0, 0, 0}; return r; }
-// THE plan of a fused calcBound call (k_calc_bound_batch; the launch and xpg_test_lineq_bounds_plan both ask it). As
-// project_plan, but cap_rows <= 0 is the packed calcBound's default 4 * rows + 16, a seat has THREE cap-row slots (two sides
-// and the held prefix), and the plan knows the steps a system takes: rhs - 1 prefix steps and rhs (rhs - 1) / 2 tail steps.
-struct BoundsPlan { int cap, cap_out, cap_lds; LineqGeom q; long long seats, steps; size_t seat_bytes; };
-inline int bounds_plan(int nb, int rows, int cols, int rhs, int cap_rows, int cap_out_rows, BoundsPlan & p)
+// The projection that keeps every level (k_fme_levels_batch): the walk, the seats and the geometry are the projection's, the
+// results are one per system and list entry (out_bytes: the level slots).
+inline int levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, LineqPlan & p)
+{
+    if (n_elim <= 0) return XPG_ERR_SHAPE;
+    if (n_elim > FME_CHAIN_MAX) return XPG_ERR_UNSUPPORTED;
+    if (nb <= 0 || rows <= 0 || cols <= 1) return XPG_ERR_SHAPE;
+    if (const int rc = lineq_plan_rule(nb, rows, cols, cap_rows, cap_out_rows, kind_chain(true, false), p)) return rc;
+    plan_slots(p, (long long)nb * n_elim, (long long)nb * n_elim * cols, 0);
+    return 0;
+}
+// A fused calcBound (k_calc_bound_batch): one result per system and variable; a system takes rhs - 1 prefix steps and
+// rhs (rhs - 1) / 2 tail steps.
+inline int bounds_plan(int nb, int rows, int cols, int rhs, int cap_rows, int cap_out_rows, LineqPlan & p)
 {
     if (nb <= 0 || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols) return XPG_ERR_SHAPE;
-    p.cap = cap_rows <= 0 ? 4 * rows + 16 : cap_rows;
-    if (p.cap < rows) p.cap = rows;
-    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
-    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
-    const FmeLds fl = fme_lds(p.cap, p.cap, cols);
-    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
-    p.cap_lds = fl.cap_lds;
-    p.q = lineq_geom(nb, 64, fl.lds);
-    p.seats = (long long)p.q.grid * p.q.G;
-    p.seat_bytes = (size_t)p.seats * 3 * (size_t)p.cap * cols * 8;
-    p.steps = (long long)(rhs - 1) * (rhs + 2) / 2;
+    if (const int rc = lineq_plan_rule(nb, rows, cols, cap_rows, cap_out_rows, kind_bounds(false), p)) return rc;
+    plan_slots(p, (long long)nb * rhs, (long long)nb * rhs * cols, (long long)(rhs - 1) * (rhs + 2) / 2);
     return 0;
 }
-// What the calling thread's last xpg_lineq_bounds_batch_* call did (xpg_lineq_bounds_last_route): ProjectRoute's figures and
-// the elimination steps per system.
-struct BoundsRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, steps; };
-inline BoundsRoute & bounds_route() { static thread_local BoundsRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
 
+// ---- THE route record: what the calling thread's last call of a family did (xpg_lineq_*_last_route) ---------------------------
+// One record type, one thread_local record per family (they are independent: a caller reads one after calling another). A call
+// clears its family's record when it begins and writes it once its launch is enqueued; the shared pieces below (the enqueue
+// functions, the ways up and down) write none -- the hull calls launch the ragged kernels and leave the ragged records alone.
+// plan_figures turns a plan into the figures; the launch site and the family's xpg_test_lineq_*_plan view both call it, the view
+// showing the capacities the plan settled on behind the route's figures:
+//   family          the route's figures                                                         the view adds
+//   PROJECT         launches (1) grid groups sys_lds cap_lds seat_bytes                         cap cap_out
+//   LEVELS          the same six, level_bytes (bytes of the level slots)                        cap cap_out
+//   RAGGED          the same six, out_bytes (bytes of the output slots)                         cap cap_out cols rows (the envelope)
+//   BOUNDS          the same six, steps (elimination steps per system)                          cap cap_out
+//   BOUNDS_RAGGED   the same six, out_bytes, steps (of the whole batch)                         cap cap_out cols rows
+//   HULL            producer launches (1), k_group_reduce launches (1), its grid and LDS bytes   cap cap_out cap_hull lds_rows ecols
+//                   per workgroup, groups at home in LDS / in a device slot, bytes of the         (hull_figures, lineq_hull_host.hip.h;
+//                   producer's seats / of the device slots / of the output slots, and the         the view has no `gathered`)
+//                   rows gathered over all groups (counted after the call; not a plan figure)
+// groups: systems per workgroup; sys_lds: LDS bytes per system; seat_bytes: bytes of seat slots the launch was given.
+enum { ROUTE_PROJECT, ROUTE_LEVELS, ROUTE_RAGGED, ROUTE_BOUNDS, ROUTE_BOUNDS_RAGGED, ROUTE_HULL, ROUTE_FAMILIES };
+enum { ROUTE_MAX = 10, FIGURES_MAX = 16 };
+struct LineqRoute { long long f[ROUTE_MAX]; };
+const int ROUTE_FIGURES[ROUTE_FAMILIES] = {6, 7, 7, 7, 8, 10};
+inline LineqRoute & lineq_route(int family) { static thread_local LineqRoute r[ROUTE_FAMILIES] = {}; return r[family]; }
+inline void route_clear(int family) { lineq_route(family) = LineqRoute(); }
+inline void route_write(int family, const long long * f)
+{
+    for (int k = 0; k < ROUTE_FIGURES[family]; k++) lineq_route(family).f[k] = f[k];
+}
+inline int figures_out(long long * out, int n, const long long * f, int have)
+{
+    for (int k = 0; k < n && k < have; k++) out[k] = f[k];
+    return 0;
+}
+inline int route_out(int family, long long * out, int n)
+{
+    return out && n >= 0 ? figures_out(out, n, lineq_route(family).f, ROUTE_FIGURES[family]) : XPG_ERR_SHAPE;
+}
+// The figures of a plan (the table above, the hull's row apart): the route's, then the view's. Returns how many there are.
+inline int plan_figures(int family, const LineqPlan & p, long long * f)
+{
+    const bool ragged = family == ROUTE_RAGGED || family == ROUTE_BOUNDS_RAGGED;
+    int n = 0;
+    f[n++] = p.launches; f[n++] = p.q.grid; f[n++] = p.q.G; f[n++] = p.q.sys_lds; f[n++] = p.cap_lds; f[n++] = (long long)p.seat_bytes;
+    if (family == ROUTE_LEVELS || ragged) f[n++] = (long long)p.out_bytes;
+    if (family == ROUTE_BOUNDS || family == ROUTE_BOUNDS_RAGGED) f[n++] = p.steps;
+    f[n++] = p.cap; f[n++] = p.cap_out;
+    if (ragged) { f[n++] = p.cols; f[n++] = p.rows; }
+    return n;
+}
+inline void route_write(int family, const LineqPlan & p) { long long f[FIGURES_MAX]; plan_figures(family, p, f); route_write(family, f); }
+// (a plan view: rc is the named rule's answer for p -- an error is the view's answer)
+inline int plan_out(int family, int rc, const LineqPlan & p, long long * out, int n)
+{
+    long long f[FIGURES_MAX];
+    return rc ? rc : figures_out(out, n, f, plan_figures(family, p, f));
+}
+
+// ---- projection: a list of variables eliminated in ONE launch (k_fme_chain_batch), and the projection that keeps every level: the
+// same walk, the rows after EACH step stored (k_fme_levels_batch) ---------------------------------------------------------------
 inline int project_check(int cols, int rhs, const int32_t * elim, int n_elim)
 {
     if (cols <= 1 || rhs < 1 || rhs >= cols || !elim || n_elim <= 0) return XPG_ERR_SHAPE;
     for (int k = 0; k < n_elim; k++) if (elim[k] < 0 || elim[k] >= rhs) return XPG_ERR_SHAPE;
     return n_elim > FME_CHAIN_MAX ? XPG_ERR_UNSUPPORTED : 0;
 }
-// Device arrays, enqueue only: d_outs [nb][cap_out_rows][cols] receives the live rows of each result (nothing behind them),
-// d_rows / d_ok / d_steps [nb] as k_fme_chain_batch writes them. The seats' slots are the handle's (grow-only). The row
-// stride of d_outs is the caller's: cap_rows < rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE, nothing is defaulted or
-// clamped but cap_out_rows <= 0, which stands for cap_rows.
-inline int lineq_project_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
-                                   int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows,
-                                   int32_t * d_ok, int32_t * d_steps)
+// Device arrays, enqueue only; `p` is the plan of what was launched (launches == 0: nothing). Projection: d_outs
+// [nb][cap_out_rows][cols] receives the live rows of each result (nothing behind them), d_rows [nb]. Levels: d_outs
+// [nb][n_elim][cap_out_rows][cols], level k of system b in slot (b, k), d_rows [nb][n_elim]. d_ok / d_steps [nb] as the kernels
+// write them. The seats' slots are the handle's (grow-only, one area for both). The row stride of d_outs is the caller's, who laid
+// d_outs out with it: cap_rows < rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE, nothing is defaulted or clamped but (projection)
+// cap_out_rows <= 0, which stands for cap_rows; levels refuse that too.
+inline int chain_batch_enqueue(xpg_ctx * ctx, bool levels, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
+                               int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows, int32_t * d_ok,
+                               int32_t * d_steps, LineqPlan & p)
 {
-    project_route() = ProjectRoute{0, 0, 0, 0, 0, 0};
+    p = LineqPlan();
     if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
     if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || !d_rows || !d_ok || !d_steps) return XPG_ERR_SHAPE;
-    // the caller laid d_outs out with these capacities: none is replaced here (cap_out_rows <= 0 alone stands for cap_rows)
-    if (cap_rows < rows || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
+    if (cap_rows < rows || cap_out_rows > cap_rows || (levels && cap_out_rows <= 0)) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    ProjectPlan p;
-    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, p)) return rc;
+    if (levels && (long long)nb * n_elim > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    LineqPlan q;
+    if (const int rc = levels ? levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, q) : project_plan(nb, rows, cols, cap_rows, cap_out_rows, q))
+        return rc;
     Scratch & slots = ctx->scratch[SCRATCH_LINEQ_PROJECT];
-    if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_project seats)")) return rc;
+    if (const int rc = scratch_reserve(ctx, slots, q.seat_bytes, q.seat_bytes, levels ? "hipMalloc(lineq_levels seats)" : "hipMalloc(lineq_project seats)"))
+        return rc;
     ElimList el;
     el.n = n_elim;
     for (int k = 0; k < FME_CHAIN_MAX; k++) el.u[k] = k < n_elim ? elim[k] : 0;
-    XPG_TRY(lds_limit((const void *)k_fme_chain_batch, ctx->device, p.q.lds));
-    hipLaunchKernelGGL(k_fme_chain_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, el,
-                       darkshadow, (R32 *)slots.buf, p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps,
-                       p.cap_lds, p.q.sys_lds);
+    const auto kernel = levels ? k_fme_levels_batch : k_fme_chain_batch;
+    XPG_TRY(lds_limit((const void *)kernel, ctx->device, q.q.lds));
+    hipLaunchKernelGGL(kernel, dim3(q.q.grid), q.q.block, q.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, el, darkshadow, (R32 *)slots.buf,
+                       q.cap, d_outs, q.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps, q.cap_lds, q.q.sys_lds);
     XPG_TRY(hipGetLastError());
-    project_route() = ProjectRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes};
+    p = q;
     return 0;
 }
-// Host arrays with a PACKED result, as lineq_fme_batch_packed: one upload, the one launch, k_rows_scan / k_pack_rows, one
-// synchronisation before the rows come down (none after it where the slots are small enough to come down with the counts).
-// A system that ends with out_ok <= 0 contributes no rows; the others are packed all the same. XPG_ERR_SHAPE when `out` holds
-// fewer than row_offsets[nb] rows (row_offsets, out_ok and out_steps are filled); neither out nor view: a sizing call.
-inline int lineq_project_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, const int32_t * elim,
-                                      int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
-                                      const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
+inline int lineq_chain_batch_dev(xpg_ctx * ctx, bool levels, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
+                                 int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows, int32_t * d_ok,
+                                 int32_t * d_steps)
 {
-    if (view) *view = 0;
-    project_route() = ProjectRoute{0, 0, 0, 0, 0, 0};
-    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
-    if (!ctx || nb < 0 || !mats || rows <= 0 || !row_offsets || !out_ok || !out_steps || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
-    if (nb == 0) { row_offsets[0] = 0; return 0; }
-    ProjectPlan p;
-    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, p)) return rc;
-    const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nb * p.cap_out * cols * 8;
-    const size_t meta = (size_t)(nb + 1) * 8 + (size_t)nb * 12;      // offsets, then ok, rows and steps
-    const size_t meta_al = (meta + 255) & ~(size_t)255;
-    DevBuf di, dout, dr, dk, ds, doff;
-    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nb * 4)); XPG_TRY(dk.alloc(ctx, (size_t)nb * 4));
-    XPG_TRY(ds.alloc(ctx, (size_t)nb * 4)); XPG_TRY(doff.alloc(ctx, (size_t)(nb + 1) * 8));
-    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
-    if (rc) return rc;
-    char * hp = hpack_buf(ctx, false);
-    if (small_in) {
-        memcpy(hp + meta_al, mats, bi);
-        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = lineq_project_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, elim, n_elim, darkshadow, p.cap, p.cap_out, (R32 *)dout.p,
-                                 (int32_t *)dr.p, (int32_t *)dk.p, (int32_t *)ds.p);
-    if (rc) return rc;
-    return packed_rows_down(ctx, nb, cols, p.cap_out, dout, dr, dk, &ds, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
-                            out, out_cap_rows, view, row_offsets, out_ok, out_steps, [](const char *) {});
-}
-
-// ---- projection that keeps every level: the list eliminated in ONE launch, the rows after EACH step stored (k_fme_levels_batch)
-// THE plan of a levels call (the launch and xpg_test_lineq_levels_plan both ask it): project_plan's capacities, LDS layout,
-// geometry and seats -- the walk is the projection's -- except that the level slots follow nb * n_elim, not the grid, so
-// cap_out_rows <= 0 is min(cap_rows, 4 * rows + 16) (the packed calcBound's default for a result) instead of cap_rows: at the
-// projection's worst-case default the slots of 1024 nests of 60 rows and depth 6 would be gigabytes.
-struct LevelsPlan { ProjectPlan p; size_t level_bytes; };
-inline int levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, LevelsPlan & l)
-{
-    if (n_elim <= 0) return XPG_ERR_SHAPE;
-    if (n_elim > FME_CHAIN_MAX) return XPG_ERR_UNSUPPORTED;
-    if (const int rc = project_plan(nb, rows, cols, cap_rows, cap_out_rows, l.p)) return rc;
-    if (cap_out_rows <= 0) l.p.cap_out = l.p.cap < 4 * rows + 16 ? l.p.cap : 4 * rows + 16;
-    l.level_bytes = (size_t)nb * n_elim * (size_t)l.p.cap_out * cols * 8;
-    return 0;
-}
-// What the calling thread's last xpg_lineq_levels_batch_* call did (xpg_lineq_levels_last_route): ProjectRoute's figures and
-// the bytes of the level slots.
-struct LevelsRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, level_bytes; };
-inline LevelsRoute & levels_route() { static thread_local LevelsRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
-// Device arrays, enqueue only: d_outs [nb][n_elim][cap_out_rows][cols] receives the live rows of level k of system b in slot
-// (b, k) (nothing behind them), d_rows [nb][n_elim] their counts, d_ok / d_steps [nb] as k_fme_levels_batch writes them. The
-// seats are the projection's (the same grow-only scratch, the same two slots per seat). Both capacities are the caller's, who
-// laid d_outs out with them: cap_rows < rows, cap_out_rows <= 0 or cap_out_rows > cap_rows is XPG_ERR_SHAPE.
-inline int lineq_levels_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, const int32_t * elim,
-                                  int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows,
-                                  int32_t * d_ok, int32_t * d_steps)
-{
-    levels_route() = LevelsRoute{0, 0, 0, 0, 0, 0, 0};
-    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
-    if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || !d_rows || !d_ok || !d_steps) return XPG_ERR_SHAPE;
-    if (cap_rows < rows || cap_out_rows <= 0 || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
-    if (nb == 0) return 0;
-    if ((long long)nb * n_elim > INT_MAX) return XPG_ERR_UNSUPPORTED;
-    LevelsPlan l;
-    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
-    const ProjectPlan & p = l.p;
-    Scratch & slots = ctx->scratch[SCRATCH_LINEQ_PROJECT];
-    if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_levels seats)")) return rc;
-    ElimList el;
-    el.n = n_elim;
-    for (int k = 0; k < FME_CHAIN_MAX; k++) el.u[k] = k < n_elim ? elim[k] : 0;
-    XPG_TRY(lds_limit((const void *)k_fme_levels_batch, ctx->device, p.q.lds));
-    hipLaunchKernelGGL(k_fme_levels_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, el,
-                       darkshadow, (R32 *)slots.buf, p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps,
-                       p.cap_lds, p.q.sys_lds);
-    XPG_TRY(hipGetLastError());
-    levels_route() = LevelsRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)l.level_bytes};
-    return 0;
-}
-// Host arrays with a PACKED result in the layout of lineq_bounds_batch_packed: row_offsets [nb * n_elim + 1], entry
-// b * n_elim + k where level k of system b starts. One upload, the one launch, packed_rows_down over the nb * n_elim results;
-// the verdicts (ok, steps: [nb] each) come down through hred beside it, under the same synchronisation. A system with
-// out_ok <= 0 contributes no rows at any level, the others are packed all the same; out / view / sizing call as
-// lineq_project_batch_packed.
-inline int lineq_levels_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, const int32_t * elim,
-                                     int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
-                                     const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
-{
-    if (view) *view = 0;
-    levels_route() = LevelsRoute{0, 0, 0, 0, 0, 0, 0};
-    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
-    if (!ctx || nb < 0 || !mats || rows <= 0 || !row_offsets || !out_ok || !out_steps || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
-    if (nb == 0) { row_offsets[0] = 0; return 0; }
-    LevelsPlan l;
-    if (const int rc = levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, l)) return rc;
-    if ((long long)nb * n_elim > INT_MAX) return XPG_ERR_UNSUPPORTED;
-    const int nres = nb * n_elim;
-    const size_t bi = (size_t)nb * rows * cols * 8, bo = l.level_bytes, bv = (size_t)nb * 4;
-    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 12;  // offsets, then (unused) ok, rows and (unused) steps
-    const size_t meta_al = (meta + 255) & ~(size_t)255;
-    DevBuf di, dout, dr, dv, doff;                                   // dv: ok and steps, [2][nb]
-    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nres * 4)); XPG_TRY(dv.alloc(ctx, 2 * bv));
-    XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
-    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
-    if (rc) return rc;
-    if ((rc = hpack_reserve(ctx, 2 * bv, true))) return rc;
-    char * hp = hpack_buf(ctx, false);
-    int32_t * hv = (int32_t *)hpack_buf(ctx, true);
-    if (small_in) {
-        memcpy(hp + meta_al, mats, bi);
-        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int32_t * const d_ok = (int32_t *)dv.p;
-    rc = lineq_levels_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, elim, n_elim, darkshadow, l.p.cap, l.p.cap_out, (R32 *)dout.p,
-                                (int32_t *)dr.p, d_ok, d_ok + nb);
-    if (rc) return rc;
-    XPG_TRY(hipMemcpyAsync(hv, dv.p, 2 * bv, hipMemcpyDeviceToHost, ctx->stream));
-    rc = packed_rows_down(ctx, nres, cols, l.p.cap_out, dout, dr, dv, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
-                          out, out_cap_rows, view, row_offsets, (int32_t *)0, (int32_t *)0, [](const char *) {});
-    if (rc == 0 || rc == XPG_ERR_SHAPE) {                            // (it has synchronised: a buffer too small still gets its verdicts)
-        memcpy(out_ok, hv, bv); memcpy(out_steps, hv + nb, bv);
-    }
+    const int family = levels ? ROUTE_LEVELS : ROUTE_PROJECT;
+    route_clear(family);
+    LineqPlan p;
+    const int rc = chain_batch_enqueue(ctx, levels, nb, d_mats, rows, cols, rhs, elim, n_elim, darkshadow, cap_rows, cap_out_rows, d_outs, d_rows,
+                                       d_ok, d_steps, p);
+    if (rc == 0) route_write(family, p);
     return rc;
+}
+// Host arrays with a PACKED result, as lineq_fme_batch_packed: one upload (packed_up), the one launch, and packed_rows_down --
+// k_rows_scan / k_pack_rows and one synchronisation before the rows come down (none after it where the slots are small enough to
+// come down with the counts). Projection: row_offsets [nb + 1]. Levels: row_offsets [nb * n_elim + 1], entry b * n_elim + k where
+// level k of system b starts (the layout of lineq_bounds_batch_packed). A system that ends with out_ok <= 0 contributes no rows (at
+// any level); the others are packed all the same. XPG_ERR_SHAPE when `out` holds fewer than the rows needed (row_offsets, out_ok
+// and out_steps are filled); neither out nor view: a sizing call.
+inline int lineq_chain_batch_packed(xpg_ctx * ctx, bool levels, int nb, const R32 * mats, int rows, int cols, int rhs, const int32_t * elim,
+                                    int n_elim, int darkshadow, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
+                                    const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps)
+{
+    const int family = levels ? ROUTE_LEVELS : ROUTE_PROJECT;
+    if (view) *view = 0;
+    route_clear(family);
+    if (const int rc = project_check(cols, rhs, elim, n_elim)) return rc;          // the list's rules first: they need no handle
+    if (!ctx || nb < 0 || !mats || rows <= 0 || !row_offsets || !out_ok || !out_steps || (out && out_cap_rows < 0)) return XPG_ERR_SHAPE;
+    if (nb == 0) { row_offsets[0] = 0; return 0; }
+    LineqPlan p;
+    if (const int rc = levels ? levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, p) : project_plan(nb, rows, cols, cap_rows, cap_out_rows, p))
+        return rc;
+    if (p.slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    PackedUp u;
+    if (const int rc = packed_up(ctx, nb, mats, rows, cols, (int)p.slots, 2, p.out_bytes, false, false, u)) return rc;
+    if (const int rc = chain_batch_enqueue(ctx, levels, nb, (const R32 *)u.di.p, rows, cols, rhs, elim, n_elim, darkshadow, p.cap, p.cap_out,
+                                           (R32 *)u.dout.p, u.d_rows(), u.d_verdict(0), u.d_verdict(1), p)) return rc;
+    route_write(family, p);
+    int32_t * const verdicts[2] = {out_ok, out_steps};
+    return packed_rows_down(ctx, u, cols, p.cap_out, (const char *)0, out, out_cap_rows, view, row_offsets, verdicts, no_lap);
 }
 
 // ---- projection / levels for systems of MIXED shapes and lists: one launch of k_fme_chain_ragged ---------------------------------
-// THE plan of a ragged call (the launch and xpg_test_lineq_ragged_plan both ask it), decided before anything is launched:
-// every system's list under project_check's rules (a shape error anywhere wins over a list too long anywhere, as inside one
-// list), then the ENVELOPE -- the widest system's cols, the capacities of the system with the most rows -- under project_plan's
-// / levels_plan's rules, so that a batch whose shapes all agree gets exactly the uniform plan. The output slots follow the
-// systems, cap_out x OWN cols cells each: one per system, or (levels) one per list entry.
+// The plan of a ragged call, decided before anything is launched: every system's list under project_check's rules (a shape error
+// anywhere wins over a list too long anywhere, as inside one list), then the ENVELOPE -- the widest system's cols, the capacities
+// of the system with the most rows -- under the rule of project_plan / levels_plan, so that a batch whose shapes all agree gets
+// exactly the uniform plan. The output slots follow the systems, cap_out x OWN cols cells each: one per system, or (levels) one
+// per list entry.
 //   rhs_idx NULL: the last column of each system. elim_offsets [nb + 1], elim_offsets[0] == 0, system b's list is
 //   elim[elim_offsets[b] .. elim_offsets[b + 1]).
-struct RaggedChainPlan { int cols, rows, cap, cap_out, cap_lds; LineqGeom q; long long seats, slots; size_t seat_bytes, out_bytes; };
 inline int ragged_chain_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, const int32_t * elim,
-                             const int32_t * elim_offsets, bool levels, int cap_rows, int cap_out_rows, RaggedChainPlan & p)
+                             const int32_t * elim_offsets, bool levels, int cap_rows, int cap_out_rows, LineqPlan & p)
 {
     if (nb <= 0 || !rows || !cols || !elim_offsets || elim_offsets[0] != 0) return XPG_ERR_SHAPE;
     bool too_long = false;
     long long cells = 0;
-    p.cols = 0; p.rows = 0;
+    int erows = 0, ecols = 0;
     for (int b = 0; b < nb; b++) {
         if (rows[b] <= 0 || elim_offsets[b + 1] < elim_offsets[b]) return XPG_ERR_SHAPE;
         const int n = elim_offsets[b + 1] - elim_offsets[b];
         const int rc = project_check(cols[b], rhs_idx ? rhs_idx[b] : cols[b] - 1, elim ? elim + elim_offsets[b] : elim, n);
         if (rc == XPG_ERR_SHAPE) return rc;
         too_long |= rc != 0;
-        if (cols[b] > p.cols) p.cols = cols[b];
-        if (rows[b] > p.rows) p.rows = rows[b];
+        if (cols[b] > ecols) ecols = cols[b];
+        if (rows[b] > erows) erows = rows[b];
         cells += (long long)(levels ? n : 1) * cols[b];
     }
     if (too_long) return XPG_ERR_UNSUPPORTED;
-    if (p.rows > 32767) return XPG_ERR_UNSUPPORTED;                            // (cap >= rows: refused below in any case)
-    p.cap = cap_rows <= 0 ? p.rows * p.rows / 4 + p.rows + 1 : cap_rows;
-    if (p.cap < p.rows) p.cap = p.rows;
-    p.cap_out = cap_out_rows > p.cap ? p.cap : cap_out_rows;
-    if (cap_out_rows <= 0) p.cap_out = levels && 4 * p.rows + 16 < p.cap ? 4 * p.rows + 16 : p.cap;
-    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
-    const FmeLds fl = fme_lds(p.cap, p.cap, p.cols);
-    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
-    p.cap_lds = fl.cap_lds;
-    p.q = lineq_geom(nb, 64, fl.lds);
-    if (p.q.G != 1) return XPG_ERR_UNSUPPORTED;                                // (the kernel's seat is the workgroup: fme's whole wave)
-    p.seats = (long long)p.q.grid * p.q.G;
-    p.seat_bytes = (size_t)p.seats * 2 * (size_t)p.cap * p.cols * 8;
-    p.slots = levels ? elim_offsets[nb] : nb;
-    p.out_bytes = (size_t)cells * (size_t)p.cap_out * 8;
+    if (const int rc = lineq_plan_rule(nb, erows, ecols, cap_rows, cap_out_rows, kind_chain(levels, true), p)) return rc;
+    plan_slots(p, levels ? elim_offsets[nb] : nb, cells, 0);
     return 0;
 }
-// What the calling thread's last xpg_lineq_{project,levels}_batch_ragged_rat32 call did (xpg_lineq_ragged_last_route): launches
-// of the chain kernel (1), its grid, systems per workgroup, LDS bytes per system, cap_lds, bytes of seat slots, bytes of
-// output slots.
-struct RaggedRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, out_bytes; };
-inline RaggedRoute & ragged_route() { static thread_local RaggedRoute r = {0, 0, 0, 0, 0, 0, 0}; return r; }
-// The block a ragged packed call (chain, levels, calcBound) sends up, and the buffers of its way down. ONE upload: [descriptors]
-// [lists: nlist entries of `elim`, none where nlist == 0][the systems, gathered back to back], built in the handle's pinned
-// buffer behind meta_al bytes kept for what comes down first (cell offsets [nres + 1], then the ints as on the device) and, with
-// small slots, in front of room for the slots themselves. list(b, at, n, per), asked once per system in order, gives the
-// descriptor's list_at and list_n and the number of result slots of system b (cap_out x OWN cols cells each, following the
-// systems' order: out_off). dints: rows [nres], then nv verdict arrays [nb].
+// The block a ragged packed call (chain, levels, calcBound, hull) sends up, and the buffers of its way down. ONE upload:
+// [descriptors][lists: nlist entries of `elim`, none where nlist == 0][the systems, gathered back to back], built in the handle's
+// pinned buffer behind meta_bytes kept for what comes down first (ragged_meta of the results that come down) and, with small
+// slots, in front of room for the slots themselves. list(b, at, n, per), asked once per system in order, gives the descriptor's
+// list_at and list_n and the number of result slots of system b (cap_out x OWN cols cells each, following the systems' order:
+// out_off). dints: rows [nres], then nv verdict arrays [nb].
 struct RaggedUp {
     DevBuf dup, dout, dints, dcells, doff;
-    int nres, nv, cap_out; size_t up_al, meta_al, bo; bool small_out;
+    int nb, nres, nv, cap_out; size_t up_al, meta_al, bo; bool small_out;
     RaggedSys * hd; const RaggedSys * d_sys; const int * d_lists; const R32 * d_mats;
+    int * d_rows() const { return (int *)dints.p; }
+    int * d_verdict(int v) const { return (int *)dints.p + nres + (size_t)v * nb; }
 };
+// cell offsets [nres + 1], then the ints as on the device: counts [nres] and nv verdict arrays [n]
+inline size_t ragged_meta(int nres, int n, int nv) { return (size_t)(nres + 1) * 8 + ((size_t)nres + (size_t)n * nv) * 4; }
 template <class List>
 inline int ragged_up(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * rows, const int32_t * cols, const long long * offsets,
-                     const int32_t * rhs_idx, const int32_t * elim, int nlist, List list, int nres, int nv, int cap_out, size_t out_bytes, RaggedUp & u)
+                     const int32_t * rhs_idx, const int32_t * elim, int nlist, List list, int nres, int nv, int cap_out, size_t out_bytes,
+                     size_t meta_bytes, RaggedUp & u)
 {
     const size_t b_desc = (size_t)nb * sizeof(RaggedSys), b_list = ((size_t)nlist * 4 + 7) & ~(size_t)7;
     size_t in_cells = 0;
     for (int b = 0; b < nb; b++) in_cells += (size_t)rows[b] * cols[b];
     const size_t b_up = b_desc + b_list + in_cells * 8;
-    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 4 + (size_t)nb * 4 * nv;
-    u.nres = nres; u.nv = nv; u.cap_out = cap_out; u.bo = out_bytes;
-    u.up_al = (b_up + 255) & ~(size_t)255; u.meta_al = (meta + 255) & ~(size_t)255;
+    u.nb = nb; u.nres = nres; u.nv = nv; u.cap_out = cap_out; u.bo = out_bytes;
+    u.up_al = (b_up + 255) & ~(size_t)255; u.meta_al = (meta_bytes + 255) & ~(size_t)255;
     u.small_out = u.bo <= ((size_t)512 << 10);
     XPG_TRY(u.dup.alloc(ctx, b_up)); XPG_TRY(u.dout.alloc(ctx, u.bo)); XPG_TRY(u.dints.alloc(ctx, (size_t)(nres + nv * (size_t)nb) * 4));
     XPG_TRY(u.dcells.alloc(ctx, (size_t)nres * 4)); XPG_TRY(u.doff.alloc(ctx, (size_t)(nres + 1) * 8));
@@ -620,37 +590,52 @@ inline int ragged_up(xpg_ctx * ctx, int nb, const R32 * mats, const int32_t * ro
     u.d_mats = (const R32 *)((char *)u.dup.p + b_desc + b_list);
     return 0;
 }
+// What a ragged way down brings, said by the call that launched: the n descriptors whose out_off / list_at / list_n place the
+// results in the slot buffer, on the host and on the device (the systems of a ragged call; the GROUPS of a hull call, whose
+// regions are the members' slots), the slot buffer and its bytes, the ints (counts [nres], then nv verdict arrays [n]) with the
+// scratch of the scan (dcells [nres], doff [nres + 1]), cap_out, and where the slots sit in the pinned block when they are small
+// enough to come down whole.
+struct RaggedDown {
+    const RaggedSys * hd, * d_sys; const DevBuf * dout; size_t bo; const DevBuf * dints, * dcells, * doff;
+    int nres, nv, cap_out; size_t slots_at; bool small_out;
+};
+inline RaggedDown ragged_down(const RaggedUp & u)
+{
+    const RaggedDown d = {u.hd, u.d_sys, &u.dout, u.bo, &u.dints, &u.dcells, &u.doff, u.nres, u.nv, u.cap_out, u.meta_al + u.up_al, u.small_out};
+    return d;
+}
 // The way down of a ragged packed call, after its kernel is enqueued: one synchronisation before the rows travel. With small
 // slots they come down with the counts and are packed here; else k_ragged_cells / k_rows_scan give the offsets under that
-// synchronisation and k_pack_ragged sends the live cells alone. per_entry: a system has list_n results, the first at list_at
-// (levels, calcBound: the kernels' levels mode); else one, result b. verdicts: the u.nv arrays [nb] that follow the counts.
-inline int ragged_rows_down(xpg_ctx * ctx, int nb, const int32_t * cols, RaggedUp & u, bool per_entry, R32 * outs, long long outs_cap_cells,
+// synchronisation and k_pack_ragged sends the live cells alone. per_entry: a descriptor has list_n results, the first at list_at
+// (levels, calcBound: the kernels' levels mode); else one, result b. cols [n]: the width of each descriptor's results. verdicts:
+// the d.nv arrays [n] that follow the counts.
+inline int ragged_rows_down(xpg_ctx * ctx, int n, const int32_t * cols, const RaggedDown & d, bool per_entry, R32 * outs, long long outs_cap_cells,
                             const R32 ** view, long long * out_cell_offsets, int32_t * out_rows, int32_t * const * verdicts)
 {
-    const int nres = u.nres;
+    const int nres = d.nres;
     char * hp = hpack_buf(ctx, false);
     long long * h_off = (long long *)hp;
     int32_t * h_ints = (int32_t *)(hp + (size_t)(nres + 1) * 8);
-    XPG_TRY(hipMemcpyAsync(h_ints, u.dints.p, (size_t)(nres + u.nv * (size_t)nb) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(h_ints, d.dints->p, (size_t)(nres + d.nv * (size_t)n) * 4, hipMemcpyDeviceToHost, ctx->stream));
     const auto verdicts_out = [&]() {
         memcpy(out_rows, h_ints, (size_t)nres * 4);
-        for (int v = 0; v < u.nv; v++) memcpy(verdicts[v], h_ints + nres + (size_t)v * nb, (size_t)nb * 4);
+        for (int v = 0; v < d.nv; v++) memcpy(verdicts[v], h_ints + nres + (size_t)v * n, (size_t)n * 4);
     };
-    if (u.small_out) {
-        char * hs = hp + u.meta_al + u.up_al;
-        XPG_TRY(hipMemcpyAsync(hs, u.dout.p, u.bo, hipMemcpyDeviceToHost, ctx->stream));
+    if (d.small_out) {
+        char * hs = hp + d.slots_at;
+        XPG_TRY(hipMemcpyAsync(hs, d.dout->p, d.bo, hipMemcpyDeviceToHost, ctx->stream));
         XPG_TRY(hipStreamSynchronize(ctx->stream));
         verdicts_out();
         long long tot = 0;
-        for (int b = 0; b < nb; b++)
-            for (int k = 0, first = per_entry ? u.hd[b].list_at : b; k < (per_entry ? u.hd[b].list_n : 1); k++) {
+        for (int b = 0; b < n; b++)
+            for (int k = 0, first = per_entry ? d.hd[b].list_at : b; k < (per_entry ? d.hd[b].list_n : 1); k++) {
                 out_cell_offsets[first + k] = tot; tot += (long long)out_rows[first + k] * cols[b];
             }
         out_cell_offsets[nres] = tot;
         if (outs && outs_cap_cells < tot) return XPG_ERR_SHAPE;
-        for (int b = 0; b < nb; b++)                                 // forward moves: a destination never lies above its source
-            for (int k = 0, first = per_entry ? u.hd[b].list_at : b; k < (per_entry ? u.hd[b].list_n : 1); k++) {
-                const char * src = hs + ((size_t)u.hd[b].out_off + (size_t)k * u.cap_out * cols[b]) * 8;
+        for (int b = 0; b < n; b++)                                  // forward moves: a destination never lies above its source
+            for (int k = 0, first = per_entry ? d.hd[b].list_at : b; k < (per_entry ? d.hd[b].list_n : 1); k++) {
+                const char * src = hs + ((size_t)d.hd[b].out_off + (size_t)k * d.cap_out * cols[b]) * 8;
                 const size_t nbytes = (size_t)(out_cell_offsets[first + k + 1] - out_cell_offsets[first + k]) * 8;
                 if (outs) memcpy((char *)outs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
                 if (view) memmove(hs + (size_t)out_cell_offsets[first + k] * 8, src, nbytes);
@@ -658,11 +643,11 @@ inline int ragged_rows_down(xpg_ctx * ctx, int nb, const int32_t * cols, RaggedU
         if (view && tot > 0) *view = (const R32 *)hs;
         return 0;
     }
-    hipLaunchKernelGGL(k_ragged_cells, dim3((nb + 255) / 256 < 1024 ? (nb + 255) / 256 : 1024), dim3(256), 0, ctx->stream, nb, u.d_sys, per_entry ? 1 : 0,
-                       (const int *)u.dints.p, (int *)u.dcells.p);
-    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)u.dcells.p, (long long *)u.doff.p);
+    hipLaunchKernelGGL(k_ragged_cells, dim3((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), dim3(256), 0, ctx->stream, n, d.d_sys, per_entry ? 1 : 0,
+                       (const int *)d.dints->p, (int *)d.dcells->p);
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, ctx->stream, nres, (const int *)d.dcells->p, (long long *)d.doff->p);
     XPG_TRY(hipGetLastError());
-    XPG_TRY(hipMemcpyAsync(h_off, u.doff.p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XPG_TRY(hipMemcpyAsync(h_off, d.doff->p, (size_t)(nres + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     XPG_TRY(hipStreamSynchronize(ctx->stream));
     verdicts_out();
     memcpy(out_cell_offsets, h_off, (size_t)(nres + 1) * 8);
@@ -672,8 +657,8 @@ inline int ragged_rows_down(xpg_ctx * ctx, int nb, const int32_t * cols, RaggedU
     const size_t bp = (size_t)total * 8;
     DevBuf dpk;
     XPG_TRY(dpk.alloc(ctx, bp));
-    hipLaunchKernelGGL(k_pack_ragged, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, ctx->stream, nb, u.d_sys, per_entry ? 1 : 0, (const R32 *)u.dout.p,
-                       u.cap_out, (const int *)u.dcells.p, (const long long *)u.doff.p, (R32 *)dpk.p);
+    hipLaunchKernelGGL(k_pack_ragged, dim3(n < 4096 ? n : 4096), dim3(256), 0, ctx->stream, n, d.d_sys, per_entry ? 1 : 0, (const R32 *)d.dout->p,
+                       d.cap_out, (const int *)d.dcells->p, (const long long *)d.doff->p, (R32 *)dpk.p);
     XPG_TRY(hipGetLastError());
     if (view) {                                                      // into pinned memory; the caller's copy, if any, from there
         if (const int rc = hpack_reserve(ctx, bp)) return rc;
@@ -688,6 +673,27 @@ inline int ragged_rows_down(xpg_ctx * ctx, int nb, const int32_t * cols, RaggedU
     }
     return 0;
 }
+// THE launch of k_fme_chain_ragged<KEEP_LEVELS> and of k_calc_bound_ragged (enqueue only, no route record: the ragged packed
+// calls and the hull call both launch through them): the systems of `up` under plan p, the seats at `seats` (reserved by the
+// caller before anything of the call is enqueued), the results into up.dout, the counts and verdicts into up.dints in the order
+// the ways down read them -- ok, steps; ok, chain, steps.
+template <bool KEEP_LEVELS>
+inline int chain_ragged_enqueue(xpg_ctx * ctx, const LineqPlan & p, const RaggedUp & up, int darkshadow, void * seats)
+{
+    XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<KEEP_LEVELS>, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_fme_chain_ragged<KEEP_LEVELS>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, up.nb, up.d_sys, up.d_lists, up.d_mats,
+                       darkshadow, (R32 *)seats, p.cap, p.cols, (R32 *)up.dout.p, p.cap_out, up.d_rows(), up.d_verdict(0), up.d_verdict(1), p.cap_lds);
+    XPG_TRY(hipGetLastError());
+    return 0;
+}
+inline int calc_bound_ragged_enqueue(xpg_ctx * ctx, const LineqPlan & p, const RaggedUp & up, void * seats)
+{
+    XPG_TRY(lds_limit((const void *)k_calc_bound_ragged, ctx->device, p.q.lds));
+    hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, up.nb, up.d_sys, up.d_mats, (R32 *)seats, p.cap, p.cols,
+                       (R32 *)up.dout.p, p.cap_out, up.d_rows(), up.d_verdict(0), up.d_verdict(1), up.d_verdict(2), p.cap_lds);
+    XPG_TRY(hipGetLastError());
+    return 0;
+}
 // Host arrays with a PACKED result in CELLS (the rows differ in width; the convention of xpg_lineq_fme_batch_ragged_rat32):
 // out_cell_offsets [slots + 1] and out_rows [slots], slots = nb (projection: result b) or elim_offsets[nb] (levels: level k of
 // system b at elim_offsets[b] + k). ONE upload (ragged_up), ONE launch, and one synchronisation before the rows travel
@@ -700,10 +706,10 @@ inline int lineq_chain_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, co
                                      long long * out_cell_offsets, int32_t * out_rows, int32_t * out_ok, int32_t * out_steps)
 {
     if (view) *view = 0;
-    ragged_route() = RaggedRoute{0, 0, 0, 0, 0, 0, 0};
+    route_clear(ROUTE_RAGGED);
     if (nb < 0 || !out_cell_offsets) return XPG_ERR_SHAPE;
     if (nb == 0) { out_cell_offsets[0] = 0; return 0; }
-    RaggedChainPlan p;
+    LineqPlan p;
     if (const int rc = ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, levels, cap_rows, cap_out_rows, p)) return rc;
     if (!ctx || !mats || !offsets || !out_rows || !out_ok || !out_steps || (outs && outs_cap_cells < 0)) return XPG_ERR_SHAPE;
     for (int b = 0; b < nb; b++) if (offsets[b] < 0) return XPG_ERR_SHAPE;
@@ -711,21 +717,13 @@ inline int lineq_chain_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, co
     if (const int rc = scratch_reserve(ctx, seats, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_ragged seats)")) return rc;
     RaggedUp up;
     const auto list = [&](int b, int & at, int & n, int & per) { at = elim_offsets[b]; n = elim_offsets[b + 1] - at; per = levels ? n : 1; };
-    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, elim, elim_offsets[nb], list, (int)p.slots, 2, p.cap_out, p.out_bytes, up)) return rc;
-    int * d_rows = (int *)up.dints.p, * d_ok = d_rows + up.nres, * d_steps = d_ok + nb;
-    if (levels) {
-        XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<true>, ctx->device, p.q.lds));
-        hipLaunchKernelGGL(k_fme_chain_ragged<true>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_lists, up.d_mats, darkshadow,
-                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
-    } else {
-        XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<false>, ctx->device, p.q.lds));
-        hipLaunchKernelGGL(k_fme_chain_ragged<false>, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_lists, up.d_mats, darkshadow,
-                           (R32 *)seats.buf, p.cap, p.cols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
-    }
-    XPG_TRY(hipGetLastError());
-    ragged_route() = RaggedRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes};
-    int32_t * const verdicts[3] = {out_ok, out_steps, 0};
-    return ragged_rows_down(ctx, nb, cols, up, levels, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
+    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, elim, elim_offsets[nb], list, (int)p.slots, 2, p.cap_out, p.out_bytes,
+                                 ragged_meta((int)p.slots, nb, 2), up)) return rc;
+    if (const int rc = levels ? chain_ragged_enqueue<true>(ctx, p, up, darkshadow, seats.buf) : chain_ragged_enqueue<false>(ctx, p, up, darkshadow, seats.buf))
+        return rc;
+    route_write(ROUTE_RAGGED, p);
+    int32_t * const verdicts[2] = {out_ok, out_steps};
+    return ragged_rows_down(ctx, nb, cols, ragged_down(up), levels, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
 }
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for nb systems at once: for every variable j the
@@ -836,18 +834,18 @@ inline int lineq_calc_bound_batch(xpg_ctx * ctx, int nb, const R32 * mats, int r
 
 // ---- calcBound fused: every chain of every system in ONE launch (k_calc_bound_batch) -----------------------------------------
 // Device arrays, enqueue only: d_outs [nb][rhs][cap_out_rows][cols] receives the live rows of variable j's bounds in slot
-// (b, j), d_rows [nb][rhs] their counts, d_ok / d_chain / d_steps [nb] as the kernel writes them. As lineq_project_batch_dev:
-// the seats' slots are the handle's (grow-only, a slot of their own), the row stride of d_outs is the caller's -- cap_rows <
+// (b, j), d_rows [nb][rhs] their counts, d_ok / d_chain / d_steps [nb] as the kernel writes them. As lineq_chain_batch_dev:
+// the seats' slots are the handle's (grow-only, an area of their own), the row stride of d_outs is the caller's -- cap_rows <
 // rows or cap_out_rows > cap_rows is XPG_ERR_SHAPE, only cap_out_rows <= 0 stands for cap_rows.
 inline int lineq_bounds_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int rows, int cols, int rhs, int cap_rows, int cap_out_rows,
                                   R32 * d_outs, int32_t * d_rows, int32_t * d_ok, int32_t * d_chain, int32_t * d_steps)
 {
-    bounds_route() = BoundsRoute{0, 0, 0, 0, 0, 0, 0};
+    route_clear(ROUTE_BOUNDS);
     if (!ctx || nb < 0 || !d_mats || !d_outs || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols || !d_rows || !d_ok || !d_chain || !d_steps)
         return XPG_ERR_SHAPE;
     if (cap_rows < rows || cap_out_rows > cap_rows) return XPG_ERR_SHAPE;
     if (nb == 0) return 0;
-    BoundsPlan p;
+    LineqPlan p;
     if (const int rc = bounds_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, p)) return rc;
     Scratch & slots = ctx->scratch[SCRATCH_LINEQ_BOUNDS];
     if (const int rc = scratch_reserve(ctx, slots, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_bounds seats)")) return rc;
@@ -855,101 +853,59 @@ inline int lineq_bounds_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_mats, int
     hipLaunchKernelGGL(k_calc_bound_batch, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, d_mats, rows, cols, rhs, (R32 *)slots.buf,
                        p.cap, d_outs, p.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_chain, (int *)d_steps, p.cap_lds, p.q.sys_lds);
     XPG_TRY(hipGetLastError());
-    bounds_route() = BoundsRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, p.steps};
+    route_write(ROUTE_BOUNDS, p);
     return 0;
 }
 // Host arrays with a PACKED result in the layout of the packed calcBound: row_offsets [nb * rhs + 1], entry b * rhs + j where
-// the bounds of variable j of system b start. One upload, the one launch, packed_rows_down over the nb * rhs results; the
-// verdicts (ok, chain, steps: [nb] each) come down through hred beside it, under the same synchronisation. A system with
-// out_ok <= 0 contributes no rows, the others are packed all the same; out / view / sizing call as lineq_project_batch_packed.
+// the bounds of variable j of system b start. One upload (packed_up), the one launch, packed_rows_down over the nb * rhs results
+// and the three verdict arrays [nb]. A system with out_ok <= 0 contributes no rows, the others are packed all the same; out /
+// view / sizing call as lineq_chain_batch_packed.
 inline int lineq_bounds_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int rhs, int cap_rows, int cap_out_rows,
                                      R32 * out, long long out_cap_rows, const R32 ** view, long long * row_offsets, int32_t * out_ok,
                                      int32_t * out_chain, int32_t * out_steps)
 {
     if (view) *view = 0;
-    bounds_route() = BoundsRoute{0, 0, 0, 0, 0, 0, 0};
+    route_clear(ROUTE_BOUNDS);
     if (!ctx || nb < 0 || !mats || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols || !row_offsets || !out_ok || !out_chain || !out_steps ||
         (out && out_cap_rows < 0))
         return XPG_ERR_SHAPE;
     if (nb == 0) { row_offsets[0] = 0; return 0; }
-    BoundsPlan p;
+    LineqPlan p;
     if (const int rc = bounds_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, p)) return rc;
-    if ((long long)nb * rhs > INT_MAX) return XPG_ERR_UNSUPPORTED;
-    const int nres = nb * rhs;
-    const size_t bi = (size_t)nb * rows * cols * 8, bo = (size_t)nres * p.cap_out * cols * 8, bv = (size_t)nb * 4;
-    const size_t meta = (size_t)(nres + 1) * 8 + (size_t)nres * 12;  // offsets, then (unused) ok, rows and (unused) steps
-    const size_t meta_al = (meta + 255) & ~(size_t)255;
-    DevBuf di, dout, dr, dv, doff;                                   // dv: ok, chain and steps, [3][nb]
-    XPG_TRY(di.alloc(ctx, bi)); XPG_TRY(dout.alloc(ctx, bo)); XPG_TRY(dr.alloc(ctx, (size_t)nres * 4)); XPG_TRY(dv.alloc(ctx, 3 * bv));
-    XPG_TRY(doff.alloc(ctx, (size_t)(nres + 1) * 8));
-    const bool small_in = bi <= ((size_t)4 << 20), small_out = bo <= ((size_t)512 << 10);
-    int rc = hpack_reserve(ctx, meta_al + (small_in ? bi : 0) + (small_out ? bo : 0));
-    if (rc) return rc;
-    if ((rc = hpack_reserve(ctx, 3 * bv, true))) return rc;
-    char * hp = hpack_buf(ctx, false);
-    int32_t * hv = (int32_t *)hpack_buf(ctx, true);
-    if (small_in) {
-        memcpy(hp + meta_al, mats, bi);
-        XPG_TRY(hipMemcpyAsync(di.p, hp + meta_al, bi, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        XPG_TRY(hipMemcpyAsync(di.p, mats, bi, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int32_t * const d_ok = (int32_t *)dv.p;
-    rc = lineq_bounds_batch_dev(ctx, nb, (const R32 *)di.p, rows, cols, rhs, p.cap, p.cap_out, (R32 *)dout.p, (int32_t *)dr.p, d_ok, d_ok + nb,
-                                d_ok + 2 * (size_t)nb);
-    if (rc) return rc;
-    XPG_TRY(hipMemcpyAsync(hv, dv.p, 3 * bv, hipMemcpyDeviceToHost, ctx->stream));
-    rc = packed_rows_down(ctx, nres, cols, p.cap_out, dout, dr, dv, (DevBuf *)0, doff, meta_al, small_in ? bi : 0, small_out, false, (const char *)0,
-                          out, out_cap_rows, view, row_offsets, (int32_t *)0, (int32_t *)0, [](const char *) {});
-    if (rc == 0 || rc == XPG_ERR_SHAPE) {                            // (it has synchronised: a buffer too small still gets its verdicts)
-        memcpy(out_ok, hv, bv); memcpy(out_chain, hv + nb, bv); memcpy(out_steps, hv + 2 * (size_t)nb, bv);
-    }
-    return rc;
+    if (p.slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    PackedUp u;
+    if (const int rc = packed_up(ctx, nb, mats, rows, cols, (int)p.slots, 3, p.out_bytes, false, false, u)) return rc;
+    if (const int rc = lineq_bounds_batch_dev(ctx, nb, (const R32 *)u.di.p, rows, cols, rhs, p.cap, p.cap_out, (R32 *)u.dout.p, u.d_rows(),
+                                              u.d_verdict(0), u.d_verdict(1), u.d_verdict(2))) return rc;
+    int32_t * const verdicts[3] = {out_ok, out_chain, out_steps};
+    return packed_rows_down(ctx, u, cols, p.cap_out, (const char *)0, out, out_cap_rows, view, row_offsets, verdicts, no_lap);
 }
 
 // ---- calcBound fused for systems of MIXED shapes: one launch of k_calc_bound_ragged -------------------------------------------
-// THE plan of a ragged calcBound call (the launch and xpg_test_lineq_bounds_ragged_plan both ask it), decided before anything
-// is launched: every system under bounds_plan's shape rules, then the ENVELOPE -- the widest system's cols, the most rows --
-// under bounds_plan's capacity rules (cap_rows <= 0: 4 * most rows + 16; three slots per seat), so that a batch whose shapes
-// all agree gets exactly the uniform plan. The output slots follow the systems, cap_out x OWN cols cells per variable; `steps`
-// is the sum over the systems. rhs_idx NULL: the last column of each system.
-struct BoundsRaggedPlan { int cols, rows, cap, cap_out, cap_lds; LineqGeom q; long long seats, slots, steps; size_t seat_bytes, out_bytes; };
+// The plan of a ragged calcBound call, decided before anything is launched: every system under bounds_plan's shape rules, then
+// the ENVELOPE -- the widest system's cols, the most rows -- under bounds_plan's rule, so that a batch whose shapes all agree
+// gets exactly the uniform plan. The output slots follow the systems, cap_out x OWN cols cells per variable; `steps` is the sum
+// over the systems. rhs_idx NULL: the last column of each system.
 inline int bounds_ragged_plan(int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx, int cap_rows, int cap_out_rows,
-                              BoundsRaggedPlan & p)
+                              LineqPlan & p)
 {
     if (nb <= 0 || !rows || !cols) return XPG_ERR_SHAPE;
-    long long cells = 0;
-    p.cols = 0; p.rows = 0; p.slots = 0; p.steps = 0;
+    long long cells = 0, slots = 0, steps = 0;
+    int erows = 0, ecols = 0;
     for (int b = 0; b < nb; b++) {
         const int rhs = rhs_idx ? rhs_idx[b] : cols[b] - 1;
         if (rows[b] <= 0 || cols[b] <= 1 || rhs < 1 || rhs >= cols[b]) return XPG_ERR_SHAPE;
-        if (cols[b] > p.cols) p.cols = cols[b];
-        if (rows[b] > p.rows) p.rows = rows[b];
+        if (cols[b] > ecols) ecols = cols[b];
+        if (rows[b] > erows) erows = rows[b];
         cells += (long long)rhs * cols[b];
-        p.slots += rhs;
-        p.steps += (long long)(rhs - 1) * (rhs + 2) / 2;
+        slots += rhs;
+        steps += (long long)(rhs - 1) * (rhs + 2) / 2;
     }
-    if (p.rows > 32767) return XPG_ERR_UNSUPPORTED;                            // (cap >= rows: refused below in any case)
-    p.cap = cap_rows <= 0 ? 4 * p.rows + 16 : cap_rows;
-    if (p.cap < p.rows) p.cap = p.rows;
-    p.cap_out = cap_out_rows <= 0 || cap_out_rows > p.cap ? p.cap : cap_out_rows;
-    if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
-    const FmeLds fl = fme_lds(p.cap, p.cap, p.cols);
-    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
-    if (p.slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
-    p.cap_lds = fl.cap_lds;
-    p.q = lineq_geom(nb, 64, fl.lds);
-    if (p.q.G != 1) return XPG_ERR_UNSUPPORTED;                                // (the kernel's seat is the workgroup: fme's whole wave)
-    p.seats = (long long)p.q.grid * p.q.G;
-    p.seat_bytes = (size_t)p.seats * 3 * (size_t)p.cap * p.cols * 8;
-    p.out_bytes = (size_t)cells * (size_t)p.cap_out * 8;
+    if (slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    if (const int rc = lineq_plan_rule(nb, erows, ecols, cap_rows, cap_out_rows, kind_bounds(true), p)) return rc;
+    plan_slots(p, slots, cells, steps);
     return 0;
 }
-// What the calling thread's last xpg_lineq_bounds_batch_ragged_rat32 call did (xpg_lineq_bounds_ragged_last_route): launches
-// of k_calc_bound_ragged (1), its grid, systems per workgroup, LDS bytes per system, cap_lds, bytes of seat slots, bytes of
-// output slots, elimination steps of the whole batch.
-struct BoundsRaggedRoute { long long launches, grid, groups, sys_lds, cap_lds, seat_bytes, out_bytes, steps; };
-inline BoundsRaggedRoute & bounds_ragged_route() { static thread_local BoundsRaggedRoute r = {0, 0, 0, 0, 0, 0, 0, 0}; return r; }
 // Host arrays with a PACKED result in CELLS, as lineq_chain_ragged_packed gives them: out_cell_offsets [R + 1] and out_rows [R],
 // R the sum of the rhs, variable j of system b at first[b] + j (first[b] the sum of the rhs before b). ONE upload (ragged_up:
 // descriptors and systems, no list -- the descriptor's list_at / list_n carry first[b] / rhs), ONE launch, one synchronisation
@@ -962,10 +918,10 @@ inline int lineq_bounds_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, c
                                       int32_t * out_chain, int32_t * out_steps)
 {
     if (view) *view = 0;
-    bounds_ragged_route() = BoundsRaggedRoute{0, 0, 0, 0, 0, 0, 0, 0};
+    route_clear(ROUTE_BOUNDS_RAGGED);
     if (nb < 0 || !out_cell_offsets) return XPG_ERR_SHAPE;
     if (nb == 0) { out_cell_offsets[0] = 0; return 0; }
-    BoundsRaggedPlan p;
+    LineqPlan p;
     if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p)) return rc;
     if (!ctx || !mats || !offsets || !out_rows || !out_ok || !out_chain || !out_steps || (outs && outs_cap_cells < 0)) return XPG_ERR_SHAPE;
     for (int b = 0; b < nb; b++) if (offsets[b] < 0) return XPG_ERR_SHAPE;
@@ -974,15 +930,12 @@ inline int lineq_bounds_ragged_packed(xpg_ctx * ctx, int nb, const R32 * mats, c
     RaggedUp up;
     int first = 0;                                                   // (asked once per system, in order)
     const auto list = [&](int b, int & at, int & n, int & per) { at = first; n = per = rhs_idx ? rhs_idx[b] : cols[b] - 1; first += n; };
-    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, (const int32_t *)0, 0, list, (int)p.slots, 3, p.cap_out, p.out_bytes, up)) return rc;
-    int * d_rows = (int *)up.dints.p, * d_ok = d_rows + up.nres, * d_chain = d_ok + nb, * d_steps = d_chain + nb;
-    XPG_TRY(lds_limit((const void *)k_calc_bound_ragged, ctx->device, p.q.lds));
-    hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.q.grid), p.q.block, p.q.lds, ctx->stream, nb, up.d_sys, up.d_mats, (R32 *)seats.buf, p.cap, p.cols,
-                       (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_chain, d_steps, p.cap_lds);
-    XPG_TRY(hipGetLastError());
-    bounds_ragged_route() = BoundsRaggedRoute{1, p.q.grid, p.q.G, p.q.sys_lds, p.cap_lds, (long long)p.seat_bytes, (long long)p.out_bytes, p.steps};
+    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, (const int32_t *)0, 0, list, (int)p.slots, 3, p.cap_out, p.out_bytes,
+                                 ragged_meta((int)p.slots, nb, 3), up)) return rc;
+    if (const int rc = calc_bound_ragged_enqueue(ctx, p, up, seats.buf)) return rc;
+    route_write(ROUTE_BOUNDS_RAGGED, p);
     int32_t * const verdicts[3] = {out_ok, out_chain, out_steps};
-    return ragged_rows_down(ctx, nb, cols, up, true, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
+    return ragged_rows_down(ctx, nb, cols, ragged_down(up), true, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
 }
 
 // Matrix<Rational>::rank on device arrays, enqueue only: d_rank [nb].

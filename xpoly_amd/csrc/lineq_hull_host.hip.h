@@ -21,8 +21,8 @@ namespace xpg {
 //              row: the result of a group goes to the front of its own region and never has more rows than lead + the live rows
 //              of its slots, so nothing grows with groups x cap_hull.
 struct HullPlan {
-    int cap, cap_out, cap_lds, cap_hull, ecols, lds_rows, grid, prod_grid; size_t lds, prod_lds, seat_bytes, slot_bytes, out_bytes;
-    long long n_lds, n_dev, slots;
+    LineqPlan prod;                                                   // the producer's plan (all zero: no members, nothing is launched)
+    int cap_hull, lds_rows, grid; size_t lds, slot_bytes, out_bytes; long long n_lds, n_dev;
 };
 enum { HULL_HOME_NONE = -1, HULL_HOME_LDS = 0, HULL_HOME_DEVICE = 1 };
 inline int hull_plan(int ng, const int32_t * goff, int nb, const int32_t * rows, const int32_t * cols, const int32_t * rhs_idx,
@@ -34,17 +34,9 @@ inline int hull_plan(int ng, const int32_t * goff, int nb, const int32_t * rows,
     for (int g = 0; g < ng; g++) if (goff[g + 1] < goff[g]) return XPG_ERR_SHAPE;
     p = HullPlan();
     if (nb > 0) {
-        if (is_union) {
-            RaggedChainPlan c;
-            if (const int rc = ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, false, cap_rows, cap_out_rows, c)) return rc;
-            p.cap = c.cap; p.cap_out = c.cap_out; p.cap_lds = c.cap_lds; p.ecols = c.cols; p.prod_grid = c.q.grid; p.prod_lds = c.q.lds;
-            p.seat_bytes = c.seat_bytes; p.out_bytes = c.out_bytes; p.slots = c.slots;
-        } else {
-            BoundsRaggedPlan c;
-            if (const int rc = bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, c)) return rc;
-            p.cap = c.cap; p.cap_out = c.cap_out; p.cap_lds = c.cap_lds; p.ecols = c.cols; p.prod_grid = c.q.grid; p.prod_lds = c.q.lds;
-            p.seat_bytes = c.seat_bytes; p.out_bytes = c.out_bytes; p.slots = c.slots;
-        }
+        if (const int rc = is_union ? ragged_chain_plan(nb, rows, cols, rhs_idx, elim, elim_offsets, false, cap_rows, cap_out_rows, p.prod)
+                                    : bounds_ragged_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p.prod)) return rc;
+        p.out_bytes = p.prod.out_bytes;
     }
     const int lead = is_union ? 0 : 1;
     long long want = 1;
@@ -56,8 +48,8 @@ inline int hull_plan(int ng, const int32_t * goff, int nb, const int32_t * rows,
             if (cols[b] != cols[b0] || (rhs_idx ? rhs_idx[b] : cols[b] - 1) != rhs) return XPG_ERR_SHAPE;
         const long long w = lead + 2ll * rhs * n;
         if (w > want) want = w;
-        if ((long long)n * (is_union ? 1 : rhs) * p.cap_out + p.cap_out > INT_MAX) return XPG_ERR_UNSUPPORTED;   // (a region's rows are ints)
-        p.out_bytes += (size_t)lead * p.cap_out * cols[b0] * 8;
+        if ((long long)n * (is_union ? 1 : rhs) * p.prod.cap_out + p.prod.cap_out > INT_MAX) return XPG_ERR_UNSUPPORTED;   // (a region's rows are ints)
+        p.out_bytes += (size_t)lead * p.prod.cap_out * cols[b0] * 8;
     }
     if (cap_hull_rows > 32767) return XPG_ERR_UNSUPPORTED;
     p.cap_hull = cap_hull_rows > 0 ? cap_hull_rows : (int)(want < 32767 ? want : 32767);
@@ -65,23 +57,23 @@ inline int hull_plan(int ng, const int32_t * goff, int nb, const int32_t * rows,
         for (int g = 0; g < ng; g++) { if (homes) homes[g] = HULL_HOME_NONE; if (gcaps) gcaps[g] = 0; }
         return 0;
     }
-    const int fit = 32 * 1024 / (p.ecols * 8) > 0 ? 32 * 1024 / (p.ecols * 8) : 1;
+    const int fit = 32 * 1024 / (p.prod.cols * 8) > 0 ? 32 * 1024 / (p.prod.cols * 8) : 1;
     p.lds_rows = p.cap_hull < fit ? p.cap_hull : fit;
-    p.lds = (size_t)p.lds_rows * p.ecols * 8 + (lineq_lds_bytes(p.cap_hull, 1) - (size_t)p.cap_hull * 8) + 16;
+    p.lds = (size_t)p.lds_rows * p.prod.cols * 8 + (lineq_lds_bytes(p.cap_hull, 1) - (size_t)p.cap_hull * 8) + 16;
     p.lds = (p.lds + 15) & ~(size_t)15;
     if (p.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
     for (int g = 0; g < ng; g++) {
         const int b0 = goff[g], n = goff[g + 1] - b0;
         if (n == 0) { if (homes) homes[g] = HULL_HOME_NONE; if (gcaps) gcaps[g] = 0; continue; }
-        const long long room = lead + (long long)n * (is_union ? 1 : (rhs_idx ? rhs_idx[b0] : cols[b0] - 1)) * p.cap_out;
+        const long long room = lead + (long long)n * (is_union ? 1 : (rhs_idx ? rhs_idx[b0] : cols[b0] - 1)) * p.prod.cap_out;
         const long long gcap = room < p.cap_hull ? room : p.cap_hull;
-        const bool in_lds = gcap * cols[b0] <= (long long)p.lds_rows * p.ecols;
+        const bool in_lds = gcap * cols[b0] <= (long long)p.lds_rows * p.prod.cols;
         if (in_lds) p.n_lds++; else p.n_dev++;
         if (homes) homes[g] = in_lds ? HULL_HOME_LDS : HULL_HOME_DEVICE;
         if (gcaps) gcaps[g] = (int32_t)gcap;
     }
     p.grid = lineq_grid(ng);
-    const size_t one = (size_t)p.cap_hull * p.ecols * 8;
+    const size_t one = (size_t)p.cap_hull * p.prod.cols * 8;
     if (p.n_dev) {
         const size_t most = ((size_t)1 << 30) / one;
         if ((size_t)p.grid > most) p.grid = most > 0 ? (int)most : 1;
@@ -89,11 +81,25 @@ inline int hull_plan(int ng, const int32_t * goff, int nb, const int32_t * rows,
     }
     return 0;
 }
-// What the calling thread's last hull call did (xpg_lineq_hull_last_route): launches of the producer (1) and of k_group_reduce
-// (1), the latter's grid and LDS bytes per workgroup, the groups whose home is LDS and a device slot, bytes of the producer's
-// seats, of the workgroups' device slots and of the output slots, the rows gathered over all groups.
-struct HullRoute { long long prod_launches, launches, grid, lds, n_lds, n_dev, seat_bytes, slot_bytes, out_bytes, gathered; };
-inline HullRoute & hull_route() { static thread_local HullRoute r = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; return r; }
+// The figures of a hull plan (the HULL row of the table beside LineqRoute, lineq_host.hip.h): the route's ten -- the last,
+// the rows gathered over all groups, is no plan figure: 0 here, counted by the call once the verdicts are down -- then what the
+// plan view adds. The launch (route_write) and xpg_test_lineq_hull_plan (hull_plan_out) both call it.
+enum { HULL_GATHERED = 9, HULL_FIGURES = 15 };
+inline void hull_figures(const HullPlan & p, long long * f)
+{
+    const long long g[HULL_FIGURES] = { p.prod.launches, p.prod.launches, p.grid, (long long)p.lds, p.n_lds, p.n_dev, (long long)p.prod.seat_bytes,
+                                        (long long)p.slot_bytes, (long long)p.out_bytes, 0, p.prod.cap, p.prod.cap_out, p.cap_hull, p.lds_rows,
+                                        p.prod.cols };
+    for (int k = 0; k < HULL_FIGURES; k++) f[k] = g[k];
+}
+inline int hull_plan_out(int rc, const HullPlan & p, long long * out, int n)   // (rc: hull_plan's answer for p; the view has no `gathered`)
+{
+    if (rc) return rc;
+    long long f[HULL_FIGURES];
+    hull_figures(p, f);
+    figures_out(out, n, f, HULL_GATHERED);
+    return n > HULL_GATHERED ? figures_out(out + HULL_GATHERED, n - HULL_GATHERED, f + HULL_GATHERED + 1, HULL_FIGURES - HULL_GATHERED - 1) : 0;
+}
 
 // Host arrays in, a PACKED result in CELLS out, one entry per GROUP: out_cell_offsets [ng + 1], out_rows [ng] and the verdicts
 // [ng] as k_group_reduce writes them. ONE upload (ragged_up: the members' descriptors, the lists of a projected union with the
@@ -107,7 +113,7 @@ inline int lineq_hull_ragged_packed(xpg_ctx * ctx, int ng, const int32_t * goff,
 {
     const bool is_union = elim_offsets != 0;
     if (view) *view = 0;
-    hull_route() = HullRoute{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    route_clear(ROUTE_HULL);
     if (ng < 0 || nb < 0 || !out_cell_offsets) return XPG_ERR_SHAPE;
     if (ng == 0) { if (nb != 0) return XPG_ERR_SHAPE; out_cell_offsets[0] = 0; return 0; }
     HullPlan p;
@@ -133,7 +139,7 @@ inline int lineq_hull_ragged_packed(xpg_ctx * ctx, int ng, const int32_t * goff,
             gd[(size_t)g] = RaggedSys{b0, out_at, n, gc, rhs, first, each, lead};
             gcols[(size_t)g] = gc;
             for (int b = b0; b < b0 + n; b++) per[(size_t)b] = each + (lead && b == b0 + n - 1 ? 1 : 0);
-            out_at += ((long long)n * each + (n ? lead : 0)) * p.cap_out * gc;
+            out_at += ((long long)n * each + (n ? lead : 0)) * p.prod.cap_out * gc;
             first += n * each;
         }
     }
@@ -143,53 +149,43 @@ inline int lineq_hull_ragged_packed(xpg_ctx * ctx, int ng, const int32_t * goff,
     if (n_elim) memcpy(lists.data(), elim, (size_t)n_elim * 4);
     memcpy(lists.data() + desc_at, gd.data(), (size_t)ng * sizeof(RaggedSys));
     Scratch & seats = ctx->scratch[is_union ? SCRATCH_LINEQ_PROJECT : SCRATCH_LINEQ_BOUNDS];
-    if (const int rc = scratch_reserve(ctx, seats, p.seat_bytes, p.seat_bytes, "hipMalloc(lineq_hull seats)")) return rc;
+    if (const int rc = scratch_reserve(ctx, seats, p.prod.seat_bytes, p.prod.seat_bytes, "hipMalloc(lineq_hull seats)")) return rc;
     // everything the two launches need is allocated before the first, so that nothing stands between them
-    RaggedUp up, gu;
-    DevBuf dslot;
+    RaggedUp up;
+    DevBuf dslot, gints, gcells, goffs;                              // the workgroups' device slots; the groups' ints and scan scratch
     if (p.slot_bytes) XPG_TRY(dslot.alloc(ctx, p.slot_bytes));
-    XPG_TRY(gu.dints.alloc(ctx, (size_t)ng * 6 * 4)); XPG_TRY(gu.dcells.alloc(ctx, (size_t)ng * 4)); XPG_TRY(gu.doff.alloc(ctx, (size_t)(ng + 1) * 8));
+    XPG_TRY(gints.alloc(ctx, (size_t)ng * 6 * 4)); XPG_TRY(gcells.alloc(ctx, (size_t)ng * 4)); XPG_TRY(goffs.alloc(ctx, (size_t)(ng + 1) * 8));
     int first = 0;                                                   // (asked once per member, in order)
     const auto list = [&](int b, int & at, int & n, int & pr) {
         if (is_union) { at = elim_offsets[b]; n = elim_offsets[b + 1] - at; }
         else { at = first; n = rhs_idx ? rhs_idx[b] : cols[b] - 1; first += n; }
         pr = per[(size_t)b];
     };
-    // (the counts of 3 ng + 1 results keep the block's head large enough for the groups' offsets, counts and verdicts)
-    const int nres = p.slots > 3ll * ng + 1 ? (int)p.slots : 3 * ng + 1;
-    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, lists.data(), (int)lists.size(), list, nres, is_union ? 2 : 3, p.cap_out,
-                                 p.out_bytes, up)) return rc;
-    int * const d_rows = (int *)up.dints.p, * const d_ok = d_rows + up.nres;
-    int * d_chain = 0, * d_steps = 0;
-    if (is_union) {
-        d_steps = d_ok + nb;
-        XPG_TRY(lds_limit((const void *)k_fme_chain_ragged<false>, ctx->device, p.prod_lds));
-        hipLaunchKernelGGL(k_fme_chain_ragged<false>, dim3(p.prod_grid), dim3(64, 1), p.prod_lds, ctx->stream, nb, up.d_sys, up.d_lists, up.d_mats, darkshadow,
-                           (R32 *)seats.buf, p.cap, p.ecols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_steps, p.cap_lds);
-    } else {
-        d_chain = d_ok + nb; d_steps = d_chain + nb;
-        XPG_TRY(lds_limit((const void *)k_calc_bound_ragged, ctx->device, p.prod_lds));
-        hipLaunchKernelGGL(k_calc_bound_ragged, dim3(p.prod_grid), dim3(64, 1), p.prod_lds, ctx->stream, nb, up.d_sys, up.d_mats, (R32 *)seats.buf, p.cap,
-                           p.ecols, (R32 *)up.dout.p, p.cap_out, d_rows, d_ok, d_chain, d_steps, p.cap_lds);
-    }
-    XPG_TRY(hipGetLastError());
+    // (what comes down first is the GROUPS': their offsets, counts and five verdict arrays; the members' ints stay on the device)
+    if (const int rc = ragged_up(ctx, nb, mats, rows, cols, offsets, rhs_idx, lists.data(), (int)lists.size(), list, (int)p.prod.slots, is_union ? 2 : 3,
+                                 p.prod.cap_out, p.out_bytes, ragged_meta(ng, ng, 5), up)) return rc;
+    if (const int rc = is_union ? chain_ragged_enqueue<false>(ctx, p.prod, up, darkshadow, seats.buf) : calc_bound_ragged_enqueue(ctx, p.prod, up, seats.buf))
+        return rc;
+    // the members' verdicts as k_group_reduce reads them: ok, then (hull) chain and steps, or (projected union) steps alone
+    const int * const d_chain = is_union ? (const int *)0 : up.d_verdict(1), * const d_steps = up.d_verdict(is_union ? 1 : 2);
     const RaggedSys * const d_grp = (const RaggedSys *)(up.d_lists + desc_at);
-    int * const g_rows = (int *)gu.dints.p;
+    int * const g_rows = (int *)gints.p;
     XPG_TRY(lds_limit((const void *)k_group_reduce, ctx->device, p.lds));
-    hipLaunchKernelGGL(k_group_reduce, dim3(p.grid), dim3(64, 1), p.lds, ctx->stream, ng, d_grp, (R32 *)up.dout.p, p.cap_out, (const int *)d_rows,
-                       (const int *)d_ok, (const int *)d_chain, (const int *)d_steps, is_intersect, p.cap_hull, p.ecols, p.lds_rows * p.ecols,
+    hipLaunchKernelGGL(k_group_reduce, dim3(p.grid), dim3(64, 1), p.lds, ctx->stream, ng, d_grp, (R32 *)up.dout.p, p.prod.cap_out, (const int *)up.d_rows(),
+                       (const int *)up.d_verdict(0), d_chain, d_steps, is_intersect, p.cap_hull, p.prod.cols, p.lds_rows * p.prod.cols,
                        (R32 *)dslot.p, g_rows, g_rows + ng, g_rows + 2 * (size_t)ng, g_rows + 3 * (size_t)ng, g_rows + 4 * (size_t)ng,
                        g_rows + 5 * (size_t)ng);
     XPG_TRY(hipGetLastError());
-    hull_route() = HullRoute{1, 1, p.grid, (long long)p.lds, p.n_lds, p.n_dev, (long long)p.seat_bytes, (long long)p.slot_bytes, (long long)p.out_bytes, 0};
-    // the way down is the ragged calls', over the GROUPS: the members' slots become the groups' regions
-    gu.dout.p = up.dout.p; gu.dout.cap = up.dout.cap; gu.dout.owner = up.dout.owner; up.dout.p = 0;
-    gu.nres = ng; gu.nv = 5; gu.cap_out = p.cap_out; gu.up_al = up.up_al; gu.meta_al = up.meta_al; gu.bo = up.bo; gu.small_out = up.small_out;
-    gu.hd = gd.data(); gu.d_sys = d_grp;
+    long long f[HULL_FIGURES];
+    hull_figures(p, f);
+    route_write(ROUTE_HULL, f);
+    // the way down is the ragged calls', over the GROUPS: the members' slots are the groups' regions
+    RaggedDown down = ragged_down(up);
+    down.hd = gd.data(); down.d_sys = d_grp; down.dints = &gints; down.dcells = &gcells; down.doff = &goffs; down.nres = ng; down.nv = 5;
     std::vector<int32_t> gath((size_t)ng, 0);
     int32_t * const verdicts[5] = {out_ok, out_member, out_chain, out_steps, gath.data()};
-    const int rc = ragged_rows_down(ctx, ng, gcols.data(), gu, false, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
-    if (rc == 0 || rc == XPG_ERR_SHAPE) for (int g = 0; g < ng; g++) hull_route().gathered += gath[(size_t)g];
+    const int rc = ragged_rows_down(ctx, ng, gcols.data(), down, false, outs, outs_cap_cells, view, out_cell_offsets, out_rows, verdicts);
+    if (rc == 0 || rc == XPG_ERR_SHAPE) for (int g = 0; g < ng; g++) lineq_route(ROUTE_HULL).f[HULL_GATHERED] += gath[(size_t)g];
     return rc;
 }
 
