@@ -10,13 +10,15 @@
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
 // should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
-// levels_all, project_each, levels_nests, calc_bound_all, calc_bound_each, hull_all, project_union_each -- take the caller's matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
+// levels_all, project_each, levels_nests, calc_bound_all, calc_bound_each, hull_all, project_union_each -- take the caller's
+// matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
 #define XPOLY_AMD_LINEQ_HPP
 
 #include <cstddef>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -26,6 +28,157 @@
 namespace xpoly_amd {
 
 namespace detail {
+// ---- what every collector below is made of, stated once (tests/cxx/collectors_trace.cpp pins what they do)
+inline xpg_ctx * ctx_or_shared(xpg_ctx * c) { return c ? c : shared_context(); }
+
+template <class RMatT> inline void put_cells(RMatT & m, const xpg_rat32 * a, int rows, int cols)
+{
+    m.reinit((unsigned)rows, (unsigned)cols);
+    if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a, sizeof(xpg_rat32) * (size_t)rows * cols);
+}
+
+// One packed view of a list of matrices: rows, cols and cell offsets of each, their cells back to back in list order, the
+// largest row count. at(i) is matrix i (a pointer), shape_of(m) the rows and columns it travels with: the rule for what counts
+// as having none is the caller's. A class of equal shapes is the same pack -- [n][rows][cols], what the _packed_ entry points
+// take -- under the rule that knows its shape and does not ask each member again.
+struct packed {
+    std::vector<int32_t> rows, cols;
+    std::vector<long long> off;
+    std::vector<xpg_rat32> flat;                                    // (never without a cell: data() is no null pointer)
+    int most;
+    long long cells() const { return off.back(); }
+};
+struct shape_as_is { template <class M> std::pair<int, int> operator()(const M * m) const { return std::make_pair((int)m->get_row_size(), (int)m->get_col_size()); } };
+struct shape_known { int rows, cols; template <class M> std::pair<int, int> operator()(const M *) const { return std::make_pair(rows, cols); } };
+template <class At, class Shape> inline packed pack(int n, At at, Shape shape_of)
+{
+    packed p;
+    p.rows.resize((size_t)n); p.cols.resize((size_t)n); p.off.assign((size_t)n + 1, 0); p.most = 0;
+    for (int i = 0; i < n; i++) {
+        const std::pair<int, int> shape = shape_of(at(i));
+        p.rows[(size_t)i] = (int32_t)shape.first; p.cols[(size_t)i] = (int32_t)shape.second;
+        p.off[(size_t)i + 1] = p.off[(size_t)i] + (long long)p.rows[(size_t)i] * p.cols[(size_t)i];
+        if (p.rows[(size_t)i] > p.most) p.most = p.rows[(size_t)i];
+    }
+    p.flat.resize((size_t)(p.cells() ? p.cells() : 1));
+    for (int i = 0; i < n; i++)
+        if (p.off[(size_t)i + 1] > p.off[(size_t)i])
+            std::memcpy((void *)(p.flat.data() + p.off[(size_t)i]), (const void *)at(i)->get_matrix(),
+                        sizeof(xpg_rat32) * (size_t)(p.off[(size_t)i + 1] - p.off[(size_t)i]));
+    return p;
+}
+template <class RMatT, class Shape> inline packed pack(const std::vector<RMatT *> & systems, const std::vector<int> & which, Shape shape_of)
+{ return pack((int)which.size(), [&](int i) { return (const RMatT *)systems[(size_t)which[(size_t)i]]; }, shape_of); }
+
+// The systems that travel: empty ones stay empty (linsys.cpp:661-664) and are answered by the caller's answer_empty(b).
+template <class RMatT, class Answer> inline std::vector<int> live_systems(const std::vector<RMatT *> & systems, Answer answer_empty)
+{
+    std::vector<int> live;
+    for (int b = 0; b < (int)systems.size(); b++) { if (systems[(size_t)b]->size() == 0) answer_empty(b); else live.push_back(b); }
+    return live;
+}
+// One class walk: fn(cls) receives the members of `which` whose key_of(b) equals that of the first one not yet handed out, in
+// the caller's order; classes come in order of first appearance. A non-zero return of fn ends the walk and is returned.
+struct class_key {
+    int rows, cols, more;                                           // more: what else the caller tells classes apart by
+    bool operator==(const class_key & o) const { return rows == o.rows && cols == o.cols && more == o.more; }
+};
+template <class RMatT> inline class_key shape_of(const std::vector<RMatT *> & systems, int b, int more = 0)
+{ const class_key k = { (int)systems[(size_t)b]->get_row_size(), (int)systems[(size_t)b]->get_col_size(), more }; return k; }
+template <class Key, class Fn> inline int for_each_class(const std::vector<int> & which, Key key_of, Fn fn)
+{
+    std::vector<class_key> keys;                                    // (SCoPs have a handful of classes: a linear search)
+    std::vector<std::vector<int> > classes;
+    for (size_t i = 0; i < which.size(); i++) {
+        const class_key k = key_of(which[i]);
+        size_t j = 0;
+        while (j < keys.size() && !(keys[j] == k)) j++;
+        if (j == keys.size()) { keys.push_back(k); classes.push_back(std::vector<int>()); }
+        classes[j].push_back(which[i]);
+    }
+    for (size_t j = 0; j < classes.size(); j++) {
+        const int rc = fn(classes[j]);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+// One retry rule. A system (group) that reports -need was short of rows; the call is made again with the capacity it was short
+// of raised to the largest need reported: of a group itself (member -1) cap_hull_rows; above the cap_rows tried a step's
+// unreduced rows, cap_rows; else an output slot, cap_out_rows. What differs between the collectors is data:
+struct caps { int cap, out, hull; };                                // cap_rows, cap_out_rows, cap_hull_rows; 0: the library's default
+enum slot_rule {
+    one_capacity,                                                   // cap_out_rows stays 0 (the slots take cap_rows): EVERY need sets cap_rows
+    own_slot,                                                       // a slot's need raises cap_out_rows alone
+    slot_follows,                                                   // the same, and a raised cap_rows is the slots' as well
+    slot_is_cap                                                     // the slots take cap_rows whatever was short
+};
+struct retry_rule {
+    caps first;                                                     // what the first call passes
+    caps spelled;                                                   // cap != 0: the defaults that call settled on, spelled out after it
+    slot_rule slot;
+    bool groups;                                                    // the verdicts are groups': member -1 is the group's own need
+    int attempts;                                                   // calls at the most; still short: XPG_ERR_UNSUPPORTED
+};
+// What a call answers with: the view into the handle's pinned buffer, an offset (and, the ragged forms, a row count) per result,
+// a verdict, member, chain and step count per system or group -- each entry point fills the ones it has. Plain pointers into one
+// block the driver owns: a sink receives a copy.
+struct answer {
+    const xpg_rat32 * view;
+    long long * off;
+    int32_t * rows, * ok, * member, * chain, * steps;
+    // result r where the offsets count ROWS of `cols` columns (the packed forms) ...
+    const xpg_rat32 * packed_at(size_t r, int cols) const { return view ? view + (size_t)off[r] * cols : view; }
+    int packed_rows(size_t r) const { return (int)(off[r + 1] - off[r]); }
+    template <class RMatT> void put_packed(RMatT & m, size_t r, int cols) const { put_cells(m, packed_at(r, cols), packed_rows(r), cols); }
+    // ... and where they count cells and every result has a row count of its own (the ragged forms)
+    const xpg_rat32 * ragged_at(size_t r) const { return view ? view + off[r] : view; }
+    template <class RMatT> void put_ragged(RMatT & m, size_t r, int cols) const { put_cells(m, ragged_at(r), (int)rows[r], cols); }
+};
+// reads the verdicts of a call: true = all answered, else the right capacity is raised
+inline bool answered(const retry_rule & how, caps & c, const answer & a, size_t systems)
+{
+    int need_cap = 0, need_out = 0, need_hull = 0;
+    for (size_t i = 0; i < systems; i++) {
+        const int need = -a.ok[i];
+        if (need <= 0) continue;                                    // answered
+        if (how.groups && a.member[i] < 0) { if (need > need_hull) need_hull = need; }
+        else if (how.slot == one_capacity || need > c.cap) { if (need > need_cap) need_cap = need; }
+        else if (need > need_out) need_out = need;
+    }
+    if (need_cap) c.cap = need_cap;
+    if (how.slot == slot_follows && need_cap) c.out = c.cap;
+    else if (need_out) c.out = need_out;
+    if (how.slot == slot_is_cap) c.out = c.cap;
+    if (need_hull) c.hull = need_hull;
+    return !(need_cap || need_out || need_hull);
+}
+// call(capacities, answer) makes the library call for `systems` systems (groups) with `results` results in all; sink(answer)
+// takes the results once every answer is there. Returns the call's code as soon as it is not 0, else 0, or XPG_ERR_UNSUPPORTED:
+// never a silent empty result.
+template <class Call, class Sink>
+inline int call_until_answered(const retry_rule & how, size_t systems, size_t results, Call call, Sink sink)
+{
+    caps c = how.first;
+    const size_t room = results + 1 + (results + 4 * systems + 1) / 2;   // in long long: the offsets, then the five int32 arrays
+    long long few[64];                                              // (a batch of one, a small class: no allocation)
+    const std::unique_ptr<long long[]> many(room > 64 ? new long long[room] : (long long *)0);
+    answer a;
+    a.off = room > 64 ? many.get() : few; a.rows = (int32_t *)(void *)(a.off + results + 1); a.ok = a.rows + results;
+    a.member = a.ok + systems; a.chain = a.member + systems; a.steps = a.chain + systems;
+    for (int attempt = 0; attempt < how.attempts; attempt++) {
+        std::memset((void *)a.off, 0, sizeof(long long) * room);
+        a.view = 0;
+        const int rc = call(c, a);
+        if (rc != 0) return rc;
+        if (attempt == 0 && how.spelled.cap) c = how.spelled;
+        if (answered(how, c, a, systems)) { const answer got = a; sink(got); return 0; }
+    }
+    return XPG_ERR_UNSUPPORTED;
+}
+inline int chain_default(int rows) { return rows * rows / 4 + rows + 1; }     // the library's default cap_rows of an fme chain
+inline int bound_default(int rows) { return 4 * rows + 16; }                  // of a calcBound walk, and a level's slot at the most
+
 // (defined below the collectors: the one call behind Lineq::ConvexHullUnionAndIntersect, hull_all and project_union_each)
 template <class RMatT>
 int hull_groups(const std::vector<std::vector<RMatT *> > & groups, const std::vector<int32_t> & rhs_idx,
@@ -37,12 +190,7 @@ template <class RMatT> class Lineq {
     xpg_ctx * m_ctx;
     RMatT * m_coeff;                 // linsys.h:64-70
     int m_rhs_idx;
-    xpg_ctx * ctx() { return m_ctx ? m_ctx : detail::shared_context(); }
-    static void put(RMatT & m, const std::vector<xpg_rat32> & a, int rows, int cols)
-    {
-        m.reinit(rows, cols);
-        if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a.data(), sizeof(xpg_rat32) * (size_t)rows * cols);
-    }
+    xpg_ctx * ctx() { return detail::ctx_or_shared(m_ctx); }
 public:
     explicit Lineq(RMatT * m, int rhs_idx = -1, xpg_ctx * c = 0) : m_ctx(c), m_coeff(m), m_rhs_idx(rhs_idx)
     { if (m && rhs_idx == -1) m_rhs_idx = (int)m->get_col_size() - 1; }
@@ -137,7 +285,7 @@ public:
         std::memcpy((void *)a.data(), (const void *)m.get_matrix(), sizeof(xpg_rat32) * a.size());
         int32_t kept = 0, ok = 0;
         if (xpg_lineq_reduce_batch_rat32(ctx(), 1, a.data(), rows, cols, (int)rhs_idx, is_intersect ? 1 : 0, &kept, &ok) != 0) return false;
-        put(m, a, kept, cols);
+        detail::put_cells(m, a.data(), kept, cols);
         return ok != 0;
     }
     // Lineq::removeIdenRow, linsys.cpp:1209-1268
@@ -148,7 +296,7 @@ public:
         std::vector<xpg_rat32> a((size_t)rows * cols);
         std::memcpy((void *)a.data(), (const void *)m.get_matrix(), sizeof(xpg_rat32) * a.size());
         int32_t kept = 0;
-        if (xpg_lineq_remove_iden_batch_rat32(ctx(), 1, a.data(), rows, cols, &kept) == 0) put(m, a, kept, cols);
+        if (xpg_lineq_remove_iden_batch_rat32(ctx(), 1, a.data(), rows, cols, &kept) == 0) detail::put_cells(m, a.data(), kept, cols);
     }
     // Lineq::move2var, linsys.cpp:1177-1200
     void move2var(RMatT & ieq, unsigned rhs_idx, unsigned first_sym, unsigned last_sym, unsigned * first_var_idx, unsigned * last_var_idx)
@@ -169,9 +317,7 @@ public:
         int32_t ok = 0;
         if (xpg_lineq_fme_batch_packed_rat32(ctx(), 1, (const xpg_rat32 *)m_coeff->get_matrix(), rows, cols, m_rhs_idx, (int)u,
                                              darkshadow ? 1 : 0, 0, (xpg_rat32 *)0, 0, &view, off, &ok) != 0) return false;
-        const int orows = (int)off[1];
-        res.reinit(orows, cols);
-        if (orows > 0 && cols > 0) std::memcpy((void *)res.get_matrix(), (const void *)view, sizeof(xpg_rat32) * (size_t)orows * cols);
+        detail::put_cells(res, view, (int)off[1], cols);
         return ok != 0;
     }
     // Lineq::has_solution, linsys.cpp:830-906
@@ -192,40 +338,36 @@ public:
     //                                             (linsys.cpp:1072-1074), so the call site at linsys.cpp:312 compiles unchanged
     //   bool calcBound(std::vector<RMat> &)    -- the same with value semantics (resized to m_rhs_idx)
 private:
+    // sink(j, cells, rows, cols): variable j's bounds, read straight out of the handle's pinned buffer once they are all there.
+    // A capacity found short is set to the need reported and the call made once more.
     template <class Sink> bool calc_bound_into(Sink sink)
     {
-        // the packed form: only the live rows of the nv bound systems travel, read straight out of the handle's pinned buffer
+        // the packed form: only the live rows of the nv bound systems travel
         const int rows = (int)m_coeff->get_row_size(), cols = (int)m_coeff->get_col_size(), nv = m_rhs_idx;
-        int cap = 4 * rows + 16;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            std::vector<long long> off((size_t)nv + 1, 0);
-            const xpg_rat32 * view = 0;
-            int32_t ok = 0, chain = -1, step = 0;
-            if (xpg_lineq_bounds_batch_packed_rat32(ctx(), 1, (const xpg_rat32 *)m_coeff->get_matrix(), rows, cols, nv, cap, 0, (xpg_rat32 *)0, 0,
-                                                    &view, off.data(), &ok, &chain, &step) != 0) return false;
-            if (ok < 0) { cap = -ok; continue; }
-            if (ok == 0) return false;                       // "system inconsistency!" (linsys.cpp:1065-1068)
-            for (int j = 0; j < nv; j++) {
-                const int r = (int)(off[(size_t)j + 1] - off[(size_t)j]);
-                std::vector<xpg_rat32> one;
-                if (r) one.assign(view + (size_t)off[(size_t)j] * cols, view + (size_t)off[(size_t)j + 1] * cols);
-                sink(j, one, r, cols);
-            }
-            return true;
-        }
-        return false;
+        const detail::retry_rule how = { { detail::bound_default(rows), 0, 0 }, { 0, 0, 0 }, detail::one_capacity, false, 2 };
+        bool consistent = false;
+        return detail::call_until_answered(how, 1, (size_t)nv,
+            [&](const detail::caps & c, detail::answer & a) {
+                return xpg_lineq_bounds_batch_packed_rat32(ctx(), 1, (const xpg_rat32 *)m_coeff->get_matrix(), rows, cols, nv, c.cap, c.out,
+                                                           (xpg_rat32 *)0, 0, &a.view, a.off, a.ok, a.chain, a.steps);
+            },
+            [&](const detail::answer & a) {
+                if (a.ok[0] == 0) return;                        // "system inconsistency!" (linsys.cpp:1065-1068)
+                consistent = true;
+                for (int j = 0; j < nv; j++) sink(j, a.packed_at((size_t)j, cols), a.packed_rows((size_t)j), cols);
+            }) == 0 && consistent;
     }
 public:
     bool calcBound(std::vector<RMatT> & limits)
     {
         limits.resize((size_t)m_rhs_idx);
-        return calc_bound_into([&](int j, const std::vector<xpg_rat32> & a, int r, int c) { put(limits[(size_t)j], a, r, c); });
+        return calc_bound_into([&](int j, const xpg_rat32 * a, int r, int c) { detail::put_cells(limits[(size_t)j], a, r, c); });
     }
     template <class ListT, class = decltype(std::declval<ListT &>().get_head_nth(0u)), class = decltype(std::declval<ListT &>().get_elem_count())>
     bool calcBound(ListT & limits)
     {
         if ((int)limits.get_elem_count() != m_rhs_idx) return false;      // the reference ASSERTs (linsys.cpp:1050-1051)
-        return calc_bound_into([&](int j, const std::vector<xpg_rat32> & a, int r, int c) { put(*limits.get_head_nth((unsigned)j), a, r, c); });
+        return calc_bound_into([&](int j, const xpg_rat32 * a, int r, int c) { detail::put_cells(*limits.get_head_nth((unsigned)j), a, r, c); });
     }
     // Loop-bound generation, LoopTran::transformIterSpace (src/eng/ldtran.cpp:178-196 unimodular, :241-257 nonsingular):
     //     newb = aux_limits.get_tail();
@@ -241,11 +383,6 @@ public:
     //   bool fmeLevels(std::vector<RMat> & aux_limits, RMat * A = 0) -- value semantics: resized to m_rhs_idx, [0] the
     //                                                                 outermost bound (the head), back() the system
 private:
-    static void put_rows(RMatT & m, const xpg_rat32 * a, int rows, int cols)
-    {
-        m.reinit((unsigned)rows, (unsigned)cols);
-        if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a, sizeof(xpg_rat32) * (size_t)rows * cols);
-    }
     // sink(pos, cells, rows, cols): pos 0 is the system itself (the tail), pos k + 1 level k; called only once every level
     // is there, read straight out of the handle's pinned buffer. A capacity found short is raised to the need reported --
     // need > cap: a step's unreduced rows, else a level's slot -- and the call made again, at most four times.
@@ -262,22 +399,20 @@ private:
         }
         std::vector<int32_t> elim((size_t)n);
         for (int k = 0; k < n; k++) elim[(size_t)k] = nv - 1 - k;
-        int cap = rows * rows / 4 + rows + 1, cap_out = cap < 4 * rows + 16 ? cap : 4 * rows + 16;
-        for (int attempt = 0; attempt < 4; attempt++) {
-            std::vector<long long> off((size_t)n + 1, 0);
-            const xpg_rat32 * view = 0;
-            int32_t ok = 0, step = 0;
-            if (xpg_lineq_levels_batch_packed_rat32(ctx(), 1, in, rows, cols, nv, elim.data(), n, 0, cap, cap_out, (xpg_rat32 *)0, 0, &view,
-                                                    off.data(), &ok, &step) != 0) return false;
-            if (ok < 0) { if (-ok > cap) cap = -ok; else cap_out = -ok; continue; }
-            if (ok == 0) return false;                           // "system inconsistency!" (ldtran.cpp:186-188)
-            sink(0, in, rows, cols);
-            for (int k = 0; k < n; k++)
-                sink(k + 1, off[(size_t)k + 1] > off[(size_t)k] ? view + (size_t)off[(size_t)k] * cols : (const xpg_rat32 *)0,
-                     (int)(off[(size_t)k + 1] - off[(size_t)k]), cols);
-            return true;
-        }
-        return false;
+        const int cap = detail::chain_default(rows);
+        const detail::retry_rule how = { { cap, cap < detail::bound_default(rows) ? cap : detail::bound_default(rows), 0 }, { 0, 0, 0 }, detail::own_slot, false, 4 };
+        bool consistent = false;
+        return detail::call_until_answered(how, 1, (size_t)n,
+            [&](const detail::caps & c, detail::answer & a) {
+                return xpg_lineq_levels_batch_packed_rat32(ctx(), 1, in, rows, cols, nv, elim.data(), n, 0, c.cap, c.out, (xpg_rat32 *)0, 0, &a.view,
+                                                           a.off, a.ok, a.steps);
+            },
+            [&](const detail::answer & a) {
+                if (a.ok[0] == 0) return;                        // "system inconsistency!" (ldtran.cpp:186-188)
+                consistent = true;
+                sink(0, in, rows, cols);
+                for (int k = 0; k < n; k++) sink(k + 1, a.packed_at((size_t)k, cols), a.packed_rows((size_t)k), cols);
+            }) == 0 && consistent;
     }
 public:
     bool fmeLevels(std::vector<RMatT> & aux_limits, RMatT * A = 0)
@@ -285,7 +420,7 @@ public:
         if (m_rhs_idx < 1) return false;
         const size_t nv = (size_t)m_rhs_idx;
         std::vector<RMatT> got(nv);
-        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { put_rows(got[nv - 1 - (size_t)pos], a, r, c); })) return false;
+        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { detail::put_cells(got[nv - 1 - (size_t)pos], a, r, c); })) return false;
         aux_limits.swap(got);
         if (A) *A = aux_limits[0];
         return true;
@@ -301,7 +436,7 @@ public:
             dst.push_back(newb);
             if ((int)dst.size() == m_rhs_idx) break;
         }
-        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { put_rows(*dst[(size_t)pos], a, r, c); })) return false;
+        if (!levels_into([&](int pos, const xpg_rat32 * a, int r, int c) { detail::put_cells(*dst[(size_t)pos], a, r, c); })) return false;
         if (A) *A = *dst.back();
         return true;
     }
@@ -340,20 +475,9 @@ public:
 template <class RMatT>
 inline int dep_is_empty_all(const std::vector<RMatT *> & polys, std::vector<int32_t> & empty, xpg_ctx * c = 0)
 {
-    const int nb = (int)polys.size();
-    std::vector<int32_t> rows((size_t)nb), cols((size_t)nb);
-    std::vector<long long> off((size_t)nb + 1, 0);
-    for (int b = 0; b < nb; b++) {
-        rows[(size_t)b] = (int32_t)polys[(size_t)b]->get_row_size(); cols[(size_t)b] = (int32_t)polys[(size_t)b]->get_col_size();
-        off[(size_t)b + 1] = off[(size_t)b] + (long long)rows[(size_t)b] * cols[(size_t)b];
-    }
-    std::vector<xpg_rat32> flat((size_t)off[(size_t)nb]);
-    for (int b = 0; b < nb; b++)
-        if (rows[(size_t)b] * cols[(size_t)b])
-            std::memcpy((void *)(flat.data() + off[(size_t)b]), (const void *)polys[(size_t)b]->get_matrix(),
-                        sizeof(xpg_rat32) * (size_t)rows[(size_t)b] * cols[(size_t)b]);
-    empty.assign((size_t)nb, 0);
-    return xpg_dep_is_empty_batch_ragged_rat32(c ? c : detail::shared_context(), nb, flat.data(), rows.data(), cols.data(), off.data(),
+    const detail::packed p = detail::pack((int)polys.size(), [&](int b) { return (const RMatT *)polys[(size_t)b]; }, detail::shape_as_is());
+    empty.assign(polys.size(), 0);
+    return xpg_dep_is_empty_batch_ragged_rat32(detail::ctx_or_shared(c), (int)polys.size(), p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(),
                                                empty.data(), (long long *)0);
 }
 
@@ -373,32 +497,21 @@ inline int has_solution_all(const std::vector<RMatT *> & leqs, const std::vector
     if ((int)eqs.size() != nb || rhs_idx < 1 || (int)vc.get_row_size() != rhs_idx || (int)vc.get_col_size() != cols) return XPG_ERR_SHAPE;
     out.assign((size_t)nb, 0);
     if (nb == 0) return 0;
-    const auto rows_of = [&](const RMatT * m) { return m && m->get_col_size() ? (int)m->get_row_size() : 0; };
-    std::vector<int32_t> lrows((size_t)nb), erows((size_t)nb);
-    std::vector<long long> loff((size_t)nb + 1, 0), eoff((size_t)nb + 1, 0);
-    for (int b = 0; b < nb; b++) {
+    const auto rows_of = [](const RMatT * m) { return m && m->get_col_size() ? (int)m->get_row_size() : 0; };
+    const auto shape_of = [&](const RMatT * m) { return std::make_pair(rows_of(m), m ? (int)m->get_col_size() : 0); };
+    for (int b = 0; b < nb; b++)
         for (const RMatT * m : { (const RMatT *)leqs[(size_t)b], (const RMatT *)eqs[(size_t)b] })
             if (rows_of(m) > 0 && (int)m->get_col_size() != cols) return XPG_ERR_SHAPE;
-        lrows[(size_t)b] = rows_of(leqs[(size_t)b]); erows[(size_t)b] = rows_of(eqs[(size_t)b]);
-        loff[(size_t)b + 1] = loff[(size_t)b] + (long long)lrows[(size_t)b] * cols;
-        eoff[(size_t)b + 1] = eoff[(size_t)b] + (long long)erows[(size_t)b] * cols;
-    }
-    std::vector<xpg_rat32> L((size_t)loff[(size_t)nb]), E((size_t)eoff[(size_t)nb]);
-    for (int b = 0; b < nb; b++) {
-        if (lrows[(size_t)b])
-            std::memcpy((void *)(L.data() + loff[(size_t)b]), (const void *)leqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * (size_t)lrows[(size_t)b] * cols);
-        if (erows[(size_t)b])
-            std::memcpy((void *)(E.data() + eoff[(size_t)b]), (const void *)eqs[(size_t)b]->get_matrix(), sizeof(xpg_rat32) * (size_t)erows[(size_t)b] * cols);
-    }
+    const detail::packed L = detail::pack(nb, [&](int b) { return (const RMatT *)leqs[(size_t)b]; }, shape_of),
+                         E = detail::pack(nb, [&](int b) { return (const RMatT *)eqs[(size_t)b]; }, shape_of);
+    const xpg_rat32 * const l = L.cells() ? L.flat.data() : (const xpg_rat32 *)0, * const e = E.cells() ? E.flat.data() : (const xpg_rat32 *)0;
     if (is_int_sol)      // the integer form on the device: objective, both walks and the verdict, one synchronisation per shape class
-        return xpg_has_solution_int_batch_ragged_rat32(c ? c : detail::shared_context(), nb, L.empty() ? (const xpg_rat32 *)0 : L.data(),
-                                                       lrows.data(), loff.data(), E.empty() ? (const xpg_rat32 *)0 : E.data(), erows.data(),
-                                                       eoff.data(), (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx,
-                                                       is_unique_sol ? 1 : 0, out.data(), (int32_t *)0);
-    return xpg_has_solution_batch_ragged_rat32(c ? c : detail::shared_context(), nb, L.empty() ? (const xpg_rat32 *)0 : L.data(), lrows.data(),
-                                               loff.data(), E.empty() ? (const xpg_rat32 *)0 : E.data(), erows.data(), eoff.data(),
-                                               (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, is_int_sol ? 1 : 0,
-                                               is_unique_sol ? 1 : 0, 0xFFFFFFFFu, out.data(), (int32_t *)0);
+        return xpg_has_solution_int_batch_ragged_rat32(detail::ctx_or_shared(c), nb, l, L.rows.data(), L.off.data(), e, E.rows.data(), E.off.data(),
+                                                       (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, is_unique_sol ? 1 : 0, out.data(),
+                                                       (int32_t *)0);
+    return xpg_has_solution_batch_ragged_rat32(detail::ctx_or_shared(c), nb, l, L.rows.data(), L.off.data(), e, E.rows.data(), E.off.data(),
+                                               (const xpg_rat32 *)vc.get_matrix(), rhs_idx, cols, rhs_idx, 0, is_unique_sol ? 1 : 0, 0xFFFFFFFFu,
+                                               out.data(), (int32_t *)0);
 }
 
 // Many eliminations in ONE call: Lineq::fme(u[k], results[k]) (linsys.cpp:656-774) on systems of whatever shapes, the constant
@@ -414,48 +527,35 @@ inline int fme_all(const std::vector<RMatT *> & systems, const std::vector<int32
     if ((int)u.size() != nb || (!rhs_idx.empty() && (int)rhs_idx.size() != nb)) return XPG_ERR_SHAPE;
     results.resize((size_t)nb); ok.assign((size_t)nb, 0);
     // empty systems stay empty (linsys.cpp:661-664) and do not travel
-    std::vector<int> live;
-    for (int b = 0; b < nb; b++) { if (systems[(size_t)b]->size() == 0) { results[(size_t)b].clean(); ok[(size_t)b] = 1; } else live.push_back(b); }
+    const std::vector<int> live = detail::live_systems(systems, [&](int b) { results[(size_t)b].clean(); ok[(size_t)b] = 1; });
     const int nl = (int)live.size();
     if (nl == 0) return 0;
-    std::vector<int32_t> rows((size_t)nl), cols((size_t)nl), uu((size_t)nl), rr((size_t)nl), orows((size_t)nl), ook((size_t)nl);
-    std::vector<long long> off((size_t)nl + 1, 0), ooff((size_t)nl + 1, 0);
+    const detail::packed p = detail::pack(systems, live, detail::shape_as_is());
+    std::vector<int32_t> uu((size_t)nl), rr((size_t)nl), orows((size_t)nl), ook((size_t)nl);
+    std::vector<long long> ooff((size_t)nl + 1, 0);
+    long long capc = 0;                                             // the worst case of every result, in cells
     for (int k = 0; k < nl; k++) {
-        const RMatT & m = *systems[(size_t)live[(size_t)k]];
-        rows[(size_t)k] = (int32_t)m.get_row_size(); cols[(size_t)k] = (int32_t)m.get_col_size();
         uu[(size_t)k] = u[(size_t)live[(size_t)k]];
-        rr[(size_t)k] = rhs_idx.empty() ? cols[(size_t)k] - 1 : rhs_idx[(size_t)live[(size_t)k]];
-        off[(size_t)k + 1] = off[(size_t)k] + (long long)rows[(size_t)k] * cols[(size_t)k];
+        rr[(size_t)k] = rhs_idx.empty() ? p.cols[(size_t)k] - 1 : rhs_idx[(size_t)live[(size_t)k]];
+        capc += ((long long)p.rows[(size_t)k] * p.rows[(size_t)k] / 4 + p.rows[(size_t)k]) * p.cols[(size_t)k];
     }
-    std::vector<xpg_rat32> flat((size_t)off[(size_t)nl]);
-    for (int k = 0; k < nl; k++)
-        std::memcpy((void *)(flat.data() + off[(size_t)k]), (const void *)systems[(size_t)live[(size_t)k]]->get_matrix(),
-                    sizeof(xpg_rat32) * (size_t)rows[(size_t)k] * cols[(size_t)k]);
-    xpg_ctx * h = c ? c : detail::shared_context();
-    // a buffer for the worst case of every result while that is small (one call), else a sizing call first
-    long long capc = 0;
-    for (int k = 0; k < nl; k++) capc += ((long long)rows[(size_t)k] * rows[(size_t)k] / 4 + rows[(size_t)k]) * cols[(size_t)k];
+    xpg_ctx * h = detail::ctx_or_shared(c);
     std::vector<xpg_rat32> outs;
+    const auto call = [&](long long room) {
+        outs.resize((size_t)(room > 0 ? room : 1));
+        return xpg_lineq_fme_batch_ragged_rat32(h, nl, p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(), rr.data(), uu.data(), darkshadow ? 1 : 0,
+                                                room < 0 ? (xpg_rat32 *)0 : outs.data(), room < 0 ? 0 : room, ooff.data(), orows.data(), ook.data());
+    };
+    // a buffer for the worst case of every result while that is small (one call), else a sizing call (no buffer) first
     int rc;
-    if (capc * (long long)sizeof(xpg_rat32) <= (64ll << 20)) {
-        outs.resize((size_t)(capc > 0 ? capc : 1));
-        rc = xpg_lineq_fme_batch_ragged_rat32(h, nl, flat.data(), rows.data(), cols.data(), off.data(), rr.data(), uu.data(), darkshadow ? 1 : 0,
-                                              outs.data(), capc, ooff.data(), orows.data(), ook.data());
-    } else {
-        rc = xpg_lineq_fme_batch_ragged_rat32(h, nl, flat.data(), rows.data(), cols.data(), off.data(), rr.data(), uu.data(), darkshadow ? 1 : 0,
-                                              (xpg_rat32 *)0, 0, ooff.data(), orows.data(), ook.data());
-        if (rc == XPG_ERR_SHAPE && ooff[(size_t)nl] > 0) {
-            outs.resize((size_t)ooff[(size_t)nl]);
-            rc = xpg_lineq_fme_batch_ragged_rat32(h, nl, flat.data(), rows.data(), cols.data(), off.data(), rr.data(), uu.data(), darkshadow ? 1 : 0,
-                                                  outs.data(), ooff[(size_t)nl], ooff.data(), orows.data(), ook.data());
-        }
+    if (capc * (long long)sizeof(xpg_rat32) <= (64ll << 20)) rc = call(capc);
+    else {
+        rc = call(-1);
+        if (rc == XPG_ERR_SHAPE && ooff[(size_t)nl] > 0) rc = call(ooff[(size_t)nl]);
     }
     if (rc != 0) return rc;
     for (int k = 0; k < nl; k++) {
-        RMatT & res = results[(size_t)live[(size_t)k]];
-        res.reinit(orows[(size_t)k], cols[(size_t)k]);
-        if (orows[(size_t)k] * cols[(size_t)k])
-            std::memcpy((void *)res.get_matrix(), (const void *)(outs.data() + ooff[(size_t)k]), sizeof(xpg_rat32) * (size_t)orows[(size_t)k] * cols[(size_t)k]);
+        detail::put_cells(results[(size_t)live[(size_t)k]], outs.data() + ooff[(size_t)k], orows[(size_t)k], p.cols[(size_t)k]);
         ok[(size_t)live[(size_t)k]] = ook[(size_t)k];
     }
     return 0;
@@ -476,50 +576,27 @@ inline int project_all(const std::vector<RMatT *> & systems, const std::vector<i
     const int nb = (int)systems.size();
     results.resize((size_t)nb); ok.assign((size_t)nb, 0);
     if (elim.empty() || rhs_idx < 1) return XPG_ERR_SHAPE;
-    xpg_ctx * h = c ? c : detail::shared_context();
-    std::vector<char> done((size_t)nb, 0);
-    for (int b0 = 0; b0 < nb; b0++) {
-        if (done[(size_t)b0]) continue;
-        if (systems[(size_t)b0]->size() == 0) {                     // an empty system stays empty (linsys.cpp:661-664), no call
-            results[(size_t)b0].clean(); ok[(size_t)b0] = 1; done[(size_t)b0] = 1;
-            continue;
-        }
-        const int rows = (int)systems[(size_t)b0]->get_row_size(), cols = (int)systems[(size_t)b0]->get_col_size();
-        std::vector<int> cls;
-        for (int b = b0; b < nb; b++)
-            if (!done[(size_t)b] && systems[(size_t)b]->size() != 0 && (int)systems[(size_t)b]->get_row_size() == rows &&
-                (int)systems[(size_t)b]->get_col_size() == cols) {
-                cls.push_back(b); done[(size_t)b] = 1;
-            }
+    xpg_ctx * h = detail::ctx_or_shared(c);
+    // an empty system stays empty (linsys.cpp:661-664), no call
+    const std::vector<int> live = detail::live_systems(systems, [&](int b) { results[(size_t)b].clean(); ok[(size_t)b] = 1; });
+    return detail::for_each_class(live, [&](int b) { return detail::shape_of(systems, b); }, [&](const std::vector<int> & cls) {
         const int nc = (int)cls.size();
-        std::vector<xpg_rat32> flat((size_t)nc * rows * cols);
-        for (int k = 0; k < nc; k++)
-            std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
-        int cap = 0;                                                // the library's default first; the final slots take cap too
-        bool answered = false;
-        for (int attempt = 0; attempt < 3 && !answered; attempt++) {
-            std::vector<long long> off((size_t)nc + 1, 0);
-            std::vector<int32_t> kok((size_t)nc, 0), steps((size_t)nc, 0);
-            const xpg_rat32 * view = 0;
-            const int rc = xpg_lineq_project_batch_packed_rat32(h, nc, flat.data(), rows, cols, rhs_idx, elim.data(), (int)elim.size(),
-                                                                darkshadow ? 1 : 0, cap, 0, (xpg_rat32 *)0, 0, &view, off.data(),
-                                                                kok.data(), steps.data());
-            if (rc != 0) return rc;
-            int need = 0;
-            for (int k = 0; k < nc; k++) if (kok[(size_t)k] < 0 && -kok[(size_t)k] > need) need = -kok[(size_t)k];
-            if (need) { cap = need; continue; }                     // a step needed more rows than cap: once more with that many
-            for (int k = 0; k < nc; k++) {
-                const int b = cls[(size_t)k];
-                const long long lo = off[(size_t)k], hi = off[(size_t)k + 1];
-                ok[(size_t)b] = kok[(size_t)k];
-                results[(size_t)b].reinit((unsigned)(hi - lo), (unsigned)cols);
-                if (hi > lo) std::memcpy((void *)results[(size_t)b].get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
-            }
-            answered = true;
-        }
-        if (!answered) return XPG_ERR_UNSUPPORTED;
-    }
-    return 0;
+        const int rows = (int)systems[(size_t)cls[0]]->get_row_size(), cols = (int)systems[(size_t)cls[0]]->get_col_size();
+        const detail::shape_known shape = { rows, cols };
+        const detail::packed p = detail::pack(systems, cls, shape);
+        const detail::retry_rule how = { { 0, 0, 0 }, { 0, 0, 0 }, detail::one_capacity, false, 3 };   // the library's default first; the final slots take cap too
+        return detail::call_until_answered(how, (size_t)nc, (size_t)nc,
+            [&](const detail::caps & cp, detail::answer & a) {
+                return xpg_lineq_project_batch_packed_rat32(h, nc, p.flat.data(), rows, cols, rhs_idx, elim.data(), (int)elim.size(), darkshadow ? 1 : 0,
+                                                            cp.cap, cp.out, (xpg_rat32 *)0, 0, &a.view, a.off, a.ok, a.steps);
+            },
+            [&](const detail::answer & a) {
+                for (int k = 0; k < nc; k++) {
+                    ok[(size_t)cls[(size_t)k]] = a.ok[(size_t)k];
+                    a.put_packed(results[(size_t)cls[(size_t)k]], (size_t)k, cols);
+                }
+            });
+    });
 }
 
 // Loop-nest limits for many statements in few calls: the variables elim[0], elim[1], ... eliminated out of every *systems[k]
@@ -539,69 +616,42 @@ inline int levels_all(const std::vector<RMatT *> & systems, const std::vector<in
     levels.assign((size_t)nb, std::vector<RMatT>());
     ok.assign((size_t)nb, 0);
     if (elim.empty() || rhs_idx < 1) return XPG_ERR_SHAPE;
-    xpg_ctx * h = c ? c : detail::shared_context();
-    std::vector<char> done((size_t)nb, 0);
-    for (int b0 = 0; b0 < nb; b0++) {
-        if (done[(size_t)b0]) continue;
-        if (systems[(size_t)b0]->size() == 0) {                     // an empty system stays empty (linsys.cpp:661-664), no call
-            levels[(size_t)b0].resize((size_t)n);
-            for (int k = 0; k < n; k++) levels[(size_t)b0][(size_t)k].clean();
-            ok[(size_t)b0] = 1; done[(size_t)b0] = 1;
-            continue;
-        }
-        const int rows = (int)systems[(size_t)b0]->get_row_size(), cols = (int)systems[(size_t)b0]->get_col_size();
-        std::vector<int> cls;
-        for (int b = b0; b < nb; b++)
-            if (!done[(size_t)b] && systems[(size_t)b]->size() != 0 && (int)systems[(size_t)b]->get_row_size() == rows &&
-                (int)systems[(size_t)b]->get_col_size() == cols) {
-                cls.push_back(b); done[(size_t)b] = 1;
-            }
+    xpg_ctx * h = detail::ctx_or_shared(c);
+    // an empty system stays empty (linsys.cpp:661-664), no call
+    const std::vector<int> live = detail::live_systems(systems, [&](int b) {
+        levels[(size_t)b].resize((size_t)n);
+        for (int k = 0; k < n; k++) levels[(size_t)b][(size_t)k].clean();
+        ok[(size_t)b] = 1;
+    });
+    return detail::for_each_class(live, [&](int b) { return detail::shape_of(systems, b); }, [&](const std::vector<int> & cls) {
         const int nc = (int)cls.size();
-        std::vector<xpg_rat32> flat((size_t)nc * rows * cols);
-        for (int k = 0; k < nc; k++)
-            std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
-        int cap = rows * rows / 4 + rows + 1, cap_out = cap < 4 * rows + 16 ? cap : 4 * rows + 16;   // the library's defaults, spelled out
-        bool answered = false;
-        for (int attempt = 0; attempt < 4 && !answered; attempt++) {
-            std::vector<long long> off((size_t)nc * n + 1, 0);
-            std::vector<int32_t> kok((size_t)nc, 0), steps((size_t)nc, 0);
-            const xpg_rat32 * view = 0;
-            const int rc = xpg_lineq_levels_batch_packed_rat32(h, nc, flat.data(), rows, cols, rhs_idx, elim.data(), n, darkshadow ? 1 : 0,
-                                                               cap, cap_out, (xpg_rat32 *)0, 0, &view, off.data(), kok.data(), steps.data());
-            if (rc != 0) return rc;
-            int need_cap = 0, need_out = 0;
-            for (int k = 0; k < nc; k++) {
-                const int need = -kok[(size_t)k];
-                if (need > cap) { if (need > need_cap) need_cap = need; }
-                else if (need > need_out) need_out = need;          // (need <= 0: the system was answered)
-            }
-            if (need_cap) cap = need_cap;
-            if (need_out) cap_out = need_out;
-            if (need_cap || need_out) continue;
-            for (int k = 0; k < nc; k++) {
-                const int b = cls[(size_t)k];
-                ok[(size_t)b] = kok[(size_t)k];
-                levels[(size_t)b].resize((size_t)n);
-                for (int j = 0; j < n; j++) {
-                    const long long lo = off[(size_t)k * n + j], hi = off[(size_t)k * n + j + 1];
-                    RMatT & m = levels[(size_t)b][(size_t)j];
-                    m.reinit((unsigned)(hi - lo), (unsigned)cols);
-                    if (hi > lo) std::memcpy((void *)m.get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
+        const int rows = (int)systems[(size_t)cls[0]]->get_row_size(), cols = (int)systems[(size_t)cls[0]]->get_col_size(), cap = detail::chain_default(rows);
+        const detail::shape_known shape = { rows, cols };
+        const detail::packed p = detail::pack(systems, cls, shape);
+        const detail::retry_rule how = { { cap, cap < detail::bound_default(rows) ? cap : detail::bound_default(rows), 0 }, { 0, 0, 0 },   // the library's defaults, spelled out
+                                         detail::own_slot, false, 4 };
+        return detail::call_until_answered(how, (size_t)nc, (size_t)nc * n,
+            [&](const detail::caps & cp, detail::answer & a) {
+                return xpg_lineq_levels_batch_packed_rat32(h, nc, p.flat.data(), rows, cols, rhs_idx, elim.data(), n, darkshadow ? 1 : 0, cp.cap, cp.out,
+                                                           (xpg_rat32 *)0, 0, &a.view, a.off, a.ok, a.steps);
+            },
+            [&](const detail::answer & a) {
+                for (int k = 0; k < nc; k++) {
+                    std::vector<RMatT> & lev = levels[(size_t)cls[(size_t)k]];
+                    ok[(size_t)cls[(size_t)k]] = a.ok[(size_t)k];
+                    lev.resize((size_t)n);
+                    for (int j = 0; j < n; j++) a.put_packed(lev[(size_t)j], (size_t)k * n + j, cols);
                 }
-            }
-            answered = true;
-        }
-        if (!answered) return XPG_ERR_UNSUPPORTED;
-    }
-    return 0;
+            });
+    });
 }
 
 namespace detail {
 // What project_each and levels_nests share: the systems that travel (`live`: indices into `systems`, each with its list in
 // `lists`) go up in ONE xpg_lineq_{project,levels}_batch_ragged_rat32 call whatever their shapes and lists; a call found
 // short of rows is made again with the largest need reported -- above the capacity tried: a step's unreduced rows, cap_rows;
-// else an output slot, cap_out_rows -- at most four times, then XPG_ERR_UNSUPPORTED. sink(i, k, cells, rows, cols) receives
-// result k of live system i (k == 0 alone for a projection) out of the handle's pinned buffer, once every answer is there;
+// else an output slot, cap_out_rows -- at most four times, then XPG_ERR_UNSUPPORTED. sink(i, k, answer, r, cols) receives
+// result k of live system i (k == 0 alone for a projection), result r of the answer, once every answer is there;
 // ok[live[i]] the verdict (1, or 0: a step found the system inconsistent, every result of it empty).
 template <class RMatT, class Sink>
 inline int chain_ragged(bool levels, const std::vector<RMatT *> & systems, const std::vector<int> & live, const std::vector<std::vector<int32_t> > & lists,
@@ -609,60 +659,29 @@ inline int chain_ragged(bool levels, const std::vector<RMatT *> & systems, const
 {
     const int nl = (int)live.size();
     if (nl == 0) return 0;
-    std::vector<int32_t> rows((size_t)nl), cols((size_t)nl), rr((size_t)nl), eoff((size_t)nl + 1, 0), flat_el;
-    std::vector<long long> off((size_t)nl + 1, 0);
+    const packed p = pack(systems, live, shape_as_is());
+    std::vector<int32_t> rr((size_t)nl), eoff((size_t)nl + 1, 0), flat_el;
     for (int i = 0; i < nl; i++) {
-        const RMatT & m = *systems[(size_t)live[(size_t)i]];
-        rows[(size_t)i] = (int32_t)m.get_row_size(); cols[(size_t)i] = (int32_t)m.get_col_size();
         rr[(size_t)i] = rhs_idx[(size_t)live[(size_t)i]];
-        off[(size_t)i + 1] = off[(size_t)i] + (long long)rows[(size_t)i] * cols[(size_t)i];
         flat_el.insert(flat_el.end(), lists[(size_t)i].begin(), lists[(size_t)i].end());
         eoff[(size_t)i + 1] = (int32_t)flat_el.size();
     }
-    std::vector<xpg_rat32> flat((size_t)off[(size_t)nl]);
-    for (int i = 0; i < nl; i++)
-        std::memcpy((void *)(flat.data() + off[(size_t)i]), (const void *)systems[(size_t)live[(size_t)i]]->get_matrix(),
-                    sizeof(xpg_rat32) * (size_t)rows[(size_t)i] * cols[(size_t)i]);
-    const int nres = levels ? (int)flat_el.size() : nl;
-    int cap = 0, cap_out = 0;                                       // the library's defaults first
-    for (int attempt = 0; attempt < 4; attempt++) {
-        std::vector<long long> ooff((size_t)nres + 1, 0);
-        std::vector<int32_t> orows((size_t)nres, 0), kok((size_t)nl, 0), steps((size_t)nl, 0);
-        const xpg_rat32 * view = 0;
-        const int rc = (levels ? xpg_lineq_levels_batch_ragged_rat32 : xpg_lineq_project_batch_ragged_rat32)(
-            h, nl, flat.data(), rows.data(), cols.data(), off.data(), rr.data(), flat_el.data(), eoff.data(), darkshadow ? 1 : 0, cap, cap_out,
-            (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), steps.data());
-        if (rc != 0) return rc;
-        if (cap == 0) {                                             // the capacities that call settled on (xpoly_amd.h), spelled out
-            int most = 0;
-            for (int i = 0; i < nl; i++) if (rows[(size_t)i] > most) most = rows[(size_t)i];
-            cap = most * most / 4 + most + 1;
-            cap_out = levels && 4 * most + 16 < cap ? 4 * most + 16 : cap;
-        }
-        int need_cap = 0, need_out = 0;
-        for (int i = 0; i < nl; i++) {
-            const int need = -kok[(size_t)i];
-            if (need > cap) { if (need > need_cap) need_cap = need; }
-            else if (need > need_out) need_out = need;              // (need <= 0: the system was answered)
-        }
-        if (need_cap) cap = need_cap;
-        if (need_out) cap_out = need_out;
-        if (!levels) cap_out = cap;                                 // (a projection's final slot takes cap)
-        if (need_cap || need_out) continue;
-        for (int i = 0; i < nl; i++) {
-            ok[(size_t)live[(size_t)i]] = kok[(size_t)i];
-            const int first = levels ? eoff[(size_t)i] : i, n = levels ? eoff[(size_t)i + 1] - eoff[(size_t)i] : 1;
-            for (int k = 0; k < n; k++)
-                sink(i, k, view ? view + ooff[(size_t)(first + k)] : view, (int)orows[(size_t)(first + k)], (int)cols[(size_t)i]);
-        }
-        return 0;
-    }
-    return XPG_ERR_UNSUPPORTED;
-}
-template <class RMatT> inline void put_cells(RMatT & m, const xpg_rat32 * a, int rows, int cols)
-{
-    m.reinit((unsigned)rows, (unsigned)cols);
-    if (rows > 0 && cols > 0) std::memcpy((void *)m.get_matrix(), (const void *)a, sizeof(xpg_rat32) * (size_t)rows * cols);
+    const int nres = levels ? (int)flat_el.size() : nl, cap = chain_default(p.most);
+    // the library's defaults first, then the capacities that call settled on (xpoly_amd.h); a projection's final slot takes cap
+    const retry_rule how = { { 0, 0, 0 }, { cap, levels && bound_default(p.most) < cap ? bound_default(p.most) : cap, 0 }, levels ? own_slot : slot_is_cap, false, 4 };
+    return call_until_answered(how, (size_t)nl, (size_t)nres,
+        [&](const caps & cp, answer & a) {
+            return (levels ? xpg_lineq_levels_batch_ragged_rat32 : xpg_lineq_project_batch_ragged_rat32)(
+                h, nl, p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(), rr.data(), flat_el.data(), eoff.data(), darkshadow ? 1 : 0, cp.cap, cp.out,
+                (xpg_rat32 *)0, 0, &a.view, a.off, a.rows, a.ok, a.steps);
+        },
+        [&](const answer & a) {
+            for (int i = 0; i < nl; i++) {
+                ok[(size_t)live[(size_t)i]] = a.ok[(size_t)i];
+                const int first = levels ? eoff[(size_t)i] : i, n = levels ? eoff[(size_t)i + 1] - eoff[(size_t)i] : 1;
+                for (int k = 0; k < n; k++) sink(i, k, a, (size_t)(first + k), (int)p.cols[(size_t)i]);
+            }
+        });
 }
 } // namespace detail
 
@@ -687,8 +706,8 @@ inline int project_each(const std::vector<RMatT *> & systems, const std::vector<
         if (systems[(size_t)b]->size() == 0) { results[(size_t)b].clean(); ok[(size_t)b] = 1; }
         else { live.push_back(b); lists.push_back(elims[(size_t)b]); }
     }
-    return detail::chain_ragged(false, systems, live, lists, rhs_idx, ok, c ? c : detail::shared_context(), darkshadow,
-                                [&](int i, int, const xpg_rat32 * a, int r, int cc) { detail::put_cells(results[(size_t)live[(size_t)i]], a, r, cc); });
+    return detail::chain_ragged(false, systems, live, lists, rhs_idx, ok, detail::ctx_or_shared(c), darkshadow,
+                                [&](int i, int, const detail::answer & a, size_t r, int cc) { a.put_ragged(results[(size_t)live[(size_t)i]], r, cc); });
 }
 
 // Loop-nest limits for the statements of a SCoP in ONE call: levels_all for nests of DIFFERENT depths. System k has rhs_idx[k]
@@ -721,8 +740,8 @@ inline int levels_nests(const std::vector<RMatT *> & systems, const std::vector<
         for (int u = nv - 1; u > 0; u--) el.push_back(u);
         live.push_back(b); lists.push_back(el);
     }
-    return detail::chain_ragged(true, systems, live, lists, rhs_idx, ok, c ? c : detail::shared_context(), darkshadow,
-                                [&](int i, int k, const xpg_rat32 * a, int r, int cc) { detail::put_cells(levels[(size_t)live[(size_t)i]][(size_t)k], a, r, cc); });
+    return detail::chain_ragged(true, systems, live, lists, rhs_idx, ok, detail::ctx_or_shared(c), darkshadow,
+                                [&](int i, int k, const detail::answer & a, size_t r, int cc) { a.put_ragged(levels[(size_t)live[(size_t)i]][(size_t)k], r, cc); });
 }
 
 // Lineq::calcBound (linsys.cpp:1047-1078) for many systems: limits[k][j] receives the bounds of variable j of *systems[k]
@@ -739,49 +758,30 @@ inline int calc_bound_all(const std::vector<RMatT *> & systems, const std::vecto
     if ((int)rhs_idx.size() != nb) return XPG_ERR_SHAPE;
     limits.assign((size_t)nb, std::vector<RMatT>());
     ok.assign((size_t)nb, 0);
-    xpg_ctx * h = c ? c : detail::shared_context();
-    std::vector<char> done((size_t)nb, 0);
-    for (int b0 = 0; b0 < nb; b0++) {
-        if (done[(size_t)b0]) continue;
-        const int rows = (int)systems[(size_t)b0]->get_row_size(), cols = (int)systems[(size_t)b0]->get_col_size(), nv = rhs_idx[(size_t)b0];
-        std::vector<int> cls;
-        for (int b = b0; b < nb; b++)
-            if (!done[(size_t)b] && (int)systems[(size_t)b]->get_row_size() == rows && (int)systems[(size_t)b]->get_col_size() == cols && rhs_idx[(size_t)b] == nv) {
-                cls.push_back(b); done[(size_t)b] = 1;
-            }
-        if (rows == 0 || cols == 0 || nv < 1 || nv >= cols) return XPG_ERR_SHAPE;
-        const int nc = (int)cls.size();
-        std::vector<xpg_rat32> flat((size_t)nc * rows * cols);
-        for (int k = 0; k < nc; k++)
-            std::memcpy((void *)(flat.data() + (size_t)k * rows * cols), (const void *)systems[(size_t)cls[(size_t)k]]->get_matrix(), sizeof(xpg_rat32) * (size_t)rows * cols);
-        int cap = 4 * rows + 16;
-        bool answered = false;
-        for (int attempt = 0; attempt < 3 && !answered; attempt++) {
-            std::vector<long long> off((size_t)nc * nv + 1, 0);
-            std::vector<int32_t> kok((size_t)nc, 0), kchain((size_t)nc, 0), ksteps((size_t)nc, 0);
-            const xpg_rat32 * view = 0;
-            const int rc = xpg_lineq_bounds_batch_packed_rat32(h, nc, flat.data(), rows, cols, nv, cap, 0, (xpg_rat32 *)0, 0, &view, off.data(),
-                                                               kok.data(), kchain.data(), ksteps.data());
-            if (rc != 0) return rc;
-            int need = 0;
-            for (int k = 0; k < nc; k++) if (kok[(size_t)k] < 0 && -kok[(size_t)k] > need) need = -kok[(size_t)k];
-            if (need) { cap = need; continue; }                     // a step needed more rows than cap: once more with that many
-            for (int k = 0; k < nc; k++) {
-                const int b = cls[(size_t)k];
-                ok[(size_t)b] = kok[(size_t)k];
-                limits[(size_t)b].resize((size_t)nv);
-                for (int j = 0; j < nv; j++) {
-                    const long long lo = off[(size_t)k * nv + j], hi = off[(size_t)k * nv + j + 1];
-                    RMatT & m = limits[(size_t)b][(size_t)j];
-                    m.reinit((unsigned)(hi - lo), (unsigned)cols);
-                    if (hi > lo) std::memcpy((void *)m.get_matrix(), (const void *)(view + (size_t)lo * cols), sizeof(xpg_rat32) * (size_t)(hi - lo) * cols);
+    xpg_ctx * h = detail::ctx_or_shared(c);
+    std::vector<int> all((size_t)nb);
+    for (int b = 0; b < nb; b++) all[(size_t)b] = b;
+    return detail::for_each_class(all, [&](int b) { return detail::shape_of(systems, b, rhs_idx[(size_t)b]); }, [&](const std::vector<int> & cls) {
+        const int nc = (int)cls.size(), nv = rhs_idx[(size_t)cls[0]];
+        const int rows = (int)systems[(size_t)cls[0]]->get_row_size(), cols = (int)systems[(size_t)cls[0]]->get_col_size();
+        if (rows == 0 || cols == 0 || nv < 1 || nv >= cols) return (int)XPG_ERR_SHAPE;
+        const detail::shape_known shape = { rows, cols };
+        const detail::packed p = detail::pack(systems, cls, shape);
+        const detail::retry_rule how = { { detail::bound_default(rows), 0, 0 }, { 0, 0, 0 }, detail::one_capacity, false, 3 };
+        return detail::call_until_answered(how, (size_t)nc, (size_t)nc * nv,
+            [&](const detail::caps & cp, detail::answer & a) {
+                return xpg_lineq_bounds_batch_packed_rat32(h, nc, p.flat.data(), rows, cols, nv, cp.cap, cp.out, (xpg_rat32 *)0, 0, &a.view, a.off,
+                                                           a.ok, a.chain, a.steps);
+            },
+            [&](const detail::answer & a) {
+                for (int k = 0; k < nc; k++) {
+                    std::vector<RMatT> & lim = limits[(size_t)cls[(size_t)k]];
+                    ok[(size_t)cls[(size_t)k]] = a.ok[(size_t)k];
+                    lim.resize((size_t)nv);
+                    for (int j = 0; j < nv; j++) a.put_packed(lim[(size_t)j], (size_t)k * nv + j, cols);
                 }
-            }
-            answered = true;
-        }
-        if (!answered) return XPG_ERR_UNSUPPORTED;
-    }
-    return 0;
+            });
+    });
 }
 
 // calc_bound_all for systems of MIXED shapes in ONE call: the same arguments, limits and ok, but every system -- whatever its
@@ -799,54 +799,29 @@ inline int calc_bound_each(const std::vector<RMatT *> & systems, const std::vect
     limits.assign((size_t)nb, std::vector<RMatT>());
     ok.assign((size_t)nb, 0);
     if (nb == 0) return 0;
-    xpg_ctx * h = c ? c : detail::shared_context();
-    std::vector<int32_t> rows((size_t)nb), cols((size_t)nb);
-    std::vector<long long> off((size_t)nb + 1, 0);
+    xpg_ctx * h = detail::ctx_or_shared(c);
+    const detail::packed p = detail::pack(nb, [&](int b) { return (const RMatT *)systems[(size_t)b]; }, detail::shape_as_is());
     std::vector<int> first((size_t)nb + 1, 0);
-    int most = 0;
     for (int b = 0; b < nb; b++) {
-        rows[(size_t)b] = (int32_t)systems[(size_t)b]->get_row_size(); cols[(size_t)b] = (int32_t)systems[(size_t)b]->get_col_size();
         const int nv = rhs_idx[(size_t)b];
-        if (rows[(size_t)b] == 0 || cols[(size_t)b] == 0 || nv < 1 || nv >= cols[(size_t)b]) return XPG_ERR_SHAPE;
-        off[(size_t)b + 1] = off[(size_t)b] + (long long)rows[(size_t)b] * cols[(size_t)b];
+        if (p.rows[(size_t)b] == 0 || p.cols[(size_t)b] == 0 || nv < 1 || nv >= p.cols[(size_t)b]) return XPG_ERR_SHAPE;
         first[(size_t)b + 1] = first[(size_t)b] + nv;
-        if (rows[(size_t)b] > most) most = rows[(size_t)b];
     }
-    std::vector<xpg_rat32> flat((size_t)off[(size_t)nb]);
-    for (int b = 0; b < nb; b++)
-        std::memcpy((void *)(flat.data() + off[(size_t)b]), (const void *)systems[(size_t)b]->get_matrix(),
-                    sizeof(xpg_rat32) * (size_t)rows[(size_t)b] * cols[(size_t)b]);
-    const int nres = first[(size_t)nb];
-    int cap = 4 * most + 16, cap_out = cap;                         // the library's defaults, spelled out
-    for (int attempt = 0; attempt < 3; attempt++) {
-        std::vector<long long> ooff((size_t)nres + 1, 0);
-        std::vector<int32_t> orows((size_t)nres, 0), kok((size_t)nb, 0), kchain((size_t)nb, 0), ksteps((size_t)nb, 0);
-        const xpg_rat32 * view = 0;
-        const int rc = xpg_lineq_bounds_batch_ragged_rat32(h, nb, flat.data(), rows.data(), cols.data(), off.data(), rhs_idx.data(), cap, cap_out,
-                                                           (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), kchain.data(),
-                                                           ksteps.data());
-        if (rc != 0) return rc;
-        int need_cap = 0, need_out = 0;
-        for (int b = 0; b < nb; b++) {
-            const int need = -kok[(size_t)b];
-            if (need > cap) { if (need > need_cap) need_cap = need; }
-            else if (need > need_out) need_out = need;              // (need <= 0: the system was answered)
-        }
-        if (need_cap) { cap = need_cap; cap_out = cap; }            // (a result's slot takes cap, as in calc_bound_all)
-        else if (need_out) cap_out = need_out;
-        if (need_cap || need_out) continue;
-        for (int b = 0; b < nb; b++) {
-            const int nv = rhs_idx[(size_t)b];
-            ok[(size_t)b] = kok[(size_t)b];
-            limits[(size_t)b].resize((size_t)nv);
-            for (int j = 0; j < nv; j++) {
-                const int r = first[(size_t)b] + j;
-                detail::put_cells(limits[(size_t)b][(size_t)j], view ? view + ooff[(size_t)r] : view, (int)orows[(size_t)r], (int)cols[(size_t)b]);
+    const int nres = first[(size_t)nb], cap = detail::bound_default(p.most);
+    const detail::retry_rule how = { { cap, cap, 0 }, { 0, 0, 0 }, detail::slot_follows, false, 3 };   // the library's defaults, spelled out; a result's slot takes cap, as in calc_bound_all
+    return detail::call_until_answered(how, (size_t)nb, (size_t)nres,
+        [&](const detail::caps & cp, detail::answer & a) {
+            return xpg_lineq_bounds_batch_ragged_rat32(h, nb, p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(), rhs_idx.data(), cp.cap, cp.out,
+                                                       (xpg_rat32 *)0, 0, &a.view, a.off, a.rows, a.ok, a.chain, a.steps);
+        },
+        [&](const detail::answer & a) {
+            for (int b = 0; b < nb; b++) {
+                const int nv = rhs_idx[(size_t)b];
+                ok[(size_t)b] = a.ok[(size_t)b];
+                limits[(size_t)b].resize((size_t)nv);
+                for (int j = 0; j < nv; j++) a.put_ragged(limits[(size_t)b][(size_t)j], (size_t)(first[(size_t)b] + j), (int)p.cols[(size_t)b]);
             }
-        }
-        return 0;
-    }
-    return XPG_ERR_UNSUPPORTED;
+        });
 }
 
 namespace detail {
@@ -865,19 +840,15 @@ inline int hull_groups(const std::vector<std::vector<RMatT *> > & groups, const 
     ok.assign((size_t)ng, 0);
     if (member) member->assign((size_t)ng, -1);
     if (ng == 0) return 0;
-    xpg_ctx * h = c ? c : shared_context();
-    std::vector<int32_t> goff((size_t)ng + 1, 0), rows, cols, rhs, elim, eoff(1, 0);
-    std::vector<long long> off(1, 0);
-    int most = 0;
+    xpg_ctx * h = ctx_or_shared(c);
+    std::vector<const RMatT *> all;                                 // the members of every group, in group order
+    std::vector<int32_t> goff((size_t)ng + 1, 0), rhs, elim, eoff(1, 0);
     for (int g = 0; g < ng; g++) {
         const std::vector<RMatT *> & grp = groups[(size_t)g];
         if (elims && (*elims)[(size_t)g].size() != grp.size()) return XPG_ERR_SHAPE;
         for (size_t i = 0; i < grp.size(); i++) {
-            const int r = grp[i]->size() == 0 ? 0 : (int)grp[i]->get_row_size(), cc = (int)grp[i]->get_col_size();
-            if (r == 0 || cc == 0) return XPG_ERR_SHAPE;
-            rows.push_back(r); cols.push_back(cc); rhs.push_back(rhs_idx[(size_t)g]);
-            off.push_back(off.back() + (long long)r * cc);
-            if (r > most) most = r;
+            if (grp[i]->get_row_size() == 0 || grp[i]->get_col_size() == 0) return XPG_ERR_SHAPE;
+            all.push_back(grp[i]); rhs.push_back(rhs_idx[(size_t)g]);
             if (elims) {
                 const std::vector<int32_t> & e = (*elims)[(size_t)g][i];
                 elim.insert(elim.end(), e.begin(), e.end());
@@ -887,47 +858,29 @@ inline int hull_groups(const std::vector<std::vector<RMatT *> > & groups, const 
         goff[(size_t)g + 1] = goff[(size_t)g] + (int32_t)grp.size();
     }
     const int nb = goff[(size_t)ng];
-    std::vector<xpg_rat32> flat((size_t)off.back() + 1);
-    for (int g = 0, b = 0; g < ng; g++)
-        for (size_t i = 0; i < groups[(size_t)g].size(); i++, b++)
-            std::memcpy((void *)(flat.data() + off[(size_t)b]), (const void *)groups[(size_t)g][i]->get_matrix(),
-                        sizeof(xpg_rat32) * (size_t)rows[(size_t)b] * cols[(size_t)b]);
+    const packed p = pack(nb, [&](int b) { return all[(size_t)b]; }, shape_as_is());
     if (elim.empty()) elim.push_back(0);
-    int cap = elims ? most * most / 4 + most + 1 : 4 * most + 16, cap_out = cap, cap_hull = 0;   // the library's defaults, spelled out
-    for (int attempt = 0; attempt < 3; attempt++) {
-        std::vector<long long> ooff((size_t)ng + 1, 0);
-        std::vector<int32_t> orows((size_t)ng, 0), kok((size_t)ng, 0), kmem((size_t)ng, 0), kchain((size_t)ng, 0), ksteps((size_t)ng, 0);
-        const xpg_rat32 * view = 0;
-        const int rc = elims
-            ? xpg_lineq_project_union_batch_ragged_rat32(h, ng, goff.data(), nb, flat.data(), rows.data(), cols.data(), off.data(), rhs.data(),
-                                                         elim.data(), eoff.data(), darkshadow ? 1 : 0, is_intersect ? 1 : 0, cap, cap_out, cap_hull,
-                                                         (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(), kok.data(), kmem.data(), kchain.data(),
-                                                         ksteps.data())
-            : xpg_lineq_hull_batch_ragged_rat32(h, ng, goff.data(), nb, flat.data(), rows.data(), cols.data(), off.data(), rhs.data(),
-                                                is_intersect ? 1 : 0, cap, cap_out, cap_hull, (xpg_rat32 *)0, 0, &view, ooff.data(), orows.data(),
-                                                kok.data(), kmem.data(), kchain.data(), ksteps.data());
-        if (rc != 0) return rc;
-        int need_cap = 0, need_out = 0, need_hull = 0;
-        for (int g = 0; g < ng; g++) {
-            const int need = -kok[(size_t)g];
-            if (need <= 0) continue;                                // the group was answered
-            if (kmem[(size_t)g] < 0) { if (need > need_hull) need_hull = need; }
-            else if (need > cap) { if (need > need_cap) need_cap = need; }
-            else if (need > need_out) need_out = need;
-        }
-        if (need_cap) { cap = need_cap; cap_out = cap; }
-        else if (need_out) cap_out = need_out;
-        if (need_hull) cap_hull = need_hull;
-        if (need_cap || need_out || need_hull) continue;
-        for (int g = 0; g < ng; g++) {
-            ok[(size_t)g] = kok[(size_t)g];
-            if (member) (*member)[(size_t)g] = kmem[(size_t)g];
-            if (orows[(size_t)g] > 0) put_cells(results[(size_t)g], view + ooff[(size_t)g], (int)orows[(size_t)g], (int)cols[(size_t)goff[(size_t)g]]);
-            else results[(size_t)g].clean();
-        }
-        return 0;
-    }
-    return XPG_ERR_UNSUPPORTED;
+    const int cap = elims ? chain_default(p.most) : bound_default(p.most);
+    const retry_rule how = { { cap, cap, 0 }, { 0, 0, 0 }, slot_follows, true, 3 };   // the library's defaults, spelled out
+    return call_until_answered(how, (size_t)ng, (size_t)ng,
+        [&](const caps & cp, answer & a) {
+            return elims
+                ? xpg_lineq_project_union_batch_ragged_rat32(h, ng, goff.data(), nb, p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(), rhs.data(),
+                                                             elim.data(), eoff.data(), darkshadow ? 1 : 0, is_intersect ? 1 : 0, cp.cap, cp.out, cp.hull,
+                                                             (xpg_rat32 *)0, 0, &a.view, a.off, a.rows, a.ok, a.member,
+                                                             a.chain, a.steps)
+                : xpg_lineq_hull_batch_ragged_rat32(h, ng, goff.data(), nb, p.flat.data(), p.rows.data(), p.cols.data(), p.off.data(), rhs.data(),
+                                                    is_intersect ? 1 : 0, cp.cap, cp.out, cp.hull, (xpg_rat32 *)0, 0, &a.view, a.off, a.rows,
+                                                    a.ok, a.member, a.chain, a.steps);
+        },
+        [&](const answer & a) {
+            for (int g = 0; g < ng; g++) {
+                ok[(size_t)g] = a.ok[(size_t)g];
+                if (member) (*member)[(size_t)g] = a.member[(size_t)g];
+                if (a.rows[(size_t)g] > 0) a.put_ragged(results[(size_t)g], (size_t)g, (int)p.cols[(size_t)goff[(size_t)g]]);
+                else results[(size_t)g].clean();
+            }
+        });
 }
 } // namespace detail
 
