@@ -70,14 +70,14 @@ def lib():
             raise XpgError(
                 "%s is missing: build it with `python -m xpoly_amd.build` (hipcc, gfx950). "
                 "xpoly_amd has no CPU fallback." % SO_PATH)
-        _lib = C.CDLL(SO_PATH)
-        _lib.xpg_last_error.restype = C.c_char_p
-        _lib.xpg_version.restype = C.c_char_p
-        _lib.xpg_stream.restype = C.c_void_p
-        for name in SYMBOLS:
-            fn = getattr(_lib, name)
-            if fn.restype is C.c_int:
-                fn.restype = C.c_int
+        so = C.CDLL(SO_PATH)
+        missing = [name for name in SYMBOLS if not hasattr(so, name)]
+        if missing:                                         # a stale build: say which symbols, not an AttributeError mid-call
+            raise XpgError("%s lacks %s: rebuild it with `python -m xpoly_amd.build`" % (SO_PATH, ", ".join(missing)))
+        so.xpg_last_error.restype = C.c_char_p
+        so.xpg_version.restype = C.c_char_p
+        so.xpg_stream.restype = C.c_void_p
+        _lib = so
     return _lib
 
 

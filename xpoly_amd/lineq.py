@@ -4,11 +4,12 @@ call takes a stack of equally shaped systems [nb, rows, cols, 2] (int32 num/den)
 and runs one wavefront per system on the GPU.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
 from ._capi import lib, vp
-from .six import RAT, as_kind
+from .six import RAT, _view, as_kind, ragged_systems
 
 
 def _stack(mats):
@@ -23,6 +24,49 @@ def _stack(mats):
     return np.ascontiguousarray(a)
 
 
+def _rows_down(view, total, cell, copy):
+    """The `total` rows a packed call left behind its view pointer, as an int32 array [total, *cell] -- cell (cols, 2) for rows of
+    one width, (2,) for cells of mixed widths. The one place that reads the handle's pinned buffer. That buffer is the handle's:
+    its next packed call writes it again. copy=True takes the rows out before that can happen; copy=False hands out a view that
+    is valid only until then (what a C++ caller reads its results from). No rows: always an owned, empty array, never a view of a
+    pointer the library may not have set."""
+    shape = (total,) + cell
+    if total and not copy:
+        return np.frombuffer((C.c_int32 * math.prod(shape)).from_address(view.value), dtype=np.int32).reshape(shape)
+    rows = np.empty(shape, dtype=np.int32)
+    if total:
+        C.memmove(rows.ctypes.data, view.value, rows.nbytes)
+    return rows
+
+
+def _cut(packed, off, widths=None):
+    """[result r] of a packed readout: rows off[r] .. off[r + 1], or with widths (ragged) those cells as rows of widths[r] columns
+    (a width of 0: a result of no rows and no columns)."""
+    o = off.tolist()
+    if widths is None:
+        return [packed[a: b] for a, b in zip(o, o[1:])]
+    return [packed[a: b].reshape((b - a) // w if w else 0, w, 2) for a, b, w in zip(o, o[1:], widths)]
+
+
+def _nest(results, first):
+    """[[the results first[b] .. first[b + 1] of system b]]"""
+    return [results[a: b] for a, b in zip(first, first[1:])]
+
+
+def _every(n, nb):
+    """first[] of nb systems with n results each (n may be 0)"""
+    return [b * n for b in range(nb + 1)]
+
+
+def _flat_lists(lists):
+    """Elimination lists as the ragged entry points take them: (all entries in one int32 array, offsets[len(lists) + 1]).
+    Without any entry the array is one zero: the library is never handed a pointer to nothing."""
+    lists = [np.asarray(e, dtype=np.int32).reshape(-1) for e in lists]
+    eoff = np.zeros(len(lists) + 1, dtype=np.int32)
+    eoff[1:] = np.cumsum([e.size for e in lists])
+    return np.ascontiguousarray(np.concatenate(lists)) if int(eoff[-1]) else np.zeros(1, dtype=np.int32), eoff
+
+
 class Lineq:
     def __init__(self, ctx):
         self.ctx = ctx
@@ -31,7 +75,7 @@ class Lineq:
         """Lineq::reduce (linsys.cpp:359-626). Returns (ok[nb], [system b's surviving rows]) -- through the packed entry
         point; the rows are slices of one array."""
         ok, off, packed = self.reduce_packed(mats, rhs_idx, is_intersect)
-        return ok, [packed[off[b]: off[b + 1]] for b in range(len(ok))]
+        return ok, _cut(packed, off)
 
     def reduce_packed(self, mats, rhs_idx, is_intersect=True, copy=True):
         """xpg_lineq_reduce_batch_packed_rat32: (ok[nb], row_offsets[nb + 1], rows[row_offsets[nb], cols, 2]); the input is
@@ -44,14 +88,7 @@ class Lineq:
         self.ctx.check(lib().xpg_lineq_reduce_batch_packed_rat32(
             self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), C.c_int(int(is_intersect)),
             None, C.c_longlong(0), C.byref(view), vp(off), None, vp(ok)), "xpg_lineq_reduce_batch_packed_rat32")
-        total = int(off[nb])
-        if not copy and total:
-            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
-            return ok, off, np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
-        packed = np.empty((total, cols, 2), dtype=np.int32)
-        if total:
-            C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        return ok, off, packed
+        return ok, off, _rows_down(view, int(off[nb]), (cols, 2), copy)
 
     def reduce_inplace(self, mats, rhs_idx, is_intersect=True):
         """xpg_lineq_reduce_batch_rat32, the in-place form of the reference's signature: `mats` [nb, rows, cols, 2] (int32,
@@ -101,7 +138,7 @@ class Lineq:
                 raise ValueError("fme result needs %d rows, cap_rows is %d" % (-out_rows.min(), cap))
             return ok, [outs[b, : out_rows[b]].copy() for b in range(nb)]
         ok, off, packed = self.fme_packed(a, rhs_idx, u, darkshadow, cap_rows)
-        return ok, [packed[off[b]: off[b + 1]] for b in range(nb)]
+        return ok, _cut(packed, off)
 
     def fme_packed(self, mats, rhs_idx, u, darkshadow=False, cap_rows=None, copy=True):
         """xpg_lineq_fme_batch_packed_rat32: (ok[nb], row_offsets[nb + 1], rows[row_offsets[nb], cols, 2]).
@@ -115,14 +152,26 @@ class Lineq:
             self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), C.c_int(u),
             C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), None, C.c_longlong(0), C.byref(view), vp(off), vp(ok)),
             "xpg_lineq_fme_batch_packed_rat32")
-        total = int(off[nb])
-        if not copy and total:
-            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
-            return ok, off, np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
-        packed = np.empty((total, cols, 2), dtype=np.int32)
-        if total:                                           # out of the handle's pinned buffer, before the next call reuses it
-            C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        return ok, off, packed
+        return ok, off, _rows_down(view, int(off[nb]), (cols, 2), copy)
+
+    def _chain_packed(self, levels, mats, rhs_idx, elim, darkshadow, cap_rows, cap_out_rows, copy):
+        """xpg_lineq_{project,levels}_batch_packed_rat32: (ok[nb], steps[nb], results) with one result per system, or (levels)
+        one per system and list entry -- level k of system b at b * len(elim) + k."""
+        a = _stack(mats)
+        nb, rows, cols = a.shape[:3]
+        el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
+        n = int(el.size)
+        off = np.zeros((nb * n if levels else nb) + 1, dtype=np.int64); ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
+        if nb == 0:
+            return ok, steps, []
+        name = "xpg_lineq_%s_batch_packed_rat32" % ("levels" if levels else "project")
+        view = C.c_void_p()
+        self.ctx.check(getattr(lib(), name)(
+            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), vp(el), C.c_int(n),
+            C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view),
+            vp(off), vp(ok), vp(steps)), name)
+        res = _cut(_rows_down(view, int(off[-1]), (cols, 2), copy), off)
+        return ok, steps, _nest(res, _every(n, nb)) if levels else res
 
     def project_packed(self, mats, rhs_idx, elim, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
         """xpg_lineq_project_batch_packed_rat32: the variables of `elim` eliminated one after the other (each Lineq::fme's result
@@ -130,35 +179,14 @@ class Lineq:
         with the step that found the system inconsistent, or -need with the step that needs `need` rows (steps == len(elim):
         the final result against cap_out_rows); a system with ok <= 0 has no rows. copy=False: the rows are views of the
         handle's pinned buffer, valid until the next packed call on this handle."""
-        a = _stack(mats)
-        nb, rows, cols = a.shape[:3]
-        el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
-        off = np.zeros(nb + 1, dtype=np.int64); ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
-        if nb == 0:
-            return ok, steps, []
-        view = C.c_void_p()
-        self.ctx.check(lib().xpg_lineq_project_batch_packed_rat32(
-            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), vp(el), C.c_int(el.size),
-            C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view),
-            vp(off), vp(ok), vp(steps)), "xpg_lineq_project_batch_packed_rat32")
-        total = int(off[nb])
-        if not copy and total:
-            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
-        else:
-            packed = np.empty((total, cols, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        return ok, steps, [packed[off[b]: off[b + 1]] for b in range(nb)]
+        return self._chain_packed(False, mats, rhs_idx, elim, darkshadow, cap_rows, cap_out_rows, copy)
+
+    PROJECT_ROUTE_KEYS = ("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes")
 
     @staticmethod
     def project_last_route():
         """xpg_lineq_project_last_route of the calling thread's last projection call, as a dict."""
-        out = np.zeros(6, dtype=np.int64)
-        rc = lib().xpg_lineq_project_last_route(vp(out), C.c_int(6))
-        if rc != 0:
-            raise ValueError("xpg_lineq_project_last_route: %d" % rc)
-        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes"), (int(x) for x in out)))
+        return _view("xpg_lineq_project_last_route", Lineq.PROJECT_ROUTE_KEYS)
 
     def levels_packed(self, mats, rhs_idx, elim, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
         """xpg_lineq_levels_batch_packed_rat32: the projection that keeps every level -- the variables of `elim` eliminated one
@@ -167,55 +195,24 @@ class Lineq:
         len(elim), 0 with the step that found the system inconsistent, or -need with the step k concerned -- need > cap_rows:
         step k's unreduced result needs `need` rows; else level k has `need` > cap_out_rows rows. A system with ok <= 0 has no
         rows at any level. copy=False: the levels are views of the handle's pinned buffer, valid until the next packed call."""
-        a = _stack(mats)
-        nb, rows, cols = a.shape[:3]
-        el = np.ascontiguousarray(elim, dtype=np.int32).reshape(-1)
-        n = int(el.size)
-        off = np.zeros(nb * n + 1, dtype=np.int64); ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
-        if nb == 0:
-            return ok, steps, []
-        view = C.c_void_p()
-        self.ctx.check(lib().xpg_lineq_levels_batch_packed_rat32(
-            self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), vp(el), C.c_int(n),
-            C.c_int(int(darkshadow)), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view),
-            vp(off), vp(ok), vp(steps)), "xpg_lineq_levels_batch_packed_rat32")
-        total = int(off[-1])
-        if not copy and total:
-            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
-        else:
-            packed = np.empty((total, cols, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        o = off.tolist()
-        return ok, steps, [[packed[o[b * n + k]: o[b * n + k + 1]] for k in range(n)] for b in range(nb)]
+        return self._chain_packed(True, mats, rhs_idx, elim, darkshadow, cap_rows, cap_out_rows, copy)
 
     @staticmethod
     def levels_last_route():
         """xpg_lineq_levels_last_route of the calling thread's last levels call, as a dict."""
-        out = np.zeros(7, dtype=np.int64)
-        rc = lib().xpg_lineq_levels_last_route(vp(out), C.c_int(7))
-        if rc != 0:
-            raise ValueError("xpg_lineq_levels_last_route: %d" % rc)
-        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "level_bytes"), (int(x) for x in out)))
+        return _view("xpg_lineq_levels_last_route", Lineq.PROJECT_ROUTE_KEYS + ("level_bytes",))
 
     def _chain_ragged(self, levels, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy):
         """xpg_lineq_{project,levels}_batch_ragged_rat32: (ok[nb], steps[nb], results) with results[r] the rows of result r --
         one per system, or (levels) one per list entry, level k of system b at elim_offsets[b] + k -- and the offsets of the
         lists. The rows are cols[b] wide."""
-        from .six import _ragged_pack
-        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
-        nb = len(parts)
-        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+        flat, rows, cols, off, rhs = ragged_systems(mats_list, rhs_idx)
+        nb = len(rows)
         if elims is None:                                   # loop-nest limits: rhs_idx - 1 .. 1 of each system
             elims = [list(range(int(r) - 1, 0, -1)) for r in (rhs if rhs is not None else cols - 1)]
         if len(elims) != nb or (rhs is not None and rhs.size != nb):
             raise ValueError("one list and one rhs_idx per system: %d systems, %d lists" % (nb, len(elims)))
-        lists = [np.asarray(e, dtype=np.int32).reshape(-1) for e in elims]
-        eoff = np.zeros(nb + 1, dtype=np.int32)
-        eoff[1:] = np.cumsum([e.size for e in lists])
-        el = np.ascontiguousarray(np.concatenate(lists)) if nb and int(eoff[nb]) else np.zeros(1, dtype=np.int32)
+        el, eoff = _flat_lists(elims)
         nres = int(eoff[nb]) if levels else nb
         ooff = np.zeros(nres + 1, dtype=np.int64); orows = np.zeros(max(nres, 1), dtype=np.int32)
         ok = np.zeros(nb, dtype=np.int32); steps = np.zeros(nb, dtype=np.int32)
@@ -227,17 +224,8 @@ class Lineq:
             self.ctx._h, C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs), vp(el), vp(eoff), C.c_int(int(darkshadow)),
             C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view), vp(ooff), vp(orows), vp(ok),
             vp(steps)), name)
-        total = int(ooff[nres])
-        if not copy and total:
-            buf = (C.c_int32 * (total * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
-        else:
-            packed = np.empty((total, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        o = ooff.tolist()
         width = np.repeat(cols, np.diff(eoff)).tolist() if levels else cols.tolist()
-        return ok, steps, [packed[o[r]: o[r + 1]].reshape(-1, width[r], 2) for r in range(nres)], eoff
+        return ok, steps, _cut(_rows_down(view, int(ooff[nres]), (2,), copy), ooff, width), eoff
 
     def project_ragged(self, mats_list, rhs_idx, elims, darkshadow=False, cap_rows=None, cap_out_rows=None, copy=True):
         """xpg_lineq_project_batch_ragged_rat32: Lineq.project_packed for systems of DIFFERENT shapes, each with its own
@@ -253,25 +241,17 @@ class Lineq:
         LoopTran::transformIterSpace runs it. Returns (ok[nb], steps[nb], levels) with levels[b][k] the rows of system b once
         elims[b][0 .. k] are eliminated, and levels_packed's verdicts."""
         ok, steps, res, eoff = self._chain_ragged(True, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy)
-        e = eoff.tolist()
-        return ok, steps, [res[e[b]: e[b + 1]] for b in range(len(ok))]
+        return ok, steps, _nest(res, eoff.tolist())
 
     @staticmethod
     def ragged_last_route():
         """xpg_lineq_ragged_last_route of the calling thread's last project_ragged / levels_ragged call, as a dict."""
-        out = np.zeros(7, dtype=np.int64)
-        rc = lib().xpg_lineq_ragged_last_route(vp(out), C.c_int(7))
-        if rc != 0:
-            raise ValueError("xpg_lineq_ragged_last_route: %d" % rc)
-        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "out_bytes"), (int(x) for x in out)))
+        return _view("xpg_lineq_ragged_last_route", Lineq.PROJECT_ROUTE_KEYS + ("out_bytes",))
 
     def reduce_ragged(self, mats_list, rhs_idx=None, is_intersect=True):
         """Lineq::reduce on systems of different shapes in one call: (ok[nb], [system b's surviving rows])."""
-        from .six import _ragged_pack
-        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
-        nb = len(parts)
-        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32)
+        flat, rows, cols, off, rhs = ragged_systems(mats_list, rhs_idx)
+        nb = len(rows)
         out_rows = np.zeros(nb, dtype=np.int32); ok = np.zeros(nb, dtype=np.int32)
         self.ctx.check(lib().xpg_lineq_reduce_batch_ragged_rat32(self.ctx._h, C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off),
                                                                  vp(rhs), C.c_int(int(is_intersect)), vp(out_rows), vp(ok)),
@@ -283,11 +263,8 @@ class Lineq:
 
     def fme_ragged(self, mats_list, u, rhs_idx=None, darkshadow=False):
         """Lineq::fme on systems of different shapes, eliminating variable u[b] of system b: (ok[nb], [result b])."""
-        from .six import _ragged_pack
-        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
-        nb = len(parts)
-        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32)
+        flat, rows, cols, off, rhs = ragged_systems(mats_list, rhs_idx)
+        nb = len(rows)
         uu = np.ascontiguousarray(u, dtype=np.int32)
         out_rows = np.zeros(nb, dtype=np.int32); ok = np.zeros(nb, dtype=np.int32); ooff = np.zeros(nb + 1, dtype=np.int64)
         # ONE call where the worst case is small: the entry point computes every elimination before it looks at the output
@@ -342,11 +319,8 @@ class Lineq:
                                                                      C.c_int(rhs_idx), C.c_int(cap_rows or 0), None, C.c_longlong(0),
                                                                      C.byref(view), vp(off), vp(ok)),
                        "xpg_lineq_calc_bound_batch_packed_rat32")
-        total = int(off[-1])
-        packed = np.zeros((total, cols, 2), dtype=np.int32)
-        if total:                                           # out of the handle's pinned buffer, before the next call reuses it
-            C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        return ok, [[packed[int(off[b * rhs_idx + j]): int(off[b * rhs_idx + j + 1])].copy() for j in range(rhs_idx)] for b in range(nb)]
+        res = [r.copy() for r in _cut(_rows_down(view, int(off[-1]), (cols, 2), True), off)]
+        return ok, _nest(res, _every(rhs_idx, nb))
 
     def bounds_packed(self, mats, rhs_idx, cap_rows=0, cap_out_rows=0, copy=True):
         """xpg_lineq_bounds_batch_packed_rat32: Lineq::calcBound for every system in one launch. Returns (ok[nb], chain[nb],
@@ -366,25 +340,13 @@ class Lineq:
             self.ctx._h, C.c_int(nb), vp(a), C.c_int(rows), C.c_int(cols), C.c_int(rhs_idx), C.c_int(cap_rows or 0),
             C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view), vp(off), vp(ok), vp(chain), vp(steps)),
             "xpg_lineq_bounds_batch_packed_rat32")
-        total = int(off[-1])
-        if not copy and total:
-            buf = (C.c_int32 * (total * cols * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, cols, 2)
-        else:
-            packed = np.empty((total, cols, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        o = off.tolist()
-        return ok, chain, steps, [[packed[o[b * rhs_idx + j]: o[b * rhs_idx + j + 1]] for j in range(rhs_idx)] for b in range(nb)]
+        res = _cut(_rows_down(view, int(off[-1]), (cols, 2), copy), off)
+        return ok, chain, steps, _nest(res, _every(rhs_idx, nb))
 
     @staticmethod
     def bounds_last_route():
         """xpg_lineq_bounds_last_route of the calling thread's last fused calcBound call, as a dict."""
-        out = np.zeros(7, dtype=np.int64)
-        rc = lib().xpg_lineq_bounds_last_route(vp(out), C.c_int(7))
-        if rc != 0:
-            raise ValueError("xpg_lineq_bounds_last_route: %d" % rc)
-        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "steps"), (int(x) for x in out)))
+        return _view("xpg_lineq_bounds_last_route", Lineq.PROJECT_ROUTE_KEYS + ("steps",))
 
     def bounds_ragged(self, mats_list, rhs_idx=None, cap_rows=None, cap_out_rows=None, copy=True):
         """xpg_lineq_bounds_batch_ragged_rat32: Lineq.bounds_packed for systems of DIFFERENT shapes, each with its own rhs_idx[b]
@@ -392,11 +354,8 @@ class Lineq:
         steps[nb], bounds) with bounds[b][j] the rows x cols[b] x 2 bounds of variable j of system b and bounds_packed's verdicts;
         the capacities are the call's -- cap_rows defaults to 4 * (most rows) + 16. copy=False: views of the handle's pinned
         buffer, valid until the next packed call on this handle."""
-        from .six import _ragged_pack
-        flat, off, parts = _ragged_pack(mats_list, RAT, 2)
-        nb = len(parts)
-        rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-        rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+        flat, rows, cols, off, rhs = ragged_systems(mats_list, rhs_idx)
+        nb = len(rows)
         if rhs is not None and rhs.size != nb:
             raise ValueError("one rhs_idx per system: %d systems, %d rhs_idx" % (nb, rhs.size))
         first = np.zeros(nb + 1, dtype=np.int64)
@@ -411,29 +370,16 @@ class Lineq:
             self.ctx._h, C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs), C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0),
             None, C.c_longlong(0), C.byref(view), vp(ooff), vp(orows), vp(ok), vp(chain), vp(steps)),
             "xpg_lineq_bounds_batch_ragged_rat32")
-        total = int(ooff[nres])
-        if not copy and total:
-            buf = (C.c_int32 * (total * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
-        else:
-            packed = np.empty((total, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        o = ooff.tolist(); f = first.tolist(); w = cols.tolist()
-        return ok, chain, steps, [[packed[o[r]: o[r + 1]].reshape(-1, w[b], 2) for r in range(f[b], f[b + 1])] for b in range(nb)]
+        width = np.repeat(cols, np.diff(first)).tolist()
+        return ok, chain, steps, _nest(_cut(_rows_down(view, int(ooff[nres]), (2,), copy), ooff, width), first.tolist())
 
     @staticmethod
     def bounds_ragged_last_route():
         """xpg_lineq_bounds_ragged_last_route of the calling thread's last bounds_ragged call, as a dict."""
-        out = np.zeros(8, dtype=np.int64)
-        rc = lib().xpg_lineq_bounds_ragged_last_route(vp(out), C.c_int(8))
-        if rc != 0:
-            raise ValueError("xpg_lineq_bounds_ragged_last_route: %d" % rc)
-        return dict(zip(("launches", "grid", "groups", "sys_lds", "cap_lds", "seat_bytes", "out_bytes", "steps"), (int(x) for x in out)))
+        return _view("xpg_lineq_bounds_ragged_last_route", Lineq.PROJECT_ROUTE_KEYS + ("out_bytes", "steps"))
 
     def _hull_ragged(self, groups, rhs_idx, elims, darkshadow, is_intersect, cap_rows, cap_out_rows, cap_hull_rows, copy):
         """xpg_lineq_{hull,project_union}_batch_ragged_rat32 (elims None: the hull). groups: a list of lists of systems."""
-        from .six import _ragged_pack
         ng = len(groups)
         goff = np.zeros(ng + 1, dtype=np.int32)
         goff[1:] = np.cumsum([len(g) for g in groups])
@@ -443,14 +389,10 @@ class Lineq:
         steps = np.zeros(ng, dtype=np.int32)
         if ng == 0:
             return ok, member, chain, steps, []
-        if nb:
-            flat, off, parts = _ragged_pack(members, RAT, 2)
-            rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-        else:
-            flat, off, rows, cols = None, None, None, None
-        rhs = None
-        if rhs_idx is not None:                             # one per group, or one per member
-            rhs = np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+        flat, rows, cols, off, rhs = ragged_systems(members, rhs_idx)
+        if not nb:                                          # groups without any member: no arrays at all
+            flat, rows, cols, off = None, None, None, None
+        if rhs is not None:                                 # one per group, or one per member
             if rhs.size == ng and rhs.size != nb:
                 rhs = np.ascontiguousarray(np.repeat(rhs, np.diff(goff)))
             if rhs.size != nb:
@@ -465,27 +407,16 @@ class Lineq:
                                         C.c_int(int(is_intersect)), *caps, *tail)
         else:
             name = "xpg_lineq_project_union_batch_ragged_rat32"
-            lists = [np.asarray(e, dtype=np.int32).reshape(-1) for g in elims for e in g]
+            lists = [e for g in elims for e in g]
             if len(lists) != nb:
                 raise ValueError("one list per member: %d members, %d lists" % (nb, len(lists)))
-            eoff = np.zeros(nb + 1, dtype=np.int32)
-            eoff[1:] = np.cumsum([e.size for e in lists])
-            el = np.ascontiguousarray(np.concatenate(lists)) if nb and int(eoff[nb]) else np.zeros(1, dtype=np.int32)
+            el, eoff = _flat_lists(lists)
             code = getattr(lib(), name)(self.ctx._h, C.c_int(ng), vp(goff), C.c_int(nb), vp(flat), vp(rows), vp(cols), vp(off), vp(rhs),
                                         vp(el), vp(eoff), C.c_int(int(darkshadow)), C.c_int(int(is_intersect)), *caps, *tail)
         self.ctx.check(code, name)
-        total = int(ooff[ng])
-        if not copy and total:
-            buf = (C.c_int32 * (total * 2)).from_address(view.value)
-            packed = np.frombuffer(buf, dtype=np.int32).reshape(total, 2)
-        else:
-            packed = np.empty((total, 2), dtype=np.int32)
-            if total:                                       # out of the handle's pinned buffer, before the next call reuses it
-                C.memmove(packed.ctypes.data, view.value, packed.nbytes)
-        o = ooff.tolist(); g0 = goff.tolist()
-        width = [int(cols[g0[g]]) if g0[g + 1] > g0[g] else 0 for g in range(ng)]
-        return ok, member, chain, steps, [packed[o[g]: o[g + 1]].reshape(-1, width[g], 2) if width[g] else np.zeros((0, 0, 2), dtype=np.int32)
-                                          for g in range(ng)]
+        g0 = goff.tolist()
+        width = [int(cols[g0[g]]) if g0[g + 1] > g0[g] else 0 for g in range(ng)]     # a group without members: a (0, 0, 2) result
+        return ok, member, chain, steps, _cut(_rows_down(view, int(ooff[ng]), (2,), copy), ooff, width)
 
     def hull_ragged(self, groups, rhs_idx=None, is_intersect=False, cap_rows=None, cap_out_rows=None, cap_hull_rows=None, copy=True):
         """xpg_lineq_hull_batch_ragged_rat32: Lineq::ConvexHullUnionAndIntersect (linsys.cpp:283-336) for MANY lists of polyhedra
@@ -510,11 +441,7 @@ class Lineq:
     @staticmethod
     def hull_ragged_last_route():
         """xpg_lineq_hull_last_route of the calling thread's last hull_ragged / project_union_ragged call, as a dict."""
-        out = np.zeros(10, dtype=np.int64)
-        rc = lib().xpg_lineq_hull_last_route(vp(out), C.c_int(10))
-        if rc != 0:
-            raise ValueError("xpg_lineq_hull_last_route: %d" % rc)
-        return dict(zip(Lineq.HULL_ROUTE_KEYS, (int(x) for x in out)))
+        return _view("xpg_lineq_hull_last_route", Lineq.HULL_ROUTE_KEYS)
 
     def rank(self, mats):
         a = _stack(mats)

@@ -58,6 +58,20 @@ def empty_kind(shape, kind):
     return np.zeros(tuple(shape) + (2,), dtype=np.int32)
 
 
+def _name(stem, kind, tail=""):
+    return "xpg_%s_%s%s" % (stem, "f64" if kind == F64 else "rat32", tail)
+
+
+def _sym(stem, kind, tail=""):
+    """The entry point xpg_<stem>_<f64 | rat32><tail> of a kind: the one place a symbol is chosen by kind."""
+    return getattr(lib(), _name(stem, kind, tail))
+
+
+def _solved(nb, cols, kind):
+    """The (status[nb], v[nb], sol[nb, cols]) triple a batch solver writes into."""
+    return np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind)
+
+
 class Context:
     """xpg_ctx: one GPU, one HIP stream."""
 
@@ -125,55 +139,49 @@ class Context:
         """SIX::pivot arithmetic (lpsol.h:1471-1501) on host arrays, in place."""
         tab = as_kind(tab, kind, 2); obj = as_kind(obj, kind, 1)
         m, W = tab.shape[0], tab.shape[1]
-        fn = lib().xpg_pivot_f64 if kind == F64 else lib().xpg_pivot_rat32
-        self.check(fn(self._h, vp(tab), C.c_int(m), C.c_int(W), vp(obj), C.c_int(rhs_idx),
-                      C.c_int(row), C.c_int(col)), "xpg_pivot")
+        self.check(_sym("pivot", kind)(self._h, vp(tab), C.c_int(m), C.c_int(W), vp(obj), C.c_int(rhs_idx),
+                                       C.c_int(row), C.c_int(col)), "xpg_pivot")
         return tab, obj
 
     def pivot_dev(self, kind, tab_ptr, m, W, ld, obj_ptr, rhs_idx, row, col):
-        fn = lib().xpg_pivot_f64_dev if kind == F64 else lib().xpg_pivot_rat32_dev
-        self.check(fn(self._h, C.c_void_p(tab_ptr), C.c_int(m), C.c_int(W), C.c_int(ld),
-                      C.c_void_p(obj_ptr), C.c_int(rhs_idx), C.c_int(row), C.c_int(col)), "xpg_pivot_dev")
+        self.check(_sym("pivot", kind, "_dev")(self._h, vp(tab_ptr), C.c_int(m), C.c_int(W), C.c_int(ld), vp(obj_ptr),
+                                               C.c_int(rhs_idx), C.c_int(row), C.c_int(col)), "xpg_pivot_dev")
 
     # ---- batches --------------------------------------------------------------------------
     def six_batch(self, kind, is_max, tgtf, leq, max_iter=0xFFFFFFFF):
-        tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
-        nb, m, cols = leq.shape[0], leq.shape[1], leq.shape[2]
-        status = np.zeros(nb, dtype=np.int32)
-        v = empty_kind((nb,), kind)
-        sol = empty_kind((nb, cols), kind)
-        fn = lib().xpg_six_batch_f64 if kind == F64 else lib().xpg_six_batch_rat32
-        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq), C.c_int(m),
-                      C.c_int(cols), C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_six_batch")
-        return status, v, sol
+        return _six_batch(self, "six_batch", kind, is_max, tgtf, leq, max_iter, None)
+
+    def _batch_dev(self, stem, kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr, pivots_ptr, max_iter):
+        """xpg_<stem>_*_dev: device pointers, enqueue only; pivots_ptr may be None."""
+        self.check(_sym(stem, kind, "_dev")(self._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf_ptr), vp(leq_ptr), C.c_int(m),
+                                            C.c_int(cols), C.c_uint(max_iter), vp(status_ptr), vp(v_ptr), vp(sol_ptr),
+                                            vp(pivots_ptr)), "xpg_%s_dev" % stem)
+
+    def _batch_vc_dev(self, stem, kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr, v_ptr,
+                      sol_ptr, max_iter, *pivots):
+        """xpg_<stem>_*_dev: device pointers for every array (vc included), enqueue only; eq_ptr / leq_ptr may be None with 0
+        rows (not both). pivots: the pivot counts' pointer (or None) where the entry point takes one."""
+        self.check(_sym(stem, kind, "_dev")(self._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf_ptr), vp(vc_ptr), vp(eq_ptr),
+                                            C.c_int(eq_rows), vp(leq_ptr), C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter),
+                                            vp(status_ptr), vp(v_ptr), vp(sol_ptr), *(vp(p) for p in pivots)),
+                   "xpg_%s_dev" % stem)
 
     def six_batch_dev(self, kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr,
                       pivots_ptr=None, max_iter=0xFFFFFFFF):
-        fn = lib().xpg_six_batch_f64_dev if kind == F64 else lib().xpg_six_batch_rat32_dev
-        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(leq_ptr),
-                      C.c_int(m), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr),
-                      C.c_void_p(v_ptr), C.c_void_p(sol_ptr),
-                      C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_dev")
+        self._batch_dev("six_batch", kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr, pivots_ptr, max_iter)
 
     def six_batch_vc_dev(self, kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr, v_ptr,
                          sol_ptr, max_iter=0xFFFFFFFF):
         """xpg_six_batch_vc_*_dev: device pointers for every array (vc included), enqueue only -- results after sync().
         eq_ptr / leq_ptr may be None with 0 rows (not both). Nothing falls back here: a vc that is no sign pattern, or a shape
         beyond 64 KB of LDS, ends every LP with status -4."""
-        fn = lib().xpg_six_batch_vc_f64_dev if kind == F64 else lib().xpg_six_batch_vc_rat32_dev
-        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(vc_ptr),
-                      C.c_void_p(eq_ptr) if eq_ptr else None, C.c_int(eq_rows), C.c_void_p(leq_ptr) if leq_ptr else None,
-                      C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
-                      C.c_void_p(sol_ptr)), "xpg_six_batch_vc_dev")
+        self._batch_vc_dev("six_batch_vc", kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr,
+                           v_ptr, sol_ptr, max_iter)
 
     def six_batch_hbm_dev(self, kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr,
                           pivots_ptr=None, max_iter=0xFFFFFFFF):
         """xpg_six_batch_hbm_*_dev: six_batch_dev for LPs of any size (device pointers, enqueue only)."""
-        fn = lib().xpg_six_batch_hbm_f64_dev if kind == F64 else lib().xpg_six_batch_hbm_rat32_dev
-        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(leq_ptr),
-                      C.c_int(m), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr),
-                      C.c_void_p(v_ptr), C.c_void_p(sol_ptr),
-                      C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_hbm_dev")
+        self._batch_dev("six_batch_hbm", kind, is_max, nb, tgtf_ptr, leq_ptr, m, cols, status_ptr, v_ptr, sol_ptr, pivots_ptr, max_iter)
 
     def six_batch_vc_hbm_dev(self, kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr, v_ptr,
                              sol_ptr, pivots_ptr=None, max_iter=0xFFFFFFFF):
@@ -181,11 +189,8 @@ class Context:
         Sized for every variable free: within 64 KB the LDS-resident launch, untouched (pivots_ptr then reads 0xFFFFFFFF, "not
         counted"), otherwise every LP on a slot in device memory (pivots_ptr: each LP's pivot count). Beyond that kernel's
         limits: XpgError (XPG_ERR_UNSUPPORTED), nothing launched or written."""
-        fn = lib().xpg_six_batch_vc_hbm_f64_dev if kind == F64 else lib().xpg_six_batch_vc_hbm_rat32_dev
-        self.check(fn(self._h, C.c_int(int(is_max)), C.c_int(nb), C.c_void_p(tgtf_ptr), C.c_void_p(vc_ptr),
-                      C.c_void_p(eq_ptr) if eq_ptr else None, C.c_int(eq_rows), C.c_void_p(leq_ptr) if leq_ptr else None,
-                      C.c_int(leq_rows), C.c_int(cols), C.c_uint(max_iter), C.c_void_p(status_ptr), C.c_void_p(v_ptr),
-                      C.c_void_p(sol_ptr), C.c_void_p(pivots_ptr) if pivots_ptr else None), "xpg_six_batch_vc_hbm_dev")
+        self._batch_vc_dev("six_batch_vc_hbm", kind, is_max, nb, tgtf_ptr, vc_ptr, eq_ptr, eq_rows, leq_ptr, leq_rows, cols, status_ptr,
+                           v_ptr, sol_ptr, max_iter, pivots_ptr)
 
     def has_solution_batch_dev(self, nb, leq_ptr, leq_rows, eq_ptr, eq_rows, vc_ptr, cols, is_unique_sol, has_ptr, status_ptr=None,
                                max_iter=0xFFFFFFFF, is_int_sol=False):
@@ -193,10 +198,9 @@ class Context:
         sync(). Sized for every variable free. A vc that is no sign pattern ends every system -4; a shape beyond both kernels, or
         is_int_sol, raises XpgError and launches nothing."""
         self.check(lib().xpg_has_solution_batch_rat32_dev(
-            self._h, C.c_int(nb), C.c_void_p(leq_ptr) if leq_ptr else None, C.c_int(leq_rows), C.c_void_p(eq_ptr) if eq_ptr else None,
-            C.c_int(eq_rows), C.c_void_p(vc_ptr), C.c_int(cols - 1), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_int_sol)),
-            C.c_int(int(is_unique_sol)), C.c_uint(max_iter), C.c_void_p(has_ptr), C.c_void_p(status_ptr) if status_ptr else None),
-            "xpg_has_solution_batch_rat32_dev")
+            self._h, C.c_int(nb), vp(leq_ptr), C.c_int(leq_rows), vp(eq_ptr), C.c_int(eq_rows), vp(vc_ptr),
+            C.c_int(cols - 1), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_int_sol)), C.c_int(int(is_unique_sol)),
+            C.c_uint(max_iter), vp(has_ptr), vp(status_ptr)), "xpg_has_solution_batch_rat32_dev")
 
     def trim(self):
         """xpg_trim: cached device blocks, pinned staging and the scratch of six_batch_vc / six_batch_hbm / six_batch_vc_hbm /
@@ -214,19 +218,18 @@ def six_batch_multi(devices, kind, is_max, tgtf, leq, max_iter=0xFFFFFFFF):
     context and host thread of its own inside the library; results land in these host arrays."""
     tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
     nb, m, cols = leq.shape[0], leq.shape[1], leq.shape[2]
-    status = np.zeros(nb, dtype=np.int32)
-    v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    status, v, sol = _solved(nb, cols, kind)
     dev = (C.c_int * len(devices))(*devices)
-    fn = lib().xpg_six_batch_f64_multi if kind == F64 else lib().xpg_six_batch_rat32_multi
-    _check_multi(fn(C.c_int(len(devices)), dev, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq), C.c_int(m),
-                    C.c_int(cols), C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_six_batch_multi")
+    _check_multi(_sym("six_batch", kind, "_multi")(C.c_int(len(devices)), dev, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq),
+                                                   C.c_int(m), C.c_int(cols), C.c_uint(max_iter), vp(status), vp(v), vp(sol)),
+                 "xpg_six_batch_multi")
     return status, v, sol
 
 
 def mip_batch_multi(devices, is_max, is_bin, tgtf, leq):
     tgtf = as_kind(tgtf, RAT, 2); leq = as_kind(leq, RAT, 3)
     nb, rows, cols = leq.shape[0], leq.shape[1], leq.shape[2]
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), RAT); sol = empty_kind((nb, cols), RAT)
+    st, v, sol = _solved(nb, cols, RAT)
     nodes = C.c_longlong()
     dev = (C.c_int * len(devices))(*devices)
     _check_multi(lib().xpg_mip_batch_rat32_multi(C.c_int(len(devices)), dev, C.c_int(nb), C.c_int(int(is_max)),
@@ -368,22 +371,8 @@ class MIP:
         self.ctx, self.kind = ctx, kind
 
     def _solve(self, is_max, tgtf, vc, eq, leq, is_bin, rational_indicator):
-        k = self.kind
-        tgtf = as_kind(tgtf, k, 1); vc = as_kind(vc, k, 2)
-        cols = tgtf.shape[0]
-        eq_rows = 0 if eq is None else len(eq)
-        leq_rows = 0 if leq is None else len(leq)
-        eq_a = as_kind(eq, k, 2) if eq_rows else None
-        leq_a = as_kind(leq, k, 2) if leq_rows else None
         ind = None if rational_indicator is None else np.ascontiguousarray(rational_indicator, dtype=np.uint8)
-        v = empty_kind((1,), k); sol = empty_kind((cols,), k)
-        name = "xpg_mip_%s_%s" % ("maxm" if is_max else "minm", "f64" if k == F64 else "rat32")
-        st = getattr(lib(), name)(self.ctx._h, vp(tgtf), vp(vc), C.c_int(vc.shape[0]), vp(eq_a), C.c_int(eq_rows),
-                                  vp(leq_a), C.c_int(leq_rows), C.c_int(cols), C.c_int(int(is_bin)), vp(ind),
-                                  vp(v), vp(sol))
-        if st < 0 and st != -7:
-            self.ctx.check(st, name)
-        return st, v[0], sol
+        return _solve_one(self.ctx, "mip", self.kind, is_max, tgtf, vc, eq, leq, C.c_int(int(is_bin)), vp(ind))
 
     def maxm(self, tgtf, vc, eq, leq, is_bin=False, rational_indicator=None):     # lpsol.h:2636-2657
         return self._solve(True, tgtf, vc, eq, leq, is_bin, rational_indicator)
@@ -392,14 +381,15 @@ class MIP:
         return self._solve(False, tgtf, vc, eq, leq, is_bin, rational_indicator)
 
 
+PROFILE_FIELDS = ("total_ms", "host_reshape_ms", "create_and_upload_ms", "dual_on_device_ms", "device_solve_ms", "read_back_ms", "release_ms",
+                  "route", "pivots")
+
+
 def six_last_profile():
     """Where the calling thread's last SIX.maxm / minm call spent its time (xpg_six_last_profile), milliseconds."""
-    out = (C.c_double * 9)()
-    lib().xpg_six_last_profile(out, C.c_int(9))
-    names = ("total_ms", "host_reshape_ms", "create_and_upload_ms", "dual_on_device_ms", "device_solve_ms", "read_back_ms", "release_ms")
-    d = {k: round(out[i], 3) for i, k in enumerate(names)}
-    d["route"] = {1: "LDS batch kernel", 2: "HBM-resident loop"}.get(int(out[7]), "none")
-    d["pivots"] = int(out[8])                        # HBM-resident route: pivots of the loop that ended the solve
+    d = {k: round(x, 3) for k, x in _view("xpg_six_last_profile", PROFILE_FIELDS, ctype=C.c_double).items()}
+    d["route"] = {1: "LDS batch kernel", 2: "HBM-resident loop"}.get(int(d["route"]), "none")
+    d["pivots"] = int(d["pivots"])                   # HBM-resident route: pivots of the loop that ended the solve
     return d
 
 
@@ -432,11 +422,10 @@ def mip_batch(ctx, is_max, is_bin, tgtf, leq, kind=RAT):
     tgtf [nb, cols(,2)], leq [nb, rows, cols(,2)]. Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
     tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
     nb, rows, cols = leq.shape[0], leq.shape[1], leq.shape[2]
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    st, v, sol = _solved(nb, cols, kind)
     nodes = C.c_longlong()
-    fn = lib().xpg_mip_batch_rat32 if kind == RAT else lib().xpg_mip_batch_f64
-    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf),
-                 vp(leq), C.c_int(rows), C.c_int(cols), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch")
+    ctx.check(_sym("mip_batch", kind)(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(leq), C.c_int(rows),
+                                      C.c_int(cols), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch")
     return st, v, sol, nodes.value
 
 
@@ -447,11 +436,11 @@ def mip_batch_eq(ctx, is_max, is_bin, tgtf, leq, eq, kind=RAT):
     leq = None if leq is None else as_kind(leq, kind, 3)
     nb, eq_rows, cols = eq.shape[0], eq.shape[1], eq.shape[2]
     rows = 0 if leq is None else leq.shape[1]
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
+    st, v, sol = _solved(nb, cols, kind)
     nodes = C.c_longlong()
-    fn = lib().xpg_mip_batch_eq_rat32 if kind == RAT else lib().xpg_mip_batch_eq_f64
-    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(leq), C.c_int(rows), vp(eq),
-                 C.c_int(eq_rows), C.c_int(cols), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch_eq")
+    ctx.check(_sym("mip_batch_eq", kind)(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(leq), C.c_int(rows),
+                                         vp(eq), C.c_int(eq_rows), C.c_int(cols), vp(st), vp(v), vp(sol), C.byref(nodes)),
+              "xpg_mip_batch_eq")
     return st, v, sol, nodes.value
 
 
@@ -472,13 +461,63 @@ def _vc_batch_args(kind, tgtf, vc, leq, eq):
     return tgtf, vc, leq, eq, nb, cols, rows, eq_rows
 
 
-def _view(name, fields, *args):
-    """A host-only view of the library that fills an array of long long: its values under `fields`."""
-    out = (C.c_longlong * len(fields))()
+def _view(name, fields, *args, ctype=C.c_longlong):
+    """A host-only view of the library that fills n values of `ctype` (long long; double for the profile): its values under
+    `fields`. The one way any "fill n values" view of the package is read."""
+    out = (ctype * len(fields))()
     rc = getattr(lib(), name)(*args, out, C.c_int(len(fields)))
     if rc != 0:
         raise XpgError("%s: %s" % (name, _capi.ERRORS.get(rc, rc)))
-    return dict(zip(fields, (int(x) for x in out)))
+    return dict(zip(fields, out))
+
+
+def _six_batch(ctx, stem, kind, is_max, tgtf, leq, max_iter, out):
+    """xpg_<stem>_*: nb LPs of one shape (x >= 0, inequalities only) in one call. out: a triple to write into, or None."""
+    tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
+    nb, m, cols = leq.shape[0], leq.shape[1], leq.shape[2]
+    status, v, sol = _solved(nb, cols, kind) if out is None else out
+    ctx.check(_sym(stem, kind)(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq), C.c_int(m), C.c_int(cols),
+                               C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_" + stem)
+    return status, v, sol
+
+
+def _six_batch_vc(ctx, stem, kind, is_max, tgtf, vc, leq, eq, max_iter, out):
+    """xpg_<stem>_*: nb LPs of one shape under one vc in one call. out: a triple to write into, or None."""
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
+    st, v, sol = _solved(nb, cols, kind) if out is None else out
+    ctx.check(_sym(stem, kind)(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
+                               vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
+              "xpg_" + stem)
+    return st, v, sol
+
+
+def _mip_batch_vc(ctx, stem, is_max, is_bin, tgtf, vc, leq, eq, ind, kind):
+    """xpg_<stem>_*: nb MIPs of one shape under one vc in one call: (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
+    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
+    ind = None if ind is None else np.ascontiguousarray(ind, dtype=np.uint8)
+    st, v, sol = _solved(nb, cols, kind)
+    nodes = C.c_longlong()
+    ctx.check(_sym(stem, kind)(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(vc), vp(eq), C.c_int(eq_rows),
+                               vp(leq), C.c_int(rows), C.c_int(cols), vp(ind), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_" + stem)
+    return st, v, sol, nodes.value
+
+
+def _solve_one(ctx, stem, kind, is_max, tgtf, vc, eq, leq, *mid):
+    """xpg_<six | mip>_<maxm | minm>_*: one problem; `mid` are the arguments between cols and the results (max_iter, or is_bin
+    and the rational indicator). Status -7 (the reference is undefined) is an answer, any other negative status is raised."""
+    tgtf = as_kind(tgtf, kind, 1); vc = as_kind(vc, kind, 2)
+    cols = tgtf.shape[0]
+    eq_rows = 0 if eq is None else len(eq)
+    leq_rows = 0 if leq is None else len(leq)
+    eq_a = as_kind(eq, kind, 2) if eq_rows else None
+    leq_a = as_kind(leq, kind, 2) if leq_rows else None
+    v = empty_kind((1,), kind); sol = empty_kind((cols,), kind)
+    stem = "%s_%s" % (stem, "maxm" if is_max else "minm")
+    st = _sym(stem, kind)(ctx._h, vp(tgtf), vp(vc), C.c_int(vc.shape[0]), vp(eq_a), C.c_int(eq_rows), vp(leq_a), C.c_int(leq_rows), C.c_int(cols),
+                          *mid, vp(v), vp(sol))
+    if st < 0 and st != -7:
+        ctx.check(st, _name(stem, kind))
+    return st, v[0], sol
 
 
 def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator=None, kind=RAT):
@@ -486,38 +525,19 @@ def mip_batch_vc(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, rational_indicator
     leq [nb, rows, cols(,2)] or None, eq [nb, eq_rows, cols(,2)] or None (not both None), rational_indicator cols bytes or None.
     A vc that is a sign pattern (diagonal -1 = x >= 0, 0 = free, nothing else) is walked on the device, free variables split
     v = v' - v'' in front of every node LP; any other vc by the host controller. Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
-    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
-    ind = None if rational_indicator is None else np.ascontiguousarray(rational_indicator, dtype=np.uint8)
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
-    nodes = C.c_longlong()
-    fn = lib().xpg_mip_batch_vc_rat32 if kind == RAT else lib().xpg_mip_batch_vc_f64
-    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(vc), vp(eq), C.c_int(eq_rows),
-                 vp(leq), C.c_int(rows), C.c_int(cols), vp(ind), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch_vc")
-    return st, v, sol, nodes.value
-
+    return _mip_batch_vc(ctx, "mip_batch_vc", is_max, is_bin, tgtf, vc, leq, eq, rational_indicator, kind)
 
 def mip_last_route():
     """Which route the trees of the calling thread's last MIP / has_solution / dep_is_empty call took (xpg_mip_last_route):
     device_trees walked by the tree-walk kernel, host_trees by the host controller, free_vars split per tree on the device."""
-    out = (C.c_longlong * 3)()
-    lib().xpg_mip_last_route(out, C.c_int(3))
-    return dict(device_trees=int(out[0]), host_trees=int(out[1]), free_vars=int(out[2]))
-
+    return _view("xpg_mip_last_route", ("device_trees", "host_trees", "free_vars"))
 
 def mip_batch_vc_hbm(ctx, is_max, is_bin, tgtf, vc, leq, eq=None, ind=None, kind=RAT):
     """xpg_mip_batch_vc_hbm_*: mip_batch_vc for node LPs of any size. A sign-pattern vc and node LPs within 64 KB of LDS: the
     launch mip_batch_vc makes; a sign-pattern vc past that: still one launch, a workgroup per tree with the node tableaux in
     device memory; anything else by the host controller. Arrays as mip_batch_vc takes them (ind: the rational_indicator).
     Returns (status[nb], v[nb(,2)], sol[nb,cols(,2)], nodes)."""
-    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
-    ind = None if ind is None else np.ascontiguousarray(ind, dtype=np.uint8)
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
-    nodes = C.c_longlong()
-    fn = lib().xpg_mip_batch_vc_hbm_rat32 if kind == RAT else lib().xpg_mip_batch_vc_hbm_f64
-    ctx.check(fn(ctx._h, C.c_int(nb), C.c_int(int(is_max)), C.c_int(int(is_bin)), vp(tgtf), vp(vc), vp(eq), C.c_int(eq_rows),
-                 vp(leq), C.c_int(rows), C.c_int(cols), vp(ind), vp(st), vp(v), vp(sol), C.byref(nodes)), "xpg_mip_batch_vc_hbm")
-    return st, v, sol, nodes.value
-
+    return _mip_batch_vc(ctx, "mip_batch_vc_hbm", is_max, is_bin, tgtf, vc, leq, eq, ind, kind)
 
 def mip_hbm_last_route():
     """{'lds', 'hbm', 'host', 'free', 'grid'}: trees of this thread's last mip_batch_vc_hbm call on the LDS-resident walk / on
@@ -548,30 +568,14 @@ def six_batch_vc(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFFFFF)
     64 KB of LDS: SIX::normalize, the solve and calcFinalSolution run on the device for the whole batch; anything else is
     solved per problem as SIX.maxm / minm would. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); status -7 marks the
     problems the reference is undefined on; sol rows are written on status 0 only."""
-    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
-    st = np.zeros(nb, dtype=np.int32); v = empty_kind((nb,), kind); sol = empty_kind((nb, cols), kind)
-    fn = lib().xpg_six_batch_vc_f64 if kind == F64 else lib().xpg_six_batch_vc_rat32
-    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
-                 vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
-              "xpg_six_batch_vc")
-    return st, v, sol
-
+    return _six_batch_vc(ctx, "six_batch_vc", kind, is_max, tgtf, vc, leq, eq, max_iter, None)
 
 def six_batch_hbm(ctx, kind, is_max, tgtf, leq, max_iter=0xFFFFFFFF, out=None):
     """xpg_six_batch_hbm_*: Context.six_batch for LPs of any size -- an LP that fits one CU's LDS is solved as six_batch
     solves it, a larger one by a workgroup of its own on a tableau in device memory. tgtf [nb, cols], leq [nb, m, cols].
     Returns (status[nb], v[nb], sol[nb, cols]); `out`: such a triple to write into (rows of sol whose status is not 0 are
     left alone). A shape beyond the kernel's limits raises XpgError (XPG_ERR_UNSUPPORTED) and writes nothing."""
-    tgtf = as_kind(tgtf, kind, 2); leq = as_kind(leq, kind, 3)
-    nb, m, cols = leq.shape[0], leq.shape[1], leq.shape[2]
-    if out is None:
-        out = (np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind))
-    status, v, sol = out
-    fn = lib().xpg_six_batch_hbm_f64 if kind == F64 else lib().xpg_six_batch_hbm_rat32
-    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(leq), C.c_int(m), C.c_int(cols),
-                 C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_six_batch_hbm")
-    return status, v, sol
-
+    return _six_batch(ctx, "six_batch_hbm", kind, is_max, tgtf, leq, max_iter, out)
 
 def six_batch_hbm_last_route():
     """{'lds', 'hbm', 'grid'}: LPs of this thread's last six_batch_hbm call solved LDS-resident / on tableaux in device
@@ -595,16 +599,7 @@ def six_batch_vc_hbm(ctx, kind, is_max, tgtf, vc, leq, eq=None, max_iter=0xFFFFF
     finishes on a slot in device memory; anything else per problem as SIX.maxm / minm would. Arrays as six_batch_vc takes
     them. Returns (status[nb], v[nb(,2)], sol[nb, cols(,2)]); `out`: such a triple to write into (rows of sol whose status is
     not 0 are left alone)."""
-    tgtf, vc, leq, eq, nb, cols, rows, eq_rows = _vc_batch_args(kind, tgtf, vc, leq, eq)
-    if out is None:
-        out = (np.zeros(nb, dtype=np.int32), empty_kind((nb,), kind), empty_kind((nb, cols), kind))
-    st, v, sol = out
-    fn = lib().xpg_six_batch_vc_hbm_f64 if kind == F64 else lib().xpg_six_batch_vc_hbm_rat32
-    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tgtf), vp(vc), vp(eq if eq_rows else None), C.c_int(eq_rows),
-                 vp(leq if rows else None), C.c_int(rows), C.c_int(cols), C.c_uint(max_iter), vp(st), vp(v), vp(sol)),
-              "xpg_six_batch_vc_hbm")
-    return st, v, sol
-
+    return _six_batch_vc(ctx, "six_batch_vc_hbm", kind, is_max, tgtf, vc, leq, eq, max_iter, out)
 
 def six_batch_vc_hbm_last_route():
     """{'lds', 'hbm', 'fallback', 'free', 'grid'}: LPs of this thread's last six_batch_vc_hbm / six_batch_vc_hbm_dev call on the
@@ -630,10 +625,7 @@ def six_batch_last_route():
     """Which route the LPs of the calling thread's last six_batch_vc call took (xpg_six_batch_last_route): device = LPs
     reshaped and solved on the device, fallback = LPs solved one by one, free = free variables split per LP on the device
     route (-1 after a _dev call: only the device has read vc)."""
-    out = (C.c_longlong * 3)()
-    lib().xpg_six_batch_last_route(out, C.c_int(3))
-    return dict(device=int(out[0]), fallback=int(out[1]), free=int(out[2]))
-
+    return _view("xpg_six_batch_last_route", ("device", "fallback", "free"))
 
 def dep_is_empty_batch(ctx, mats, rhs_idx=None, vc=None):
     """DepPoly::is_empty(keepit, vc) (src/eng/poly.cpp:530-573) for a stack of dependence polyhedra
@@ -686,14 +678,13 @@ def has_solution(ctx, leq, eq, vc, rhs_idx, is_int_sol, is_unique_sol):
 HS_NOT_RUN = 0x7FFFFFFF                  # XPG_HS_NOT_RUN: the solve did not run
 
 
-def has_solution_batch(ctx, leq, eq, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
-    """Lineq::has_solution for nb rational systems of one shape in one call (xpg_has_solution_batch_rat32): leq [nb, rows,
-    cols(,2)], eq [nb, eq_rows, cols(,2)] or None, vc [cols - 1, cols(,2)] shared by the batch; the constant is the last column.
-    is_int_sol False: a sign-pattern vc within the batch kernels' limits is answered in ONE launch -- the feasibility objective,
-    SIX::normalize once, maxm, then minm where that left the question open -- anything else per system as has_solution does.
-    is_int_sol True: two batched MIP walks, the second on the systems the first left open. Returns has[nb] (1 / 0, or the
-    negative status a solve returned: -7 where the reference is undefined), and with want_status also status[nb, 2]: the SIX /
-    IP status of the maxm and of the minm solve, HS_NOT_RUN for a solve that did not run."""
+def _hs_answers(nb, want_status):
+    """(has[nb], status[nb, 2] filled with HS_NOT_RUN, or None)"""
+    return np.zeros(nb, dtype=np.int32), np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
+
+
+def _hs_front(ctx, leq, eq, vc, want_status):
+    """The arguments the two uniform has_solution entry points share, shaped and checked: (ctx .. rhs_idx, has, status)."""
     vc = as_kind(vc, RAT, 2)
     cols = vc.shape[1]
     leq_a = None if leq is None else as_kind(leq, RAT, 3)
@@ -706,14 +697,23 @@ def has_solution_batch(ctx, leq, eq, vc, is_int_sol, is_unique_sol, max_iter=0xF
             raise ValueError("leq / eq must be [nb, rows, cols]")
     rows = 0 if leq_a is None else leq_a.shape[1]
     eq_rows = 0 if eq_a is None else eq_a.shape[1]
-    has = np.zeros(nb, dtype=np.int32)
-    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
-    ctx.check(lib().xpg_has_solution_batch_rat32(ctx._h, C.c_int(nb), vp(leq_a if rows else None), C.c_int(rows), vp(eq_a if eq_rows else None),
-                                                 C.c_int(eq_rows), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1),
-                                                 C.c_int(int(is_int_sol)), C.c_int(int(is_unique_sol)), C.c_uint(max_iter), vp(has), vp(st)),
-              "xpg_has_solution_batch_rat32")
-    return (has, st) if want_status else has
+    head = (ctx._h, C.c_int(nb), vp(leq_a if rows else None), C.c_int(rows), vp(eq_a if eq_rows else None), C.c_int(eq_rows), vp(vc),
+            C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1))
+    return (head,) + _hs_answers(nb, want_status)
 
+
+def has_solution_batch(ctx, leq, eq, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
+    """Lineq::has_solution for nb rational systems of one shape in one call (xpg_has_solution_batch_rat32): leq [nb, rows,
+    cols(,2)], eq [nb, eq_rows, cols(,2)] or None, vc [cols - 1, cols(,2)] shared by the batch; the constant is the last column.
+    is_int_sol False: a sign-pattern vc within the batch kernels' limits is answered in ONE launch -- the feasibility objective,
+    SIX::normalize once, maxm, then minm where that left the question open -- anything else per system as has_solution does.
+    is_int_sol True: two batched MIP walks, the second on the systems the first left open. Returns has[nb] (1 / 0, or the
+    negative status a solve returned: -7 where the reference is undefined), and with want_status also status[nb, 2]: the SIX /
+    IP status of the maxm and of the minm solve, HS_NOT_RUN for a solve that did not run."""
+    head, has, st = _hs_front(ctx, leq, eq, vc, want_status)
+    ctx.check(lib().xpg_has_solution_batch_rat32(*head, C.c_int(int(is_int_sol)), C.c_int(int(is_unique_sol)), C.c_uint(max_iter), vp(has),
+                                                 vp(st)), "xpg_has_solution_batch_rat32")
+    return (has, st) if want_status else has
 
 def has_solution_batch_last_route():
     """{'lds', 'hbm', 'host', 'second', 'grid'}: systems of this thread's last has_solution_batch / has_solution_batch_dev call on
@@ -747,21 +747,7 @@ class SIX:
         self.max_iter = max_iter
 
     def _solve(self, is_max, tgtf, vc, eq, leq):
-        k = self.kind
-        tgtf = as_kind(tgtf, k, 1); vc = as_kind(vc, k, 2)
-        cols = tgtf.shape[0]
-        eq_rows = 0 if eq is None else len(eq)
-        leq_rows = 0 if leq is None else len(leq)
-        eq_a = as_kind(eq, k, 2) if eq_rows else None
-        leq_a = as_kind(leq, k, 2) if leq_rows else None
-        v = empty_kind((1,), k); sol = empty_kind((cols,), k)
-        name = "xpg_six_%s_%s" % ("maxm" if is_max else "minm", "f64" if k == F64 else "rat32")
-        st = getattr(lib(), name)(self.ctx._h, vp(tgtf), vp(vc), C.c_int(vc.shape[0]), vp(eq_a),
-                                  C.c_int(eq_rows), vp(leq_a), C.c_int(leq_rows), C.c_int(cols),
-                                  C.c_uint(self.max_iter), vp(v), vp(sol))
-        if st < 0 and st != -7:
-            self.ctx.check(st, name)
-        return st, v[0], sol
+        return _solve_one(self.ctx, "six", self.kind, is_max, tgtf, vc, eq, leq, C.c_uint(self.max_iter))
 
     def maxm(self, tgtf, vc, eq, leq):                      # lpsol.h:1993-2033
         return self._solve(True, tgtf, vc, eq, leq)
@@ -794,16 +780,15 @@ def six_batch_ragged(ctx, kind, is_max, tgtfs, leqs, max_iter=0xFFFFFFFF):
     """SIX::maxm / minm (x >= 0, inequalities only) on LPs of DIFFERENT shapes in one call: leqs[b] is rows_b x cols_b,
     tgtfs[b] has cols_b entries. Returns (status[nb], [v_b], [sol_b])."""
     nb = len(leqs)
-    leq_flat, leq_off, lp = _ragged_pack(leqs, kind, 2)
+    leq_flat, rows, cols, leq_off, _ = ragged_systems(leqs, kind=kind)
     tg_flat, tg_off, _ = _ragged_pack(tgtfs, kind, 1)
-    rows = np.array([p.shape[0] for p in lp], dtype=np.int32); cols = np.array([p.shape[1] for p in lp], dtype=np.int32)
     assert np.array_equal(np.diff(tg_off), cols), "tgtfs[b] must have cols_b entries"
     status = np.zeros(nb, dtype=np.int32)
     v = empty_kind((nb,), kind)
     sol = np.zeros_like(tg_flat)
-    fn = lib().xpg_six_batch_f64_ragged if kind == F64 else lib().xpg_six_batch_rat32_ragged
-    ctx.check(fn(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tg_flat), vp(leq_flat), vp(rows), vp(cols), vp(leq_off),
-                 vp(tg_off), C.c_uint(max_iter), vp(status), vp(v), vp(sol)), "xpg_six_batch_ragged")
+    ctx.check(_sym("six_batch", kind, "_ragged")(ctx._h, C.c_int(int(is_max)), C.c_int(nb), vp(tg_flat), vp(leq_flat), vp(rows), vp(cols),
+                                                 vp(leq_off), vp(tg_off), C.c_uint(max_iter), vp(status), vp(v), vp(sol)),
+              "xpg_six_batch_ragged")
     esz = 1 if kind == F64 else 2
     sols = [sol[int(tg_off[b]) * esz: int(tg_off[b + 1]) * esz].reshape((-1,) if kind == F64 else (-1, 2)) for b in range(nb)]
     return status, v, sols
@@ -818,11 +803,8 @@ def _hs_ragged_shapes(systems, cols):
     return mats, np.array([m.shape[0] for m in mats], dtype=np.int32)
 
 
-def has_solution_ragged(ctx, leqs, eqs, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
-    """Lineq::has_solution for rational systems of MIXED shapes under one vc in one call
-    (xpg_has_solution_batch_ragged_rat32): leqs[b] [rows_b, cols(,2)] and eqs[b] [eq_rows_b, cols(,2)], either None or without
-    rows; eqs=None: no system has equalities. Every system takes the route has_solution_batch takes for its shape -- the systems
-    of a route share ONE launch -- and gets that call's answers. Returns has[nb], and with want_status also status[nb, 2]."""
+def _hs_ragged_front(ctx, leqs, eqs, vc, want_status):
+    """The arguments the two ragged has_solution entry points share, shaped and checked: (ctx .. rhs_idx, has, status)."""
     vc = as_kind(vc, RAT, 2)
     cols = vc.shape[1]
     nb = len(leqs)
@@ -834,15 +816,21 @@ def has_solution_ragged(ctx, leqs, eqs, vc, is_int_sol, is_unique_sol, max_iter=
     em, eq_rows = _hs_ragged_shapes(eqs, cols)
     leq_flat, leq_off, _ = _ragged_pack(lm, RAT, 2)
     eq_flat, eq_off, _ = _ragged_pack(em, RAT, 2)
-    has = np.zeros(nb, dtype=np.int32)
-    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
     any_eq = bool(eq_rows.sum())
-    ctx.check(lib().xpg_has_solution_batch_ragged_rat32(
-        ctx._h, C.c_int(nb), vp(leq_flat if leq_rows.sum() else None), vp(leq_rows), vp(leq_off), vp(eq_flat if any_eq else None), vp(eq_rows),
-        vp(eq_off if any_eq else None), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_int_sol)),
-        C.c_int(int(is_unique_sol)), C.c_uint(max_iter), vp(has), vp(st)), "xpg_has_solution_batch_ragged_rat32")
-    return (has, st) if want_status else has
+    head = (ctx._h, C.c_int(nb), vp(leq_flat if leq_rows.sum() else None), vp(leq_rows), vp(leq_off), vp(eq_flat if any_eq else None),
+            vp(eq_rows), vp(eq_off if any_eq else None), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1))
+    return (head,) + _hs_answers(nb, want_status)
 
+
+def has_solution_ragged(ctx, leqs, eqs, vc, is_int_sol, is_unique_sol, max_iter=0xFFFFFFFF, want_status=False):
+    """Lineq::has_solution for rational systems of MIXED shapes under one vc in one call
+    (xpg_has_solution_batch_ragged_rat32): leqs[b] [rows_b, cols(,2)] and eqs[b] [eq_rows_b, cols(,2)], either None or without
+    rows; eqs=None: no system has equalities. Every system takes the route has_solution_batch takes for its shape -- the systems
+    of a route share ONE launch -- and gets that call's answers. Returns has[nb], and with want_status also status[nb, 2]."""
+    head, has, st = _hs_ragged_front(ctx, leqs, eqs, vc, want_status)
+    ctx.check(lib().xpg_has_solution_batch_ragged_rat32(*head, C.c_int(int(is_int_sol)), C.c_int(int(is_unique_sol)), C.c_uint(max_iter),
+                                                        vp(has), vp(st)), "xpg_has_solution_batch_ragged_rat32")
+    return (has, st) if want_status else has
 
 HAS_SOLUTION_RAGGED_ROUTE_FIELDS = ("lds", "hbm", "host", "second", "grid_lds", "grid_hbm", "no_solve")
 
@@ -879,51 +867,18 @@ def has_solution_int_batch(ctx, leq, eq, vc, is_unique_sol, want_status=False):
     walks and the verdict run on the device wherever vc is a sign pattern and the shape is within the walks' limits, anything
     else as has_solution_batch(is_int_sol=True) answers it. Returns has[nb], and with want_status also status[nb, 2] -- bit for
     bit what has_solution_batch(..., True, is_unique_sol) returns."""
-    vc = as_kind(vc, RAT, 2)
-    cols = vc.shape[1]
-    leq_a = None if leq is None else as_kind(leq, RAT, 3)
-    eq_a = None if eq is None else as_kind(eq, RAT, 3)
-    if leq_a is None and eq_a is None:
-        raise ValueError("leq and eq are both None: the batch size is unknown")
-    nb = (leq_a if leq_a is not None else eq_a).shape[0]
-    for a in (leq_a, eq_a):
-        if a is not None and (a.shape[0] != nb or a.shape[2] != cols):
-            raise ValueError("leq / eq must be [nb, rows, cols]")
-    rows = 0 if leq_a is None else leq_a.shape[1]
-    eq_rows = 0 if eq_a is None else eq_a.shape[1]
-    has = np.zeros(nb, dtype=np.int32)
-    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
-    ctx.check(lib().xpg_has_solution_int_batch_rat32(ctx._h, C.c_int(nb), vp(leq_a if rows else None), C.c_int(rows),
-                                                     vp(eq_a if eq_rows else None), C.c_int(eq_rows), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols),
-                                                     C.c_int(cols - 1), C.c_int(int(is_unique_sol)), vp(has), vp(st)),
-              "xpg_has_solution_int_batch_rat32")
+    head, has, st = _hs_front(ctx, leq, eq, vc, want_status)
+    ctx.check(lib().xpg_has_solution_int_batch_rat32(*head, C.c_int(int(is_unique_sol)), vp(has), vp(st)), "xpg_has_solution_int_batch_rat32")
     return (has, st) if want_status else has
-
 
 def has_solution_int_ragged(ctx, leqs, eqs, vc, is_unique_sol, want_status=False):
     """has_solution_int_batch for systems of MIXED shapes under one vc (xpg_has_solution_int_batch_ragged_rat32): the lists of
     has_solution_ragged; the shape classes are formed by the library, each answered by the uniform call, the answers come back
     in the order given. Returns has[nb], and with want_status also status[nb, 2]."""
-    vc = as_kind(vc, RAT, 2)
-    cols = vc.shape[1]
-    nb = len(leqs)
-    if eqs is None:
-        eqs = [None] * nb
-    if len(eqs) != nb:
-        raise ValueError("leqs and eqs must list the same systems")
-    lm, leq_rows = _hs_ragged_shapes(leqs, cols)
-    em, eq_rows = _hs_ragged_shapes(eqs, cols)
-    leq_flat, leq_off, _ = _ragged_pack(lm, RAT, 2)
-    eq_flat, eq_off, _ = _ragged_pack(em, RAT, 2)
-    has = np.zeros(nb, dtype=np.int32)
-    st = np.full((nb, 2), HS_NOT_RUN, dtype=np.int32) if want_status else None
-    any_eq = bool(eq_rows.sum())
-    ctx.check(lib().xpg_has_solution_int_batch_ragged_rat32(
-        ctx._h, C.c_int(nb), vp(leq_flat if leq_rows.sum() else None), vp(leq_rows), vp(leq_off), vp(eq_flat if any_eq else None), vp(eq_rows),
-        vp(eq_off if any_eq else None), vp(vc), C.c_int(vc.shape[0]), C.c_int(cols), C.c_int(cols - 1), C.c_int(int(is_unique_sol)), vp(has),
-        vp(st)), "xpg_has_solution_int_batch_ragged_rat32")
+    head, has, st = _hs_ragged_front(ctx, leqs, eqs, vc, want_status)
+    ctx.check(lib().xpg_has_solution_int_batch_ragged_rat32(*head, C.c_int(int(is_unique_sol)), vp(has), vp(st)),
+              "xpg_has_solution_int_batch_ragged_rat32")
     return (has, st) if want_status else has
-
 
 HAS_SOLUTION_INT_ROUTE_FIELDS = ("lds", "hbm", "host", "second", "grid", "grid2")
 
@@ -952,9 +907,17 @@ def has_solution_int_plan(vc, leq_rows, eq_rows, cols, nb, num_cus=256):
 
 def ragged_pack_rat(mats_list):
     """(flat cells, rows[nb], cols[nb], cell offsets[nb + 1]) of a list of rational systems: the arrays the ragged C entry points take."""
-    flat, off, parts = _ragged_pack(mats_list, RAT, 2)
+    return ragged_systems(mats_list)[:4]
+
+
+def ragged_systems(mats_list, rhs_idx=None, kind=RAT):
+    """The one pack of a list of systems of mixed shapes: (flat cells, rows[nb], cols[nb], cell offsets[nb + 1], rhs) with rhs
+    the per-system rhs_idx as a flat int32 array, or None (every system's last column). Whoever takes an rhs_idx checks its
+    count against what it is one of -- systems, groups or members -- under its own message."""
+    flat, off, parts = _ragged_pack(mats_list, kind, 2)
     rows = np.array([p.shape[0] for p in parts], dtype=np.int32); cols = np.array([p.shape[1] for p in parts], dtype=np.int32)
-    return flat, rows, cols, off
+    rhs = None if rhs_idx is None else np.ascontiguousarray(rhs_idx, dtype=np.int32).reshape(-1)
+    return flat, rows, cols, off, rhs
 
 
 def dep_is_empty_ragged(ctx, mats_list=None, packed=None):
