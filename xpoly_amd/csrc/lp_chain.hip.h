@@ -18,7 +18,7 @@
 //   record of pick worker w, stage t    g0 {ratio key, row}: the ONLY granule everybody polls (one 16-byte load per
 //                                       record and lane; six were measured to cost 2.6 us per hand-off in L2
 //                                       contention: 129 workers x 64 records x 6 loads on 64 lines)
-//                                       g1 {pivot element, leaving}  g2 {pair word, counter, entering | 1 + last
+//                                       g1 {1 / pivot element, leaving}  g2 {pair word, counter, entering | 1 + last
 //                                       stage this row pivoted in}  g3 {c_nv}: fetched of the WINNER only, in the
 //                                       same round as the pivot row gather
 //   commit granule, stage t             written by the committer behind its own drain (off the path)
@@ -190,12 +190,6 @@ __device__ __forceinline__ double ch_readlane_f64(double x, int lane)
     __builtin_memcpy(&x, w, 8);
     return x;
 }
-__device__ __forceinline__ unsigned long long ch_readlane_u64(unsigned long long x, int lane)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
 // The ratio as a key whose UNSIGNED order is the order better() puts ratios in: -0 and +0 are one value,
 // then the usual monotone map of IEEE doubles. ~0 is "no candidate".
 __device__ __forceinline__ unsigned long long ch_ratio_key(double q)
@@ -203,18 +197,24 @@ __device__ __forceinline__ unsigned long long ch_ratio_key(double q)
     const unsigned long long b = __builtin_bit_cast(unsigned long long, q + 0.0);   // (-0) + (+0) = +0
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-template <int CTRL> __device__ __forceinline__ unsigned long long ch_min_step(unsigned long long x)
+// The wave minimum of 64-bit keys as two 32-bit minima: the least high word, then the least low word among the lanes that
+// hold it (the others offer ~0u). Lexicographic (hi, lo) order IS the unsigned 64-bit order, so the value is the same bit for
+// bit; a step is ONE instruction, v_min_u32 with a DPP operand, where the 64-bit step was two DPP moves, a 64-bit compare
+// and two selects. (The compiler folds the DPP move into the minimum only when the lanes without a source are given the
+// minimum's identity, ~0u; with their own value, dpp_row_shr's form, it keeps a v_mov_b32_dpp in front of every v_min.)
+template <int CTRL> __device__ __forceinline__ unsigned ch_umin_step(unsigned x)
+{ return min(x, (unsigned)__builtin_amdgcn_update_dpp((int)~0u, (int)x, CTRL, 0xf, 0xf, false)); }
+__device__ __forceinline__ unsigned ch_wave_min_u32(unsigned x)
 {
-    const unsigned lo = (unsigned)dpp_row_shr<CTRL>((int)(unsigned)x), hi = (unsigned)dpp_row_shr<CTRL>((int)(unsigned)(x >> 32));
-    const unsigned long long t = ((unsigned long long)hi << 32) | lo;
-    return t < x ? t : x;
+    x = ch_umin_step<0x111>(x); x = ch_umin_step<0x112>(x); x = ch_umin_step<0x114>(x); x = ch_umin_step<0x118>(x);
+    return min(min((unsigned)__builtin_amdgcn_readlane((int)x, 15), (unsigned)__builtin_amdgcn_readlane((int)x, 31)),
+               min((unsigned)__builtin_amdgcn_readlane((int)x, 47), (unsigned)__builtin_amdgcn_readlane((int)x, 63)));
 }
 __device__ __forceinline__ unsigned long long ch_wave_min_u64(unsigned long long x)
 {
-    x = ch_min_step<0x111>(x); x = ch_min_step<0x112>(x); x = ch_min_step<0x114>(x); x = ch_min_step<0x118>(x);
-    const unsigned long long a = ch_readlane_u64(x, 15), b = ch_readlane_u64(x, 31), c = ch_readlane_u64(x, 47), d = ch_readlane_u64(x, 63);
-    const unsigned long long ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
+    const unsigned hi = (unsigned)(x >> 32), hmin = ch_wave_min_u32(hi);
+    const unsigned lmin = ch_wave_min_u32(hi == hmin ? (unsigned)x : ~0u);
+    return ((unsigned long long)hmin << 32) | lmin;
 }
 
 // Waiting without asking. A role that has handed its result over knows that the answer takes the other role's whole turn:
@@ -275,7 +275,7 @@ template <bool STAR> __device__ __forceinline__ double ch_replay(double start, c
 }
 
 // The winner of a stage, as every worker derives it from the records.
-struct ChWinner { int r, enter, leave, qstar, cc; uint32_t w; double a; unsigned long long cnv; };
+struct ChWinner { int r, enter, leave, qstar, cc; uint32_t w; double sc; unsigned long long cnv; };     // sc: 1 / pivot element
 enum { CH_CLOSE_ROW = 0x7FFFFFFE, CH_UNORDERED_ROW = 0x7FFFFFFD };
 
 // addresses in the hand-off areas (layout: lp_kernels.hip.h)
@@ -339,7 +339,7 @@ __device__ __forceinline__ bool ch_load_winner(const LpView<F64> & v, int widx, 
         if (++spins > CH_SPIN_LIMIT) return false;
         __builtin_amdgcn_s_sleep(CH_POLL_NAP);
     }
-    W.a = __builtin_bit_cast(double, ch_lo64(g1)); W.leave = (int)g1.z;
+    W.sc = __builtin_bit_cast(double, ch_lo64(g1)); W.leave = (int)g1.z;
     W.w = g2.x; W.cc = (int)g2.y; W.enter = (int)(g2.z & 0xFFFFFFu); W.qstar = (int)(g2.z >> 24) - 1;
     W.cnv = ch_lo64(g3);
     return true;
@@ -454,7 +454,9 @@ __device__ unsigned long long g_ch_ts[4][BLK_MAX][8];            // [worker clas
 // seats every worker with the larger LDS block (ch_lds_bytes); other strides leave the lines to the L1.
 // LINE is the number of columns held: 16 (the whole 128-byte line) where the XCD seats every worker with 8 KB more, else 8
 // (half of it, 4 KB: a batch of 32 stages has 16 KB of history, and 193 workers of 24 KB are one more than 32 compute units
-// of 160 KB hold), else 0.
+// of 160 KB hold), else 0. (The 193rd is the committer, which uses no LDS. Seating it as wave 1 of workgroup 0 -- 192 workgroups
+// of two waves, the whole line at 32 stages -- was built and measured: "partials seen -> gather in" 0.72 us against 0.76, the
+// launch 2.4 us longer; it stays a workgroup of its own. profiles/chain_path_ab.txt)
 inline int ch_hist_slots(int B, int line) { return line ? (B + 3) / 4 * 4 : BLK_MAX; }
 inline size_t ch_lds_bytes(int B, int line)
 {
@@ -728,7 +730,9 @@ __global__ __launch_bounds__(64) void k_blk_chain(LpView<F64> v, int batch, int 
                 // g0 first: it is what every worker of the launch waits for; the payload is read of the winner only, one round
                 // later, and carries its own tags
                 ch_store_granule3<LOCAL>(ch_rec_g0(v, w), (unsigned)kmin, (unsigned)(kmin >> 32), (unsigned)(kmin != ~0ull ? i : INT_MAX), tag);
-                const unsigned long long ab = to_bits(F64(a));
+                // 1 / pivot element (lpsol.h:1471) here, by the one lane that has nothing else to do, instead of by every lane
+                // of every prep worker between the payload's arrival and the scale: the same div() on the same operand
+                const unsigned long long ab = to_bits(div(one<F64>(), F64(a)));
                 char * pay = ch_rec_pay(v, w);
                 ch_store_granule3<LOCAL>(pay, (unsigned)ab, (unsigned)(ab >> 32), (unsigned)bi, tag);
                 ch_store_granule3<LOCAL>(pay + 16, pw_word, (unsigned)cc, (unsigned)first | ((unsigned)(sstar + 1) << 24), tag);
@@ -778,7 +782,7 @@ __global__ __launch_bounds__(64) void k_blk_chain(LpView<F64> v, int batch, int 
         const double kv = lane < t ? kv_mem : -1.0;         // (lanes at and beyond t: what makes their product -0.0, ch_replay)
         CH_TS(1);                                           // (prep) row gather round and the winner's payload in
         const int enter = g.enter, leave = g.leave;
-        const F64 sc = div(one<F64>(), F64(g.a));           // 1/(eq.get(eqnum, nv)), lpsol.h:1471
+        const F64 sc = F64(g.sc);                           // 1/(eq.get(eqnum, nv)), lpsol.h:1471: divided by the lane that published the record
         const int smode = scale_mode(sc);
         const F64 cnv = from_bits<F64>(g.cnv);
         const int cmode = scale_mode(cnv);

@@ -116,7 +116,7 @@ enum { BLK_MAX = 32,           // the most pivots a batch stages (XPG_BLOCK up t
 // partials) or 64 (128-byte records) -- and what only the consumer of ONE producer reads (the payload) lies behind it.
 //   blkR (8-byte words): [0, 64 x 16)        the launch-per-stage records (blk_pick_body -> blk_prep_body), 16 words each
 //                        + 2 w               chain record w, g0 {ratio key, row, tag}: polled by every worker
-//                        + 2 x 256 + 8 w     its payload g1 {pivot element, leaving} g2 {pair word, counter, entering | last
+//                        + 2 x 256 + 8 w     its payload g1 {1 / pivot element, leaving} g2 {pair word, counter, entering | last
 //                                            stage} g3 {c_nv}: fetched of the winner only
 //   blkP (ints):         4 w                 partial w, g0 {lowest eligible column, any c_j > 0, tag, 0}; the chain's commit granule, in the
 //                                            slot behind its last prep worker: {INT_MAX, 0, tag, pivot row | CH_CLOSE_ROW}
