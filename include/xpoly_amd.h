@@ -902,6 +902,51 @@ int xpg_lineq_levels_last_route(long long * out, int n);
  * asks -- then [7] the cap_rows and [8] the cap_out_rows it settles on.  Fills min(n, 9) entries; XPG_ERR_SHAPE (n_elim <= 0
  * too) / XPG_ERR_UNSUPPORTED (n_elim > 64 too) as the call. */
 int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_rows, int cap_out_rows, long long * out, int n);
+/* Limits of TRANSFORMED loop nests in ONE launch: LoopTran::transformIterSpace (src/eng/ldtran.cpp:131-300) starts from a nest
+ * A * i <= C and a transformation T -- det(T) and T^-1 (:148, :160), (A * T^-1 | C) (:162-175), then the fme loop rhs_idx-1 .. 1
+ * whose every level is a loop bound (:178-196).  For nb transformations tmats [nb][n][n], n = rhs_idx, each against its own
+ * nest nests [nb][rows][cols] or (shared_nest != 0) against ONE rows x cols nest -- the search over transformations: the nest
+ * goes up once.
+ *   mode 0        T is the transformation.  out_det[b] = det(T) always (Matrix<Rational>::det, src/com/matt.h:1621-1736).
+ *                 det == 0: out_kind[b] = 1 (singular; the reference ASSERTs);  |det| != 1: out_kind[b] = 2 (nonsingular, not
+ *                 unimodular: the reference's second branch, :203-291).  Both end the system with no rows, out_ok[b] = 1 and
+ *                 out_steps[b] = 0.  Else out_kind[b] = 0 and the multiplier M = T^-1 (Matrix<Rational>::inv, matt.h:1743-1845).
+ *   mode 1        T is the right multiplier M itself -- the Ui of the second branch (A * Ui, :233-235) or a T^-1 the caller
+ *                 holds: no determinant, no inverse, out_det untouched (may be NULL), out_kind[b] = 0.
+ *   out_mult      [nb][n][n]: M, the reference's invt / idx_map (zeros for a system of kind 1 or 2)
+ *   level 0       A' = (A * M | C): operator* (matt.h:60-79: tmp = 0, tmp = tmp + a(i,k) * m(k,j), k ascending), the constant
+ *                 columns copied bit for bit -- aux_limits' tail and trA.  Level k >= 1 is A' with rhs_idx-1 .. rhs_idx-k
+ *                 eliminated: a system has n levels; n == 1 has level 0 only.
+ *   row_offsets   [nb * n + 1], entry b * n + k the first row of level k of system b
+ *   cap_rows, cap_out_rows   as xpg_lineq_levels_batch_packed_rat32; a level's slot holds the nest, so an explicit cap_out_rows
+ *                 under rows is XPG_ERR_SHAPE (the default min(cap_rows, 4 * rows + 16) never is)
+ *   out_ok, out_steps [nb]   the levels call's, steps counted in eliminations (1 with n - 1; 0 or -need with the step
+ *                 concerned).  A system with out_ok[b] <= 0 contributes no rows at any level, level 0 included.
+ * outs, outs_cap_rows, out_view and the sizing call as xpg_lineq_levels_batch_packed_rat32; one upload (two copies above 4 MB),
+ * one launch.  XPG_ERR_SHAPE: rhs_idx outside [1, cols), mode outside {0, 1}, nb < 0, nests or tmats NULL with nb > 0;
+ * XPG_ERR_UNSUPPORTED as the levels call, rhs_idx - 1 > 64 included.  nb == 0: returns 0, row_offsets[0] = 0. */
+int xpg_lineq_transform_levels_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * nests, int shared_nest, const xpg_rat32 * tmats,
+                                                  int rows, int cols, int rhs_idx, int mode, int cap_rows, int cap_out_rows,
+                                                  xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                                  long long * row_offsets, int32_t * out_ok, int32_t * out_steps, int32_t * out_kind,
+                                                  xpg_rat32 * out_det, xpg_rat32 * out_mult);
+/* The same on DEVICE arrays, enqueue only: d_outs [nb][n][cap_out_rows][cols] receives each level's live rows and is not
+ * cleared behind them, d_out_rows [nb][n] their counts, d_out_ok / d_out_steps / d_out_kind [nb], d_out_det [nb] (mode 0),
+ * d_out_mult [nb][n][n] (left alone for a system of kind 1 or 2).  The intermediates' slots are the projection's.  Both
+ * capacities are the caller's, as xpg_lineq_levels_batch_rat32_dev states them: cap_rows < rows, cap_out_rows > cap_rows or
+ * cap_out_rows < rows is XPG_ERR_SHAPE. */
+int xpg_lineq_transform_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_nests, int shared_nest, const xpg_rat32 * d_tmats,
+                                               int rows, int cols, int rhs_idx, int mode, int cap_rows, int cap_out_rows,
+                                               xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps,
+                                               int32_t * d_out_kind, xpg_rat32 * d_out_det, xpg_rat32 * d_out_mult);
+/* Evidence, no reference counterpart: what the calling thread's last xpg_lineq_transform_levels_batch_* call did.  The seven
+ * figures of xpg_lineq_levels_last_route, [6] the bytes of the level slots nb x n x cap_out_rows x cols x 8.  Fills min(n, 7). */
+int xpg_lineq_transform_last_route(long long * out, int n);
+/* Host-only view for tests (no device needed): the same seven figures from the shape alone -- the function the launch itself
+ * asks -- then [7] cap_rows, [8] cap_out_rows and [9] where the inverse's scratch (n x 2n augmented matrix, T's copy, row
+ * factors, live flags) starts in a system's LDS block: 0 where it lies in the walk's two idle areas, else the byte behind the
+ * walk's scratch where it was added.  Fills min(n, 10) entries; XPG_ERR_SHAPE / XPG_ERR_UNSUPPORTED as the call. */
+int xpg_test_lineq_transform_plan(int nb, int rows, int cols, int rhs_idx, int cap_rows, int cap_out_rows, long long * out, int n);
 /* The projection and the levels for systems of MIXED shapes and lists in ONE launch: the statements of a SCoP sit at
  * different depths, so rows, cols, rhs_idx and the list rhs_idx-1 .. 1 differ from statement to statement.  mats holds the
  * systems, system b (rows[b] x cols[b]) at cell offsets[b]; rhs_idx[b] its constant column (NULL: the last column of each);

@@ -10,7 +10,8 @@
 // compile unchanged against `xpoly_amd::Lineq<RMat>` and run on the GPU. Each member is the batch entry point
 // with a batch of one (the batch forms in xpoly_amd.h are what a caller with a SCoP's worth of polyhedra
 // should use; the collectors below the class -- dep_is_empty_all, has_solution_all, fme_all, project_all,
-// levels_all, project_each, levels_nests, calc_bound_all, calc_bound_each, hull_all, project_union_each -- take the caller's
+// levels_all, project_each, levels_nests, calc_bound_all, calc_bound_each, hull_all, project_union_each, transform_levels_all
+// (and LoopTran<RMat>, the reference's LoopTran::transformIterSpace on top of it) -- take the caller's
 // matrix objects and make those calls). Header only; relies on the Matrix<Rational> contract only: get_row_size(), get_col_size(),
 // get_matrix() (row-major {int32 num; int32 den}, matt.h:152-156, rational.h:66-67), size(), reinit(r, c).
 #ifndef XPOLY_AMD_LINEQ_HPP
@@ -910,6 +911,175 @@ inline int project_union_each(const std::vector<std::vector<RMatT *> > & groups,
 {
     return detail::hull_groups(groups, rhs_idx, &elims, darkshadow, is_intersect, results, ok, member, c);
 }
+
+// ---- limits of TRANSFORMED loop nests: LoopTran::transformIterSpace (src/eng/ldtran.cpp:131-300) ---------------------------------
+// What one transformation of a nest comes back as: the verdicts of xpg_lineq_transform_levels_batch_packed_rat32, the
+// determinant (mode 0), invt (the multiplier; empty for kind 1 and 2) and the levels -- levels[0] the transformed nest (A * invt
+// | C), levels[k] that system with rhs_idx-1 .. rhs_idx-k eliminated; all empty for kind 1 / 2 or ok <= 0.
+template <class RMatT> struct transformed_nest {
+    int32_t ok, steps, kind; xpg_rat32 det; RMatT invt; std::vector<RMatT> levels;
+};
+namespace detail {
+// The one call behind LoopTran and transform_levels_all: nb transformations tm [nb][nv][nv] against nests [nb][rows][cols] or
+// (shared) ONE nest, retried on -need as levels_all retries. sink(answer, kind, det, mult) once every answer is there.
+template <class Sink>
+inline int transform_call(xpg_ctx * h, int nb, const xpg_rat32 * nests, bool shared, const xpg_rat32 * tm, int rows, int cols, int nv, int mode,
+                          Sink sink)
+{
+    const int cap = chain_default(rows);
+    const retry_rule how = { { cap, cap < bound_default(rows) ? cap : bound_default(rows), 0 }, { 0, 0, 0 }, own_slot, false, 4 };
+    std::vector<int32_t> kind((size_t)nb);
+    std::vector<xpg_rat32> det((size_t)nb), mult((size_t)nb * nv * nv);
+    return call_until_answered(how, (size_t)nb, (size_t)nb * nv,
+        [&](const caps & cp, answer & a) {
+            return xpg_lineq_transform_levels_batch_packed_rat32(h, nb, nests, shared ? 1 : 0, tm, rows, cols, nv, mode, cp.cap, cp.out, (xpg_rat32 *)0, 0,
+                                                                 &a.view, a.off, a.ok, a.steps, kind.data(), det.data(), mult.data());
+        },
+        [&](const answer & a) { sink(a, kind.data(), det.data(), mult.data()); });
+}
+template <class RMatT>
+inline int transform_levels_some(const std::vector<const RMatT *> & nests, bool shared, const std::vector<RMatT *> & ts, int rhs_idx, int mode,
+                                 std::vector<transformed_nest<RMatT> > & out, xpg_ctx * c)
+{
+    const int nb = (int)ts.size(), nv = rhs_idx;
+    out.clear();
+    if (nb == 0) return 0;
+    if (nests.empty() || (!shared && (int)nests.size() != nb) || nests[0]->size() == 0 || nv < 1) return XPG_ERR_SHAPE;
+    const int rows = (int)nests[0]->get_row_size(), cols = (int)nests[0]->get_col_size();
+    for (size_t k = 0; k < nests.size(); k++)
+        if (nests[k]->size() == 0 || (int)nests[k]->get_row_size() != rows || (int)nests[k]->get_col_size() != cols) return XPG_ERR_SHAPE;
+    for (int b = 0; b < nb; b++)
+        if ((int)ts[(size_t)b]->get_row_size() != nv || (int)ts[(size_t)b]->get_col_size() != nv) return XPG_ERR_SHAPE;
+    const shape_known nshape = { rows, cols }, tshape = { nv, nv };
+    const packed pn = pack((int)nests.size(), [&](int i) { return nests[(size_t)i]; }, nshape);
+    const packed pt = pack(nb, [&](int i) { return (const RMatT *)ts[(size_t)i]; }, tshape);
+    out.resize((size_t)nb);
+    return transform_call(ctx_or_shared(c), nb, pn.flat.data(), shared, pt.flat.data(), rows, cols, nv, mode,
+        [&](const answer & a, const int32_t * kind, const xpg_rat32 * det, const xpg_rat32 * mult) {
+            for (int b = 0; b < nb; b++) {
+                transformed_nest<RMatT> & o = out[(size_t)b];
+                o.ok = a.ok[(size_t)b]; o.steps = a.steps[(size_t)b]; o.kind = kind[(size_t)b]; o.det = det[(size_t)b];
+                if (o.kind == 0) put_cells(o.invt, mult + (size_t)b * nv * nv, nv, nv);
+                o.levels.resize((size_t)nv);
+                for (int k = 0; k < nv; k++) a.put_packed(o.levels[(size_t)k], (size_t)b * nv + k, cols);
+            }
+        });
+}
+}
+// The search over transformations: ONE nest against many T in one shared-nest call -- per T the kind, the determinant, invt
+// and the levels (transformed_nest). mode 1: the ts are the right multipliers themselves. Returns 0 or a negative XPG_ERR_* code.
+template <class RMatT>
+inline int transform_levels_all(const RMatT & nest, const std::vector<RMatT *> & ts, int rhs_idx, std::vector<transformed_nest<RMatT> > & out,
+                                xpg_ctx * c = 0, int mode = 0)
+{
+    return detail::transform_levels_some(std::vector<const RMatT *>(1, &nest), true, ts, rhs_idx, mode, out, c);
+}
+// The same with one nest per T, all of one shape.
+template <class RMatT>
+inline int transform_levels_all(const std::vector<RMatT *> & nests, const std::vector<RMatT *> & ts, int rhs_idx,
+                                std::vector<transformed_nest<RMatT> > & out, xpg_ctx * c = 0, int mode = 0)
+{
+    return detail::transform_levels_some(std::vector<const RMatT *>(nests.begin(), nests.end()), false, ts, rhs_idx, mode, out, c);
+}
+
+// A class with the reference's LoopTran constructor and transformIterSpace signature (src/eng/ldtran.h:50-103), so that
+//     LoopTran lt(&A, rhs_idx);  bool uni = lt.transformIterSpace(t, stride, idx_map, aux_limits, ofst, mul, &trA);
+// compiles against xpoly_amd::LoopTran<RMat>. Beyond lineq.hpp's matrix contract it relies on RMat's own operator* and
+// assignment (matt.h:60-79), as the reference does for idx_map * invt and Ui * Hi.
+//   t unimodular: ONE mode 0 call -- det, T^-1, A * T^-1 and every level on the device. stride is a row of ones, ofst and mul
+//     are emptied, aux_limits is filled tail to head (the tail the transformed nest), trA receives the tail. Returns true.
+//   t nonsingular, not unimodular (that call answers kind 2): the reference's second branch (:203-291) -- hnf through
+//     xpg_int_hnf_batch, H^-1 through xpg_rat_inv_batch, ONE mode 1 call with Ui; stride = mul = diag(H), invt = Ui * Hi, and
+//     ofst = (the strictly lower part of H) * Hi, whose row i is the reference's sum of H(i,j) * Hi[j] over j < i (:271-289; the
+//     product also adds the zero terms, which leaves a canonical cell as it is). Returns false, status() == 0.
+//   t singular, an inconsistent nest (the reference ASSERTs at both) or a failed call: returns false with every argument left
+//     as it was and status() != 0 -- 1: t is singular, 2: "system inconsistency!", 3: H of the hnf has no inverse, else the
+//     negative XPG_ERR_* code (XPG_ERR_REF_UNDEFINED where INTMat::hnf itself is undefined for t, xpg_int_hnf_batch).
+//   idx_map = idx_map * invt, or invt where idx_map is empty (:293-298).
+template <class RMatT> class LoopTran {
+    xpg_ctx * m_ctx;
+    RMatT * m_a;
+    int m_rhs_idx, m_status;
+    static void put_ints(RMatT & m, const int32_t * v, int rows, int cols, bool lower_only = false)
+    {
+        std::vector<xpg_rat32> cells((size_t)rows * cols);
+        for (int i = 0; i < rows; i++)
+            for (int j = 0; j < cols; j++) { cells[(size_t)i * cols + j].num = lower_only && j >= i ? 0 : v[(size_t)i * cols + j]; cells[(size_t)i * cols + j].den = 1; }
+        detail::put_cells(m, cells.data(), rows, cols);
+    }
+public:
+    explicit LoopTran(RMatT * m, int rhs_idx = -1, xpg_ctx * c = 0) : m_ctx(c), m_a(0), m_rhs_idx(-1), m_status(0) { if (m) set_param(m, rhs_idx); }
+    void set_param(RMatT * m, int rhs_idx = -1) { m_a = m; m_rhs_idx = rhs_idx == -1 ? (int)m->get_col_size() - 1 : rhs_idx; }   // ldtran.cpp:51-62
+    int status() const { return m_status; }
+    template <class ListT, class = decltype(std::declval<ListT &>().get_tail()), class = decltype(std::declval<ListT &>().get_prev()),
+              class = decltype(std::declval<ListT &>().get_elem_count())>
+    bool transformIterSpace(RMatT & t, RMatT & stride, RMatT & idx_map, ListT & aux_limits, RMatT & ofst, RMatT & mul, RMatT * trA = 0)
+    {
+        const int nv = m_rhs_idx;
+        m_status = XPG_ERR_SHAPE;
+        if (!m_a || m_a->size() == 0 || nv < 1 || nv >= (int)m_a->get_col_size() || (int)aux_limits.get_elem_count() != nv ||
+            (int)t.get_row_size() != nv || (int)t.get_col_size() != nv)
+            return false;                                               // the reference ASSERTs (:139-140, :151)
+        std::vector<RMatT *> dst;                                       // the tail first; none of them is the nest itself
+        for (RMatT * newb = aux_limits.get_tail(); (int)dst.size() < nv; newb = aux_limits.get_prev()) {
+            if (!newb || newb == m_a) return false;
+            dst.push_back(newb);
+        }
+        xpg_ctx * h = detail::ctx_or_shared(m_ctx);
+        const int rows = (int)m_a->get_row_size(), cols = (int)m_a->get_col_size();
+        const xpg_rat32 * in = (const xpg_rat32 *)m_a->get_matrix();
+        int kind = 0, ok = 0;
+        std::vector<RMatT> got((size_t)nv);
+        RMatT invt;
+        const auto keep = [&](const detail::answer & a, const int32_t * k, const xpg_rat32 *, const xpg_rat32 * mult) {
+            kind = k[0]; ok = a.ok[0];
+            if (kind != 0 || ok != 1) return;
+            detail::put_cells(invt, mult, nv, nv);
+            for (int j = 0; j < nv; j++) a.put_packed(got[(size_t)j], (size_t)j, cols);
+        };
+        int rc = detail::transform_call(h, 1, in, true, (const xpg_rat32 *)t.get_matrix(), rows, cols, nv, 0, keep);
+        if (rc != 0) { m_status = rc; return false; }
+        if (kind == 1) { m_status = 1; return false; }                  // "T is singular!!" (:149)
+        const bool is_uni = kind == 0;
+        std::vector<int32_t> hm((size_t)nv * nv), um((size_t)nv * nv);
+        RMatT Hi;
+        if (!is_uni) {
+            std::vector<int32_t> it((size_t)nv * nv);
+            const xpg_rat32 * tc = (const xpg_rat32 *)t.get_matrix();
+            for (size_t x = 0; x < it.size(); x++) it[x] = tc[x].den ? tc[x].num / tc[x].den : 0;    // it.copy(t) (:207)
+            int32_t st = 0, inv_ok = 0;
+            rc = xpg_int_hnf_batch(h, 1, it.data(), nv, nv, hm.data(), um.data(), &st);               // tmph = it * tmpu (:208)
+            if (rc != 0 || st != 0) { m_status = rc ? rc : st; return false; }
+            RMatT H, Ui;
+            put_ints(H, hm.data(), nv, nv); put_ints(Ui, um.data(), nv, nv);
+            std::vector<xpg_rat32> hi((size_t)nv * nv);
+            rc = xpg_rat_inv_batch(h, 1, (const xpg_rat32 *)H.get_matrix(), nv, hi.data(), &inv_ok);  // H.inv(Hi) (:223)
+            if (rc != 0 || !inv_ok) { m_status = rc ? rc : 3; return false; }
+            detail::put_cells(Hi, hi.data(), nv, nv);
+            rc = detail::transform_call(h, 1, in, true, (const xpg_rat32 *)Ui.get_matrix(), rows, cols, nv, 1, keep);   // A * Ui (:233-235)
+            if (rc != 0) { m_status = rc; return false; }
+            invt = Ui * Hi;                                             // (:224)
+        }
+        if (ok != 1) { m_status = ok == 0 ? 2 : XPG_ERR_UNSUPPORTED; return false; }      // "system inconsistency!" (:186-188, :249-251)
+        m_status = 0;
+        for (int j = 0; j < nv; j++) *dst[(size_t)j] = got[(size_t)j];
+        if (trA) *trA = got[0];                                         // (:197-200, :258-261)
+        if (is_uni) {
+            std::vector<int32_t> ones((size_t)nv, 1);
+            put_ints(stride, ones.data(), 1, nv);                       // (:167-170)
+            ofst.reinit(0, 0); mul.reinit(0, 0);                        // (:154-155)
+        } else {
+            std::vector<int32_t> diag((size_t)nv);
+            for (int i = 0; i < nv; i++) diag[(size_t)i] = hm[(size_t)i * nv + i];
+            put_ints(stride, diag.data(), 1, nv); put_ints(mul, diag.data(), 1, nv);     // H.getdiag(stride); mul.copy(stride) (:221-222)
+            RMatT lower;
+            put_ints(lower, hm.data(), nv, nv, true);
+            ofst = lower * Hi;                                          // (:271-289)
+        }
+        if (idx_map.size() > 0) idx_map = idx_map * invt; else idx_map = invt;           // (:293-298)
+        return is_uni;
+    }
+};
 
 } // namespace xpoly_amd
 #endif

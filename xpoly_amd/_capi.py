@@ -54,6 +54,8 @@ SYMBOLS = [
     "xpg_lineq_bounds_batch_ragged_rat32", "xpg_lineq_bounds_ragged_last_route", "xpg_test_lineq_bounds_ragged_plan",
     "xpg_lineq_hull_batch_ragged_rat32", "xpg_lineq_project_union_batch_ragged_rat32", "xpg_lineq_hull_last_route",
     "xpg_lineq_project_union_last_route", "xpg_test_lineq_hull_plan",
+    "xpg_lineq_transform_levels_batch_packed_rat32", "xpg_lineq_transform_levels_batch_rat32_dev", "xpg_lineq_transform_last_route",
+    "xpg_test_lineq_transform_plan",
 ]
 
 _lib = None

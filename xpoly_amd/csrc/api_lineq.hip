@@ -223,6 +223,37 @@ int xpg_test_lineq_levels_plan(int nb, int rows, int cols, int n_elim, int cap_r
     LineqPlan p;
     return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_LEVELS, levels_plan(nb, rows, cols, n_elim, cap_rows, cap_out_rows, p), p, out, n);
 }
+// ---- limits of transformed loop nests: T^-1, A * T^-1 and every level in one launch (lineq_host.hip.h) ------------------------
+int xpg_lineq_transform_levels_batch_packed_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * nests, int shared_nest, const xpg_rat32 * tmats,
+                                                  int rows, int cols, int rhs_idx, int mode, int cap_rows, int cap_out_rows,
+                                                  xpg_rat32 * outs, long long outs_cap_rows, const xpg_rat32 ** out_view,
+                                                  long long * row_offsets, int32_t * out_ok, int32_t * out_steps, int32_t * out_kind,
+                                                  xpg_rat32 * out_det, xpg_rat32 * out_mult)
+{
+    XPG_BIND(ctx);
+    return lineq_transform_batch_packed(ctx, nb, (const R32 *)nests, shared_nest, (const R32 *)tmats, rows, cols, rhs_idx, mode, cap_rows,
+                                        cap_out_rows, (R32 *)outs, outs_cap_rows, (const R32 **)out_view, row_offsets, out_ok, out_steps,
+                                        out_kind, (R32 *)out_det, (R32 *)out_mult);
+}
+int xpg_lineq_transform_levels_batch_rat32_dev(xpg_ctx * ctx, int nb, const xpg_rat32 * d_nests, int shared_nest, const xpg_rat32 * d_tmats,
+                                               int rows, int cols, int rhs_idx, int mode, int cap_rows, int cap_out_rows,
+                                               xpg_rat32 * d_outs, int32_t * d_out_rows, int32_t * d_out_ok, int32_t * d_out_steps,
+                                               int32_t * d_out_kind, xpg_rat32 * d_out_det, xpg_rat32 * d_out_mult)
+{
+    XPG_BIND(ctx);
+    return lineq_transform_batch_dev(ctx, nb, (const R32 *)d_nests, shared_nest, (const R32 *)d_tmats, rows, cols, rhs_idx, mode, cap_rows,
+                                     cap_out_rows, (R32 *)d_outs, d_out_rows, d_out_ok, d_out_steps, d_out_kind, (R32 *)d_out_det,
+                                     (R32 *)d_out_mult);
+}
+// what the calling thread's last xpg_lineq_transform_levels_batch_* call did (lineq_host.hip.h: the table beside LineqRoute)
+int xpg_lineq_transform_last_route(long long * out, int n) { return route_out(ROUTE_TRANSFORM, out, n); }
+// host-only test view: the plan of a transformed-nest call from its shape alone (lineq_host.hip.h transform_plan), with the
+// capacities it settles on and where the inverse's scratch lies behind the route's seven figures
+int xpg_test_lineq_transform_plan(int nb, int rows, int cols, int rhs_idx, int cap_rows, int cap_out_rows, long long * out, int n)
+{
+    LineqPlan p;
+    return !out || n < 0 ? XPG_ERR_SHAPE : plan_out(ROUTE_TRANSFORM, transform_plan(nb, rows, cols, rhs_idx, cap_rows, cap_out_rows, p), p, out, n);
+}
 // ---- projection / levels of systems of mixed shapes and lists in one launch (lineq_host.hip.h) --------------------------------
 int xpg_lineq_project_batch_ragged_rat32(xpg_ctx * ctx, int nb, const xpg_rat32 * mats, const int32_t * rows, const int32_t * cols,
                                          const long long * offsets, const int32_t * rhs_idx, const int32_t * elim, const int32_t * elim_offsets,

@@ -62,10 +62,12 @@ struct PackedUp {
     size_t ints_bytes() const { return ((size_t)nres + (size_t)nv * nb) * 4; }
     char * h_room(xpg_ctx * ctx) const { return hpack_buf(ctx, internal) + meta_al + in_stage; }
 };
-inline int packed_up(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int nres, int nv, size_t bo, bool in_place, bool internal,
-                     PackedUp & u)
+// `more` (transformed nests; else none): a second host array that travels behind the first -- di holds [bi_first bytes of
+// mats][more_bytes of more], staged and sent as ONE block where the two are small together, else one copy each.
+inline int packed_up_bytes(xpg_ctx * ctx, int nb, const void * mats, size_t bi_first, const void * more, size_t more_bytes, int nres, int nv,
+                           size_t bo, bool in_place, bool internal, PackedUp & u)
 {
-    const size_t bi = (size_t)nb * rows * cols * 8;
+    const size_t bi = bi_first + more_bytes;
     const bool small_in = bi <= ((size_t)4 << 20);
     u.nb = nb; u.nres = nres; u.nv = nv; u.bo = bo; u.internal = internal;
     u.meta_al = ((size_t)(nres + 1) * 8 + u.ints_bytes() + 255) & ~(size_t)255;
@@ -74,10 +76,21 @@ inline int packed_up(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols
     XPG_TRY(u.di.alloc(ctx, bi)); XPG_TRY(u.dints.alloc(ctx, u.ints_bytes())); XPG_TRY(u.doff.alloc(ctx, (size_t)(nres + 1) * 8));
     if (!in_place) XPG_TRY(u.dout.alloc(ctx, bo));
     if (const int rc = hpack_reserve(ctx, u.meta_al + u.in_stage + (in_place ? bi : u.small_out ? bo : 0), internal)) return rc;
-    const void * src = mats;
-    if (small_in) { src = hpack_buf(ctx, internal) + u.meta_al; memcpy((void *)src, mats, bi); }
-    XPG_TRY(hipMemcpyAsync(u.di.p, src, bi, hipMemcpyHostToDevice, ctx->stream));
+    if (small_in) {
+        char * stage = hpack_buf(ctx, internal) + u.meta_al;
+        memcpy(stage, mats, bi_first);
+        if (more_bytes) memcpy(stage + bi_first, more, more_bytes);
+        XPG_TRY(hipMemcpyAsync(u.di.p, stage, bi, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    }
+    XPG_TRY(hipMemcpyAsync(u.di.p, mats, bi_first, hipMemcpyHostToDevice, ctx->stream));
+    if (more_bytes) XPG_TRY(hipMemcpyAsync((char *)u.di.p + bi_first, more, more_bytes, hipMemcpyHostToDevice, ctx->stream));
     return 0;
+}
+inline int packed_up(xpg_ctx * ctx, int nb, const R32 * mats, int rows, int cols, int nres, int nv, size_t bo, bool in_place, bool internal,
+                     PackedUp & u)
+{
+    return packed_up_bytes(ctx, nb, mats, (size_t)nb * rows * cols * 8, (const void *)0, 0, nres, nv, bo, in_place, internal, u);
 }
 
 // Lineq::reduce / removeIdenRow for nb host systems with a PACKED result (round 6): row_offsets[nb + 1] (in rows) and the
@@ -309,15 +322,21 @@ inline int lineq_fme_batch_packed(xpg_ctx * ctx, int nb, const R32 * mats, int r
 //   steps        elimination steps of the batch (calcBound), of one system (the uniform calcBound)
 struct LineqPlan {
     int launches, rows, cols, cap, cap_out, cap_lds; LineqGeom q; long long seats, slots, steps; size_t seat_bytes, out_bytes;
+    int inv_at;         // transformed nests: where the inverse's scratch starts in a system's LDS block (0: in the walk's areas)
 };
 // What tells the families apart in the rule: cap_rows <= 0 is fme's worst case rows^2 / 4 + rows + 1 (every positive-negative pair
 // and the rows without the variable) or the packed calcBound's 4 * rows + 16; cap_out_rows <= 0 is cap, or min(cap, 4 * rows + 16)
 // where the output slots follow nb * n_elim and not the grid (levels: at the projection's worst case the slots of 1024 nests of
 // 60 rows and depth 6 would be gigabytes); a seat has two cap-row slots or three (calcBound: two sides and the held prefix); and
 // the ragged kernels' seat is the workgroup (fme's whole wave), so they refuse a geometry with several systems per workgroup.
-struct PlanKind { bool fme_cap, levels_out; int seat_slots; bool seat_is_workgroup; };
-inline PlanKind kind_chain(bool levels, bool ragged) { const PlanKind k = {true, levels, 2, ragged}; return k; }
-inline PlanKind kind_bounds(bool ragged) { const PlanKind k = {false, false, 3, ragged}; return k; }
+// inv_n > 0 (transformed nests): the system also inverts an inv_n x inv_n matrix before its walk begins. That scratch
+// (transform_inv_bytes) is dead before the walk loads its input and the walk's result and input areas are idle until then: it
+// lies IN those areas where they hold it (inv_at 0, no byte added) and else behind the walk's own scratch, its bytes added to the
+// system's LDS before the 160 KB rule and the geometry.
+struct PlanKind { bool fme_cap, levels_out; int seat_slots; bool seat_is_workgroup; int inv_n; };
+inline PlanKind kind_chain(bool levels, bool ragged) { const PlanKind k = {true, levels, 2, ragged, 0}; return k; }
+inline PlanKind kind_bounds(bool ragged) { const PlanKind k = {false, false, 3, ragged, 0}; return k; }
+inline PlanKind kind_transform(int n) { const PlanKind k = {true, true, 2, false, n}; return k; }
 // The rule. cap_out_rows above cap: cap. The LDS layout is fme_lds(cap, cap, cols), the rule calcBound's chains run under --
 // measured for k_fme_batch, not again for the chain kernels. Returns 0 or XPG_ERR_UNSUPPORTED: rows or cap
 // above 32767 (rows are indexed as short; the guard on rows keeps rows * rows an int), LDS over 160 KB, a seat that is no workgroup.
@@ -332,9 +351,15 @@ inline int lineq_plan_rule(int nb, int rows, int cols, int cap_rows, int cap_out
     if (cap_out_rows <= 0) p.cap_out = k.levels_out && few < p.cap ? few : p.cap;
     if (p.cap > 32767) return XPG_ERR_UNSUPPORTED;
     const FmeLds fl = fme_lds(p.cap, p.cap, cols);
-    if (fl.lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
+    size_t lds = fl.lds;
+    p.inv_at = 0;
+    if (k.inv_n > 0 && transform_inv_bytes(k.inv_n) > ((size_t)fl.cap_lds + p.cap) * cols * 8) {
+        p.inv_at = (int)((fl.lds + 15) & ~(size_t)15);
+        lds = (size_t)p.inv_at + transform_inv_bytes(k.inv_n);
+    }
+    if (lds > 160 * 1024) return XPG_ERR_UNSUPPORTED;
     p.cap_lds = fl.cap_lds;
-    p.q = lineq_geom(nb, 64, fl.lds);
+    p.q = lineq_geom(nb, 64, lds);
     if (k.seat_is_workgroup && p.q.G != 1) return XPG_ERR_UNSUPPORTED;
     p.seats = (long long)p.q.grid * p.q.G;
     p.seat_bytes = (size_t)p.seats * k.seat_slots * (size_t)p.cap * cols * 8;
@@ -373,6 +398,19 @@ inline int bounds_plan(int nb, int rows, int cols, int rhs, int cap_rows, int ca
     return 0;
 }
 
+// Transformed nests (k_transform_levels_batch): levels_plan with n_elim = rhs - 1, which may be 0, and rhs slots a system --
+// the transformed nest itself, then one per step. A level's slot holds at least the nest's rows: the default min(cap, 4 * rows +
+// 16) does, an explicit cap_out_rows under rows is refused. The inverse's scratch: PlanKind's inv_n.
+inline int transform_plan(int nb, int rows, int cols, int rhs, int cap_rows, int cap_out_rows, LineqPlan & p)
+{
+    if (nb <= 0 || rows <= 0 || cols <= 1 || rhs < 1 || rhs >= cols) return XPG_ERR_SHAPE;
+    if (rhs - 1 > FME_CHAIN_MAX) return XPG_ERR_UNSUPPORTED;
+    if (cap_out_rows > 0 && cap_out_rows < rows) return XPG_ERR_SHAPE;
+    if (const int rc = lineq_plan_rule(nb, rows, cols, cap_rows, cap_out_rows, kind_transform(rhs), p)) return rc;
+    plan_slots(p, (long long)nb * rhs, (long long)nb * rhs * cols, 0);
+    return 0;
+}
+
 // ---- THE route record: what the calling thread's last call of a family did (xpg_lineq_*_last_route) ---------------------------
 // One record type, one thread_local record per family (they are independent: a caller reads one after calling another). A call
 // clears its family's record when it begins and writes it once its launch is enqueued; the shared pieces below (the enqueue
@@ -385,15 +423,16 @@ inline int bounds_plan(int nb, int rows, int cols, int rhs, int cap_rows, int ca
 //   RAGGED          the same six, out_bytes (bytes of the output slots)                         cap cap_out cols rows (the envelope)
 //   BOUNDS          the same six, steps (elimination steps per system)                          cap cap_out
 //   BOUNDS_RAGGED   the same six, out_bytes, steps (of the whole batch)                         cap cap_out cols rows
+//   TRANSFORM       the same six, level_bytes (bytes of the level slots, rhs a system)             cap cap_out inv_at
 //   HULL            producer launches (1), k_group_reduce launches (1), its grid and LDS bytes   cap cap_out cap_hull lds_rows ecols
 //                   per workgroup, groups at home in LDS / in a device slot, bytes of the         (hull_figures, lineq_hull_host.hip.h;
 //                   producer's seats / of the device slots / of the output slots, and the         the view has no `gathered`)
 //                   rows gathered over all groups (counted after the call; not a plan figure)
 // groups: systems per workgroup; sys_lds: LDS bytes per system; seat_bytes: bytes of seat slots the launch was given.
-enum { ROUTE_PROJECT, ROUTE_LEVELS, ROUTE_RAGGED, ROUTE_BOUNDS, ROUTE_BOUNDS_RAGGED, ROUTE_HULL, ROUTE_FAMILIES };
+enum { ROUTE_PROJECT, ROUTE_LEVELS, ROUTE_RAGGED, ROUTE_BOUNDS, ROUTE_BOUNDS_RAGGED, ROUTE_HULL, ROUTE_TRANSFORM, ROUTE_FAMILIES };
 enum { ROUTE_MAX = 10, FIGURES_MAX = 16 };
 struct LineqRoute { long long f[ROUTE_MAX]; };
-const int ROUTE_FIGURES[ROUTE_FAMILIES] = {6, 7, 7, 7, 8, 10};
+const int ROUTE_FIGURES[ROUTE_FAMILIES] = {6, 7, 7, 7, 8, 10, 7};
 inline LineqRoute & lineq_route(int family) { static thread_local LineqRoute r[ROUTE_FAMILIES] = {}; return r[family]; }
 inline void route_clear(int family) { lineq_route(family) = LineqRoute(); }
 inline void route_write(int family, const long long * f)
@@ -415,10 +454,11 @@ inline int plan_figures(int family, const LineqPlan & p, long long * f)
     const bool ragged = family == ROUTE_RAGGED || family == ROUTE_BOUNDS_RAGGED;
     int n = 0;
     f[n++] = p.launches; f[n++] = p.q.grid; f[n++] = p.q.G; f[n++] = p.q.sys_lds; f[n++] = p.cap_lds; f[n++] = (long long)p.seat_bytes;
-    if (family == ROUTE_LEVELS || ragged) f[n++] = (long long)p.out_bytes;
+    if (family == ROUTE_LEVELS || family == ROUTE_TRANSFORM || ragged) f[n++] = (long long)p.out_bytes;
     if (family == ROUTE_BOUNDS || family == ROUTE_BOUNDS_RAGGED) f[n++] = p.steps;
     f[n++] = p.cap; f[n++] = p.cap_out;
     if (ragged) { f[n++] = p.cols; f[n++] = p.rows; }
+    if (family == ROUTE_TRANSFORM) f[n++] = p.inv_at;
     return n;
 }
 inline void route_write(int family, const LineqPlan & p) { long long f[FIGURES_MAX]; plan_figures(family, p, f); route_write(family, f); }
@@ -509,6 +549,93 @@ inline int lineq_chain_batch_packed(xpg_ctx * ctx, bool levels, int nb, const R3
     route_write(family, p);
     int32_t * const verdicts[2] = {out_ok, out_steps};
     return packed_rows_down(ctx, u, cols, p.cap_out, (const char *)0, out, out_cap_rows, view, row_offsets, verdicts, no_lap);
+}
+
+// ---- limits of transformed loop nests: T^-1, A * T^-1 and every level in one launch of k_transform_levels_batch -------------------
+// What both forms refuse before they look at the handle: rhs_idx outside [1, cols), a mode that is neither 0 nor 1.
+inline int transform_check(int cols, int rhs, int mode)
+{
+    return cols <= 1 || rhs < 1 || rhs >= cols || (mode != 0 && mode != 1) ? XPG_ERR_SHAPE : 0;
+}
+// Device arrays, enqueue only; `p` is the plan of what was launched (launches == 0: nothing). d_nests [nb][rows][cols], or one
+// rows x cols nest where shared_nest; d_tmats [nb][rhs][rhs]; d_outs [nb][rhs][cap_out_rows][cols], level 0 the transformed nest;
+// d_rows [nb][rhs]; d_ok / d_steps / d_kind [nb]; d_det [nb] (written in mode 0 only); d_mult [nb][rhs][rhs]. The capacities are
+// the caller's, as chain_batch_enqueue states them for the levels, and a level's slot holds the nest: cap_out_rows < rows is
+// XPG_ERR_SHAPE. The seats' slots are the projection's.
+inline int transform_enqueue(xpg_ctx * ctx, int nb, const R32 * d_nests, int shared_nest, const R32 * d_tmats, int rows, int cols, int rhs,
+                             int mode, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows, int32_t * d_ok, int32_t * d_steps,
+                             int32_t * d_kind, R32 * d_det, R32 * d_mult, LineqPlan & p)
+{
+    p = LineqPlan();
+    if (const int rc = transform_check(cols, rhs, mode)) return rc;
+    if (!ctx || nb < 0 || rows <= 0 || !d_outs || !d_rows || !d_ok || !d_steps || !d_kind || !d_mult || (mode == 0 && !d_det)) return XPG_ERR_SHAPE;
+    if (nb > 0 && (!d_nests || !d_tmats)) return XPG_ERR_SHAPE;
+    if (cap_rows < rows || cap_out_rows > cap_rows || cap_out_rows < rows) return XPG_ERR_SHAPE;
+    if (nb == 0) return 0;
+    if ((long long)nb * rhs > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    LineqPlan q;
+    if (const int rc = transform_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, q)) return rc;
+    Scratch & slots = ctx->scratch[SCRATCH_LINEQ_PROJECT];
+    if (const int rc = scratch_reserve(ctx, slots, q.seat_bytes, q.seat_bytes, "hipMalloc(lineq_transform seats)")) return rc;
+    XPG_TRY(lds_limit((const void *)k_transform_levels_batch, ctx->device, q.q.lds));
+    hipLaunchKernelGGL(k_transform_levels_batch, dim3(q.q.grid), q.q.block, q.q.lds, ctx->stream, nb, d_nests, shared_nest ? 1 : 0, d_tmats,
+                       rows, cols, rhs, mode, (R32 *)slots.buf, q.cap, d_outs, q.cap_out, (int *)d_rows, (int *)d_ok, (int *)d_steps,
+                       (int *)d_kind, d_det, d_mult, q.cap_lds, q.inv_at, q.q.sys_lds);
+    XPG_TRY(hipGetLastError());
+    p = q;
+    return 0;
+}
+inline int lineq_transform_batch_dev(xpg_ctx * ctx, int nb, const R32 * d_nests, int shared_nest, const R32 * d_tmats, int rows, int cols,
+                                     int rhs, int mode, int cap_rows, int cap_out_rows, R32 * d_outs, int32_t * d_rows, int32_t * d_ok,
+                                     int32_t * d_steps, int32_t * d_kind, R32 * d_det, R32 * d_mult)
+{
+    route_clear(ROUTE_TRANSFORM);
+    LineqPlan p;
+    const int rc = transform_enqueue(ctx, nb, d_nests, shared_nest, d_tmats, rows, cols, rhs, mode, cap_rows, cap_out_rows, d_outs, d_rows, d_ok,
+                                     d_steps, d_kind, d_det, d_mult, p);
+    if (rc == 0) route_write(ROUTE_TRANSFORM, p);
+    return rc;
+}
+// Host arrays with a PACKED result, as lineq_chain_batch_packed: the nests (one where shared_nest) and the transformations go up
+// as one block (packed_up_bytes), the one launch, and packed_rows_down with its one synchronisation before the rows come down.
+// row_offsets [nb * rhs + 1], entry b * rhs + k where level k of system b starts, level 0 the transformed nest. The determinants
+// and the multipliers come down through the handle's second pinned buffer under the same synchronisation; out_det is written in
+// mode 0 only. A buffer too small (XPG_ERR_SHAPE) still gets its offsets, verdicts, determinants and multipliers.
+inline int lineq_transform_batch_packed(xpg_ctx * ctx, int nb, const R32 * nests, int shared_nest, const R32 * tmats, int rows, int cols,
+                                        int rhs, int mode, int cap_rows, int cap_out_rows, R32 * out, long long out_cap_rows,
+                                        const R32 ** view, long long * row_offsets, int32_t * out_ok, int32_t * out_steps,
+                                        int32_t * out_kind, R32 * out_det, R32 * out_mult)
+{
+    if (view) *view = 0;
+    route_clear(ROUTE_TRANSFORM);
+    if (const int rc = transform_check(cols, rhs, mode)) return rc;
+    if (!ctx || nb < 0 || rows <= 0 || !row_offsets || !out_ok || !out_steps || !out_kind || !out_mult || (mode == 0 && !out_det) ||
+        (out && out_cap_rows < 0) || (nb > 0 && (!nests || !tmats)))
+        return XPG_ERR_SHAPE;
+    if (nb == 0) { row_offsets[0] = 0; return 0; }
+    LineqPlan p;
+    if (const int rc = transform_plan(nb, rows, cols, rhs, cap_rows, cap_out_rows, p)) return rc;
+    if (p.slots > INT_MAX) return XPG_ERR_UNSUPPORTED;
+    const size_t b_nests = (size_t)(shared_nest ? 1 : nb) * rows * cols * 8, b_t = (size_t)nb * rhs * rhs * 8, b_det = (size_t)nb * 8;
+    PackedUp u;
+    if (const int rc = packed_up_bytes(ctx, nb, nests, b_nests, tmats, b_t, (int)p.slots, 3, p.out_bytes, false, false, u)) return rc;
+    DevBuf dmore;                                                  // determinants [nb], then multipliers [nb][rhs][rhs]
+    XPG_TRY(dmore.alloc(ctx, b_det + b_t));
+    if (const int rc = hpack_reserve(ctx, b_det + b_t, true)) return rc;
+    XPG_TRY(hipMemsetAsync(dmore.p, 0, b_det + b_t, ctx->stream));    // (a system of kind 1 or 2 has no multiplier: zeros)
+    if (const int rc = transform_enqueue(ctx, nb, (const R32 *)u.di.p, shared_nest, (const R32 *)((char *)u.di.p + b_nests), rows, cols, rhs, mode,
+                                         p.cap, p.cap_out, (R32 *)u.dout.p, u.d_rows(), u.d_verdict(0), u.d_verdict(1), u.d_verdict(2),
+                                         (R32 *)dmore.p, (R32 *)((char *)dmore.p + b_det), p)) return rc;
+    route_write(ROUTE_TRANSFORM, p);
+    char * const hmore = hpack_buf(ctx, true);
+    XPG_TRY(hipMemcpyAsync(hmore, dmore.p, b_det + b_t, hipMemcpyDeviceToHost, ctx->stream));
+    int32_t * const verdicts[3] = {out_ok, out_steps, out_kind};
+    const int rc = packed_rows_down(ctx, u, cols, p.cap_out, (const char *)0, out, out_cap_rows, view, row_offsets, verdicts, no_lap);
+    if (rc == 0 || rc == XPG_ERR_SHAPE) {
+        if (mode == 0) memcpy(out_det, hmore, b_det);
+        memcpy(out_mult, hmore + b_det, b_t);
+    }
+    return rc;
 }
 
 // ---- projection / levels for systems of MIXED shapes and lists: one launch of k_fme_chain_ragged ---------------------------------

@@ -587,6 +587,16 @@ struct UniformChain : UniformSys {
     __device__ __forceinline__ int n() const { return el.n; }
     __device__ __forceinline__ int u(int k) const { return el.u[k]; }
 };
+// system b of a transformed batch (k_transform_levels_batch): `per` = rhs slots a system. Slot 0 holds the transformed nest
+// A' = (A * M | C), which the kernel stores before the walk and the walk reads as its input -- cells the same wave has stored,
+// as the side just written; slot k + 1 is level k of the list rhs-1 .. 1, which needs no list in memory.
+struct TransformSys : UniformSys {
+    __device__ __forceinline__ const R32 * in() const { return outs + (size_t)b * per * cap_out * cols_; }
+    __device__ __forceinline__ R32 * out(int k) const { return UniformSys::out(k + 1); }
+    __device__ __forceinline__ int * cnt(int k) const { return UniformSys::cnt(k + 1); }
+    __device__ __forceinline__ int n() const { return rhs_ - 1; }
+    __device__ __forceinline__ int u(int k) const { return rhs_ - 1 - k; }
+};
 // system b of a ragged batch: the slots start at cell d.out_off, the counts at out_rows[first] (one result: first = b; a result
 // per list entry or per variable: first = d.list_at, which for calcBound carries the sum of the rhs before b, list_n its rhs --
 // k_ragged_cells / k_pack_ragged serve in their levels mode)
@@ -1206,6 +1216,112 @@ __global__ __launch_bounds__(64) void k_gauss_batch(int nb, const R32 * mats, in
             if (op == 0) { const int r = w_rank(m, tfac, live); if (lane_id() == 0) out_int[b] = r; }
             else { const R32 d = (rows == cols) ? w_det(m, tfac, live) : R32(0, 1); if (lane_id() == 0) out_val[b] = d; }
         }
+        wave_sync();
+    }
+}
+
+// ---- limits of TRANSFORMED loop nests: T^-1, A * T^-1 and every level in one launch -----------------------------------------------
+// LoopTran::transformIterSpace (src/eng/ldtran.cpp:131-300) starts from a nest A * i <= C (rows x cols, the first n = rhs columns
+// the loop indices) and a transformation T (n x n): det(T), T^-1, A' = (A * T^-1 | C), and then the fme loop n-1 .. 1 whose every
+// level bounds a loop. One system per wavefront group, the geometry and the walk of k_fme_levels_batch:
+//   mode 0  T is the transformation. det by w_det on a copy (the reference asks t.det() before t.inv(), :148 / :160), out_det[b]
+//           always written; det == 0: kind 1 (singular), |det| != 1: kind 2 (not unimodular) -- both end the system with no rows
+//           at any level, ok 1, steps 0; else M = T^-1 by w_inv, kind 0.
+//   mode 1  T is the right multiplier M itself (the non-unimodular branch's Ui, :233-235, or a T^-1 the caller holds): no
+//           determinant, no inverse, out_det[b] untouched, kind 0.
+// M goes to out_mult [nb][n][n] (the reference's invt). A'[i][j], j < n, is operator* (src/com/matt.h:60-79): tmp = 0, then
+// tmp = tmp + a(i,k) * m(k,j) for k ascending, one lane per cell; the columns n .. cols-1 are copied bit for bit (innerColumn
+// and grow_col, :162-175). A' is stored as LEVEL 0 of the system's n slots (aux_limits' tail, trA) with `rows` rows, and
+// w_chain_walk<true> runs over it through TransformSys: slot k + 1 is the system with n-1 .. n-1-k eliminated. n == 1: level 0
+// only. out_ok / out_steps are the walk's (1 / 0 / -need with its step); a system with out_ok <= 0 has 0 rows at every level,
+// level 0 included.
+//   nests [nb][rows][cols], or ONE nest for all nb transformations (shared_nest: the search over transformations);
+//   outs [nb][n][cap_out][cols], out_rows [nb][n]; cap_out >= rows (the host's rule), so level 0 fits its slot.
+// LDS: the inverse's scratch -- [T | E] n x 2n, T's copy n x n, n row factors, n live flags: transform_inv_bytes -- starts
+// inv_at bytes into the system's block. It is dead before the walk loads its input and the walk's two areas are idle until then,
+// so the host puts it there (inv_at == 0) where it fits and behind the walk's own scratch where it does not (transform_plan).
+__host__ __device__ inline size_t transform_inv_bytes(int n) { return (((size_t)3 * n * n + n) * 8 + (size_t)n + 15) & ~(size_t)15; }
+
+__global__ __launch_bounds__(64) void k_transform_levels_batch(int nb, const R32 * nests, int shared_nest, const R32 * tmats, int rows,
+                                                               int cols, int rhs, int mode, R32 * seats, int cap, R32 * outs,
+                                                               int cap_out, int * out_rows, int * out_ok, int * out_steps,
+                                                               int * out_kind, R32 * out_det, R32 * out_mult, int cap_lds,
+                                                               int inv_at, int sys_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
+    unsigned char * const lds = lds_all + (size_t)threadIdx.y * sys_lds;
+    R32 * const res_lds = (R32 *)lds;
+    R32 * const tmp_lds = res_lds + (size_t)cap_lds * cols;
+    WScratch s = carve_scratch((unsigned char *)(tmp_lds + (size_t)cap * cols), cap);
+    const size_t slot = (size_t)cap * cols;
+    R32 * const seat = seats + (size_t)sys_first() * 2 * slot;
+    const int n = rhs, nc = cols - n;
+    WMat w; w.a = (R32 *)(lds + inv_at); w.r = n; w.c = 2 * n; w.ld = 2 * n;         // [T | E]
+    WMat d; d.a = w.a + 2 * n * n; d.r = n; d.c = n; d.ld = n;                       // T again, for the determinant
+    R32 * const tfac = d.a + n * n;
+    unsigned char * const live = (unsigned char *)(tfac + n);
+    const FastDiv by_n(n, (rows > n ? rows : n) * n + wave_lanes()), by_nc(nc, rows * nc + wave_lanes());
+    for (int b = sys_first(); b < nb; b += sys_stride()) {
+        const R32 * const t = tmats + (size_t)b * n * n;
+        bool bad = false;
+        for (int x = lane_id(); x < n * n; x += wave_lanes()) {
+            const R32 v = t[x];
+            bad |= !canonical(v);
+            const int i = by_n.quot(x), j = x - i * n;
+            if (mode == 0) {
+                d.a[x] = v;
+                w.a[i * w.ld + j] = v;
+                w.a[i * w.ld + n + j] = (i == j && n > 2) ? R32(1, 1) : R32(0, 1);   // (as k_gauss_batch op 2 sets it up)
+            } else w.a[i * w.ld + n + j] = v;
+        }
+        w.cn = d.cn = grp_ballot(bad) == 0;
+        wave_sync();
+        int kind = 0;
+        if (mode == 0) {
+            const R32 det = w_det(d, tfac, live);
+            if (lane_id() == 0) out_det[b] = det;
+            if (eq(det, R32(0, 1))) kind = 1;
+            else if (!eq(abs_r(det), R32(1, 1))) kind = 2;
+            else {
+                wave_sync();
+                if (!w_inv(w, n, tfac, live)) kind = 1;
+                wave_sync();
+            }
+        }
+        const TransformSys y = {{(const R32 *)0, rows, cols, rhs, rhs, outs, cap_out, out_rows, b}};
+        int * const cnt0 = out_rows + (size_t)b * rhs;
+        ChainEnd e; e.okv = 1; e.steps = 0;
+        if (kind == 0) {
+            const R32 * const a = nests + (shared_nest ? (size_t)0 : (size_t)b * rows * cols);
+            R32 * const a0 = outs + (size_t)b * rhs * cap_out * cols;                // level 0: y.in()
+            for (int x = lane_id(); x < n * n; x += wave_lanes()) {
+                const int i = by_n.quot(x), j = x - i * n;
+                out_mult[(size_t)b * n * n + x] = w.a[i * w.ld + n + j];
+            }
+            bool abad = false;
+            for (int x = lane_id(); x < rows * n; x += wave_lanes()) {
+                const int i = by_n.quot(x), j = x - i * n;
+                abad |= !canonical(a[i * cols + j]);
+            }
+            const bool cn = w.cn && grp_ballot(abad) == 0;
+            for (int x = lane_id(); x < rows * n; x += wave_lanes()) {
+                const int i = by_n.quot(x), j = x - i * n;
+                R32 tmp(0, 1);
+                for (int k = 0; k < n; k++) tmp = q_add(cn, tmp, q_mul(cn, a[i * cols + k], w.a[k * w.ld + n + j]));
+                a0[i * cols + j] = tmp;
+            }
+            for (int x = lane_id(); x < rows * nc; x += wave_lanes()) {
+                const int i = by_nc.quot(x), j = n + x - i * nc;
+                a0[i * cols + j] = a[i * cols + j];
+            }
+            if (lane_id() == 0) *cnt0 = rows;
+            wave_sync();                                                             // M is read, level 0 is stored: the walk may load
+            e = w_chain_walk<true>(y, res_lds, tmp_lds, seat, slot, 0, cap, cap_out, cap_lds, s);
+            if (lane_id() == 0 && e.okv != 1) *cnt0 = 0;                             // (lane 0 wrote it: its stores keep their order)
+        } else if (lane_id() == 0) {
+            for (int j = 0; j < rhs; j++) cnt0[j] = 0;
+        }
+        if (lane_id() == 0) { out_ok[b] = e.okv; out_steps[b] = e.steps; out_kind[b] = kind; }
         wave_sync();
     }
 }

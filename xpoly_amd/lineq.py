@@ -202,6 +202,40 @@ class Lineq:
         """xpg_lineq_levels_last_route of the calling thread's last levels call, as a dict."""
         return _view("xpg_lineq_levels_last_route", Lineq.PROJECT_ROUTE_KEYS + ("level_bytes",))
 
+    def transform_levels_packed(self, mats, tmats, rhs_idx, mode=0, shared_nest=False, cap_rows=None, cap_out_rows=None, copy=True):
+        """xpg_lineq_transform_levels_batch_packed_rat32: the limits of transformed loop nests in one launch
+        (LoopTran::transformIterSpace, src/eng/ldtran.cpp:131-300). tmats [nb, n, n, 2] with n = rhs_idx; mats one nest per
+        transformation [nb, rows, cols, 2], or with shared_nest ONE nest [rows, cols, 2] for all of them. mode 0: tmats are
+        the transformations T (det, T^-1); mode 1: they are the right multipliers M themselves. Returns (ok[nb], steps[nb],
+        kind[nb], det[nb, 2], mult[nb, n, n, 2], levels): kind 0 with levels[b][0] = (A * M | C) and levels[b][k] that system
+        with rhs_idx-1 .. rhs_idx-k eliminated, under levels_packed's verdicts; kind 1 (T singular) or 2 (|det| != 1) with no
+        rows at any level, ok 1 and steps 0. det is None in mode 1. copy=False: the levels are views of the handle's pinned
+        buffer, valid until the next packed call."""
+        a, t = _stack(mats), _stack(tmats)
+        nb, n = t.shape[0], int(rhs_idx)
+        rows, cols = a.shape[1:3]
+        if t.shape[1:3] != (n, n) or a.shape[0] != (1 if shared_nest else nb):
+            raise ValueError("transformations [nb, %d, %d, 2] and %s, got %s and %s"
+                             % (n, n, "one nest" if shared_nest else "one nest each", t.shape, a.shape))
+        off = np.zeros(nb * n + 1, dtype=np.int64)
+        ok, steps, kind = (np.zeros(nb, dtype=np.int32) for _ in range(3))
+        det = np.zeros((nb, 2), dtype=np.int32) if mode == 0 else None
+        mult = np.zeros((nb, n, n, 2), dtype=np.int32)
+        if nb == 0:
+            return ok, steps, kind, det, mult, []
+        view = C.c_void_p()
+        self.ctx.check(lib().xpg_lineq_transform_levels_batch_packed_rat32(
+            self.ctx._h, C.c_int(nb), vp(a), C.c_int(int(shared_nest)), vp(t), C.c_int(rows), C.c_int(cols), C.c_int(n), C.c_int(mode),
+            C.c_int(cap_rows or 0), C.c_int(cap_out_rows or 0), None, C.c_longlong(0), C.byref(view), vp(off), vp(ok), vp(steps),
+            vp(kind), vp(det), vp(mult)), "xpg_lineq_transform_levels_batch_packed_rat32")
+        res = _cut(_rows_down(view, int(off[-1]), (cols, 2), copy), off)
+        return ok, steps, kind, det, mult, _nest(res, _every(n, nb))
+
+    @staticmethod
+    def transform_last_route():
+        """xpg_lineq_transform_last_route of the calling thread's last transformed-nest call, as a dict."""
+        return _view("xpg_lineq_transform_last_route", Lineq.PROJECT_ROUTE_KEYS + ("level_bytes",))
+
     def _chain_ragged(self, levels, mats_list, rhs_idx, elims, darkshadow, cap_rows, cap_out_rows, copy):
         """xpg_lineq_{project,levels}_batch_ragged_rat32: (ok[nb], steps[nb], results) with results[r] the rows of result r --
         one per system, or (levels) one per list entry, level k of system b at elim_offsets[b] + k -- and the offsets of the
@@ -547,6 +581,18 @@ def levels_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, elim, darkshadow, cap_row
                                                      C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr),
                                                      C.c_void_p(out_rows_ptr), C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr)),
               "xpg_lineq_levels_batch_rat32_dev")
+
+
+def transform_levels_dev(ctx, nb, nests_ptr, shared_nest, tmats_ptr, rows, cols, rhs_idx, mode, cap_rows, cap_out_rows, outs_ptr,
+                         out_rows_ptr, out_ok_ptr, out_steps_ptr, out_kind_ptr, out_det_ptr, out_mult_ptr):
+    """xpg_lineq_transform_levels_batch_rat32_dev: the limits of transformed loop nests on device arrays in one launch, enqueue
+    only. outs is [nb][rhs_idx][cap_out_rows][cols] (level 0 the transformed nest), out_rows [nb][rhs_idx], ok / steps / kind
+    [nb], det [nb] (mode 0), mult [nb][rhs_idx][rhs_idx]. Both capacities are the caller's: none is defaulted."""
+    ctx.check(lib().xpg_lineq_transform_levels_batch_rat32_dev(
+        ctx._h, C.c_int(nb), C.c_void_p(nests_ptr), C.c_int(int(shared_nest)), C.c_void_p(tmats_ptr), C.c_int(rows), C.c_int(cols),
+        C.c_int(rhs_idx), C.c_int(mode), C.c_int(cap_rows), C.c_int(cap_out_rows), C.c_void_p(outs_ptr), C.c_void_p(out_rows_ptr),
+        C.c_void_p(out_ok_ptr), C.c_void_p(out_steps_ptr), C.c_void_p(out_kind_ptr), C.c_void_p(out_det_ptr), C.c_void_p(out_mult_ptr)),
+        "xpg_lineq_transform_levels_batch_rat32_dev")
 
 
 def bounds_dev(ctx, nb, mats_ptr, rows, cols, rhs_idx, cap_rows, cap_out_rows, outs_ptr, out_rows_ptr, out_ok_ptr, out_chain_ptr,
