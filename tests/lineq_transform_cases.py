@@ -2,7 +2,9 @@
 transformed-nest call (lineq_host.hip.h transform_plan: the levels' plan with rhs_idx slots a system, a level's slot no smaller
 than the nest, and the place of the inverse's scratch), the nests and transformations of the cases, and the composed checker --
 oracle/checker.py's rat_det and rat_inv, its rat_op cell by cell in the order of the reference's operator* (src/com/matt.h:60-79),
-and lineq_levels_cases.stepped_levels over the list rhs_idx-1 .. 1 -- with an independent check in fractions.Fraction."""
+and lineq_levels_cases.stepped_levels over the list rhs_idx-1 .. 1 -- with an independent check in fractions.Fraction. These
+cases keep the Rational exact on purpose; the nests and transformations that make it approximate live in
+tests/lineq_rescue_cases.py, tests/test_lineq_rescue_host.py and tests/test_gpu_lineq_rescue.py."""
 from fractions import Fraction
 
 import numpy as np

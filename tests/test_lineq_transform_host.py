@@ -113,7 +113,9 @@ def test_shape_and_mode_refusals_need_no_handle():
 
 def test_the_cases_never_make_the_rational_approximate(port):
     """Every nest and transformation of the cases through the composed checker (the real reference too where its build is
-    present): entries stay within |.| <= 3, appro_count() does not move, and what comes out passes the exact check."""
+    present): entries stay within |.| <= 3, appro_count() does not move, and what comes out passes the exact check. The cases
+    that DO make it approximate live in tests/lineq_rescue_cases.py, held by tests/test_lineq_rescue_host.py and
+    tests/test_gpu_lineq_rescue.py."""
     from oracle.checker import Ref
     for lib in [port] + ([Ref()] if Ref.available() else []):
         for n in (1, 2, 3, 4):
